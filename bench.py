@@ -8,12 +8,20 @@ the full drop-in history (2S+1 = 19 planes) stored as float32 (BASELINE precisio
 input rays float64 as the generator makes them, so the history is the reference's rounded once).  A timed
 step = one launch of the fused trace kernel (rtpb_trace through the C ABI: the body of System.ray_trace,
 RT:641-661) on the GPU's bundle, the plan lowered once before the timed region, inputs and outputs
-resident in HBM.  The whole drop-in call System.ray_trace(torch rays, ...) -- lowering, table keys of the
-Ebaf11 crown (MAT:128-144), output allocation, launch -- is timed separately as `e2e_ms`.
+resident in HBM.
 Multi-GPU: one process per GPU (torchrun), each traces its own C3 bundle (rays are independent: no
 data-path collective) -> weak scaling; the job time is the max over ranks.
 
-The same JSON line carries the other BASELINE configs under "configs":
+A plain run does only what the headline figure needs: set up, W warmup steps, K timed steps, the JSON line
+(value, ms_per_step, the roofline fraction of the timed launches).  `--dump-outputs DIR` then writes what the
+last timed step computed: DIR/history_sample.npy, the full history (planes, rays, 8) of a fixed, seeded sample
+of the rays, and DIR/history_sample_rays.npy, their indices into the bundle (the inputs are the same in every
+run, so two builds compare output for output).
+
+`--full` adds everything else, each a measurement of its own after the timed steps: the whole drop-in call
+System.ray_trace(torch rays, ...) -- lowering, table keys of the Ebaf11 crown (MAT:128-144), output
+allocation, launch -- as `e2e_ms`, the placement check, fill / copy rates and PMC traffic of the roofline,
+and the other BASELINE configs under "configs":
   configs[1] C2  AC508-100-B achromat, 1M rays, float64 history (rank 0, N=1 only)
   configs[3] C4  ideal OPM (scripts/2022_01_25_ray_trace_ideal_opm.py:59-92): the 10001 x 10000 fan
                  (100,010,000 rays, 11 surfaces, 23-plane float32 history) STRONG-scaled over the ranks:
@@ -25,7 +33,8 @@ and `cpu_baseline` (N=1, rank 0): oracle/rt_refcost.py -- the reference's algori
 calibrated against the reference in tests/golden/cpu_calibration.json -- timed on this host on a bounded
 sample of C3, plus C1 (BASELINE configs[0], the plano-convex CPU case).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--config c3|c2] [--configs c2,c4,c5 | none]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--config c3|c2] [--dump-outputs DIR]
+    python bench.py --full [... --configs c2,c4,c5 | none] [--cpu-baseline off] [--traffic off] [--extras off]
     torchrun --nproc-per-node N bench.py --gpus N ...
 
 `python bench.py --gpus N` (N > 1) outside torchrun starts `torch.distributed.run --nproc-per-node N` on
@@ -49,6 +58,7 @@ UNIT = "ray-surface intersections/s"
 HBM_PEAK_GBS = 8000.0          # MI355X HBM3E spec (MI355X_MICROARCH.md)
 F64_VALU_PEAK_TFLOPS = 78.6    # MI355X FP64 vector: 1/2 of the 157.3 TFLOP/s FP32 vector peak (MI355X_MICROARCH.md:41)
 SEED = 20241008
+DUMP_BYTES = 48 << 20          # --dump-outputs: history bytes of the sampled rays (the whole dump stays below 64 MB)
 C3_FAN = (3163, 3162)          # scripts/2024_08_08_achromat_imaging.py fan at 10M rays per field
 C3_CPU_FAN = (448, 447)        # CPU-baseline sample of C3: 5 fields x 200,256 rays
 C4_FAN = (10001, 10000)        # scripts/2022_01_25_ray_trace_ideal_opm.py:59-92
@@ -70,13 +80,21 @@ def shard_seed(rank):
     return SEED + 7919 * rank
 
 
-def parse():
+def parse(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=100)
     ap.add_argument("--warmup", type=int, default=10)
     ap.add_argument("--config", default="c3", choices=["c3", "c2", "c4", "c5", "c5_1wl"],
                     help="headline workload (c5, c5_1wl: --pmc-child only)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline figure does not need: the other BASELINE configs, the CPU "
+                         "baseline, PMC traffic, fill / copy rates, the placement check and the drop-in calls "
+                         "(--configs, --cpu-baseline, --traffic and --extras select among them; without --full all "
+                         "are off)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the last step's history of a fixed, seeded sample of the rays "
+                         "to DIR/history_sample.npy and the sample's ray indices to DIR/history_sample_rays.npy")
     ap.add_argument("--configs", default="c2,c4,c5", help="other BASELINE configs in the same line ('none')")
     ap.add_argument("--scale", type=float, default=1.0, help="c3 / c4: fraction of the per-axis fan sizes")
     ap.add_argument("--rays", type=int, default=1_000_000, help="c2: rays per GPU")
@@ -92,7 +110,12 @@ def parse():
                     help="allow --gpus N above the visible GPU count (ranks share GPUs: a rehearsal, not a measurement)")
     ap.add_argument("--pmc-child", action="store_true", help=argparse.SUPPRESS)
     ap.add_argument("--pmc-shard", default="0,1", help=argparse.SUPPRESS)       # rank,world of a c4 PMC child
-    return ap.parse_args()
+    args = ap.parse_args(argv)
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    if not args.full:
+        args.configs, args.cpu_baseline, args.traffic, args.extras = "none", "off", "off", "off"
+    return args
 
 
 def dist_env():
@@ -240,6 +263,24 @@ class Workload:
         ev1.record()
         torch.cuda.synchronize()
         return ev0.elapsed_time(ev1) / steps, time.perf_counter() - t0
+
+    def dump_outputs(self, d, suffix=""):
+        """Write the history the last step left in the output buffer, for a fixed, seeded sample of the rays
+        (at most DUMP_BYTES of history; every ray of a smaller bundle): d/history_sample.npy (planes, K, 8) in
+        the storage dtype, and d/history_sample_rays.npy, the K ray indices (float64, ascending)."""
+        import torch
+        per_ray = len(self.planes) * 8 * self.out.element_size()
+        k = min(self.n, DUMP_BYTES // per_ray)
+        idx = np.sort(np.random.default_rng(SEED).choice(self.n, size=k, replace=False)) if k < self.n \
+            else np.arange(self.n)
+        idx_t = torch.from_numpy(idx).to(self.out.device)
+        torch.cuda.synchronize()
+        # plane by plane: a plane of the largest history stays below 2^31 elements
+        sample = torch.stack([self.out[p].index_select(0, idx_t) for p in range(self.out.shape[0])]).cpu().numpy()
+        os.makedirs(d, exist_ok=True)
+        np.save(os.path.join(d, f"history_sample{suffix}.npy"), sample)
+        np.save(os.path.join(d, f"history_sample_rays{suffix}.npy"), idx.astype(np.float64))
+        return sample.shape
 
     def second_buffer(self, steps):
         """Average launch duration (ms) of the same trace into a history allocated by torch's default
@@ -816,7 +857,10 @@ def main():
     # so the closing barrier's own latency is not charged to the K steps
     kernel_ms, elapsed = wl.timed(args.steps)
     _barrier(world)
-    fill = wl.fill_rate() if rank == 0 else None
+    if args.dump_outputs:
+        shape = wl.dump_outputs(args.dump_outputs, f"_rank{rank}" if world > 1 else "")
+        _log(f"rank {rank}: history sample {shape} written to {args.dump_outputs}")
+    fill = wl.fill_rate() if (args.full and rank == 0) else None
     extras = args.extras == "on"
     alt_ms = wl.second_buffer(args.steps) if (extras and world == 1 and args.config in ("c3", "c2")) else None
     e2e_ms, e2e_kernel_ms = wl.e2e() if (extras and args.config == "c3") else (None, None)
@@ -833,7 +877,7 @@ def main():
     del wl
     torch.cuda.empty_cache()
     _trim_buffers()
-    copy = stream_copy_rate(dev) if rank == 0 else None
+    copy = stream_copy_rate(dev) if (args.full and rank == 0) else None
 
     line = None
     if rank == 0:
@@ -847,7 +891,7 @@ def main():
             "metric": METRIC, "value": value, "unit": UNIT, "n_gpus": world, "steps": args.steps,
             "warmup": args.warmup, "ms_per_step": ms_per_step, "higher_is_better": True, "scaling": "weak",
             "vs_baseline": None, "dtype": "f64", "storage_dtype": "f32" if head.code != 0 else "f64",
-            "data": "synthetic",
+            "data": "synthetic", "full": args.full,
             "config": {"workload": head.workload, "baseline_config": "configs[2]" if args.config == "c3" else None,
                        "storage": head.storage, "rays_per_gpu": head.n, "surfaces": head.S,
                        "planes_stored": len(head.planes), "layout": "aos",

@@ -85,6 +85,21 @@ def test_bench_gpus_n_without_gpus_fails_before_launching():
     assert r.stdout.strip() == ""
 
 
+def test_plain_run_measures_the_headline_only_and_full_adds_the_rest():
+    """Without --full every further measurement is off, whatever selects among them; --full keeps their defaults
+    and their switches; --steps / --warmup are taken as given."""
+    import pytest
+    a = bench.parse(["--gpus", "1", "--steps", "7", "--warmup", "3", "--configs", "c2", "--dump-outputs", "d"])
+    assert (a.steps, a.warmup, a.full, a.dump_outputs) == (7, 3, False, "d")
+    assert (a.configs, a.cpu_baseline, a.traffic, a.extras) == ("none", "off", "off", "off")
+    f = bench.parse(["--full", "--steps", "7"])
+    assert f.full and f.steps == 7 and f.dump_outputs is None
+    assert (f.configs, f.cpu_baseline, f.traffic, f.extras) == ("c2,c4,c5", "auto", "auto", "on")
+    assert bench.parse(["--full", "--configs", "c2", "--traffic", "off"]).configs == "c2"
+    with pytest.raises(SystemExit):
+        bench.parse(["--steps", "0"])
+
+
 def test_strong_scaling_fields():
     """configs.c4 / configs.c5 of an N > 1 line carry their own t1 (rank 0 alone, same job) and efficiency
     t1 / (N tN) (VERDICT r05 #5)."""
