@@ -39,7 +39,7 @@
 extern "C" {
 #endif
 
-#define RTPB_ABI_VERSION 9   /* 2: + *_tables generators, surface-hook kernels, sorted-table lookup
+#define RTPB_ABI_VERSION 10  /* 2: + *_tables generators, surface-hook kernels, sorted-table lookup
                                 3: input element type separate from the storage type (in_dtype)
                                 4: + rtpb_trace_checked (table-miss flag)
                                 5: + rtpb_buffer_alloc / _free / _dlpack (placement-robust history buffers)
@@ -53,7 +53,8 @@ extern "C" {
                                    rtpb_oneshot_plans / rtpb_oneshot_clear; freeing a library buffer
                                    never synchronises the device (retired mappings are released by the
                                    next allocation that maps new memory, or by rtpb_buffer_trim)
-                                9: + rtpb_trace_packed (rtpb_trace_checked's arguments in one struct) */
+                                9: + rtpb_trace_packed (rtpb_trace_checked's arguments in one struct)
+                                10: + rtpb_focus_stats / rtpb_focus_sweep (through-focus statistics) */
 
 /* ---- error codes ---------------------------------------------------------------------------- */
 #define RTPB_OK 0
@@ -368,6 +369,28 @@ int rtpb_spot_sweep(const rtpb_plan* plan, int32_t device, int64_t n_groups, con
                     int64_t n_thetas, int64_t nphis, const double center_ray[3], const double ex[3],
                     const double ey[3], const double* theta_cos_sin, const double* phi_cos_sin, double* workspace,
                     int64_t workspace_len, double* stats_out, void* stream);
+
+/* Focus statistics of one (N, 8) AOS plane, per group as rtpb_spot_stats: the through-focus analysis of a
+   bundle without tracing it again.  With the slopes u = dx / dz and v = dy / dz (IEEE division) a ray meets
+   the plane displaced by delta along z at (x + u delta, y + v delta), so the RMS spot radius there is an
+   exact quadratic in delta whose coefficients are second moments of (x, y, u, v).  A ray counts when x, y,
+   u and v are all finite (dz = 0 and NaN or infinite directions drop it).
+   stats_out (device, n_groups x 16 doubles): count, sum x, y, z, x^2, y^2, x*y (rtpb_spot_stats' columns, and
+   its values bit for bit while every ray with finite x and y has finite slopes), then sum u, v, u^2, v^2,
+   u*v, x*u, y*v, x*v, y*u.  The same fixed-order two-pass reduction.  workspace: device doubles,
+   >= n_groups * ceil(group_size / 256) * 16.  The arguments are checked before the device is. */
+int rtpb_focus_stats(int32_t device, int32_t dtype, const void* plane, int64_t group_size, int64_t n_groups,
+                     double* workspace, int64_t workspace_len, double* stats_out, void* stream);
+
+/* Fused through-focus sweep: rtpb_spot_sweep with the 16 statistics of rtpb_focus_stats taken from each ray's
+   final position and direction -- the same arguments, row planning and kernel.  workspace: device doubles,
+   >= n_groups * ceil(n_thetas*nphis / 256) * 16.  stats_out: device, n_groups x 16.  The statistics are
+   bit-identical to rtpb_ray_fan_tables + rtpb_trace (final plane) + rtpb_focus_stats in the plan's storage
+   type.  The focus they describe lies along z: the last surface should be an image plane normal to z. */
+int rtpb_focus_sweep(const rtpb_plan* plan, int32_t device, int64_t n_groups, const double* group_params,
+                     int64_t n_thetas, int64_t nphis, const double center_ray[3], const double ex[3],
+                     const double ey[3], const double* theta_cos_sin, const double* phi_cos_sin, double* workspace,
+                     int64_t workspace_len, double* stats_out, void* stream);
 
 /* ---- pupil-phase interpolation (scripts/2022_02_06_perfect_imaging_system_psf.py:90-105) */
 /* A 2-D Delaunay triangulation with one value per vertex, in scipy.spatial.Delaunay's representation,

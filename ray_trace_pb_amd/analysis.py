@@ -13,10 +13,12 @@ from . import _capi as C
 from . import _engine as E
 
 STAT_NAMES = ("count", "sum_x", "sum_y", "sum_z", "sum_xx", "sum_yy", "sum_xy")
+# the spot sums, then the moments of the slopes u = dx/dz, v = dy/dz (rtpb_focus_stats / rtpb_focus_sweep)
+FOCUS_STAT_NAMES = STAT_NAMES + ("sum_u", "sum_v", "sum_uu", "sum_vv", "sum_uv", "sum_xu", "sum_yv", "sum_xv",
+                                 "sum_yu")
 
 
-def spot_stats_raw(plane, group_size, stream=None):
-    """Per-group sums (n_groups, 7) of a torch CUDA (N, 8) plane, N = n_groups * group_size."""
+def _plane_stats_raw(entry, ncols, plane, group_size, stream):
     import torch
     n = plane.shape[0]
     if n % group_size:
@@ -24,15 +26,26 @@ def spot_stats_raw(plane, group_size, stream=None):
     ngroups = n // group_size
     plane = plane.contiguous()
     tiles = -(-group_size // 256)
-    ws = torch.empty(ngroups * tiles * 7, dtype=torch.float64, device=plane.device)
-    stats = torch.empty((ngroups, 7), dtype=torch.float64, device=plane.device)
+    ws = torch.empty(ngroups * tiles * ncols, dtype=torch.float64, device=plane.device)
+    stats = torch.empty((ngroups, ncols), dtype=torch.float64, device=plane.device)
     if stream is None:
         stream = torch.cuda.current_stream(plane.device).cuda_stream
-    C.check(C.lib().rtpb_spot_stats(plane.device.index or 0,
+    C.check(getattr(C.lib(), entry)(plane.device.index or 0,
                                     C.RTPB_F64 if plane.dtype == torch.float64 else C.RTPB_F32,
                                     plane.data_ptr(), group_size, ngroups, ws.data_ptr(), ws.numel(),
                                     stats.data_ptr(), stream))
     return stats
+
+
+def spot_stats_raw(plane, group_size, stream=None):
+    """Per-group sums (n_groups, 7) of a torch CUDA (N, 8) plane, N = n_groups * group_size."""
+    return _plane_stats_raw("rtpb_spot_stats", 7, plane, group_size, stream)
+
+
+def focus_stats_raw(plane, group_size, stream=None):
+    """Per-group focus sums (n_groups, 16; ``FOCUS_STAT_NAMES``) of a torch CUDA (N, 8) plane -- any history
+    plane, e.g. ``h[-1]``.  A ray counts when x, y and both slopes dx/dz, dy/dz are finite."""
+    return _plane_stats_raw("rtpb_focus_stats", 16, plane, group_size, stream)
 
 
 def summarize(raw):
@@ -47,9 +60,73 @@ def summarize(raw):
             "raw": raw}
 
 
+def summarize_focus(raw):
+    """Through-focus summary from the 16 raw focus sums (``FOCUS_STAT_NAMES``; host, NumPy).
+
+    A ray at (x, y) with slopes u = dx/dz, v = dy/dz meets the plane displaced by dz along z at
+    (x + u dz, y + v dz), so the squared RMS radius about the centroid is C_xx + C_yy + 2 dz A + dz^2 B with
+    A = C_xu + C_yv and B = C_uu + C_vv -- exact for the traced bundle, no ray traced twice.  Returns
+    ``count``, ``centroid``, ``rms_radius`` and ``raw`` as :func:`summarize` gives them from columns 0-6, and
+
+    - ``mean_slope`` (..., 2) and ``cov`` (..., 4, 4), the covariance of (x, y, u, v), each entry
+      S_ab / n - mean_a * mean_b;
+    - ``defocus`` = -A / B, the displacement of the least-squares best-focus plane (NaN where B is not positive),
+      ``best_focus_z`` = sum_z / n + defocus and ``rms_radius_best``, the RMS radius there;
+    - ``focus_x_z`` / ``focus_y_z``, the line foci (sum_z / n - C_xu / C_uu and the y counterpart), and
+      ``astigmatism`` = focus_x_z - focus_y_z.
+
+    The focus quantities describe the bundle where the plane it was taken on is normal to z.  A collimated bundle
+    (``c4_system``'s output) has B at rounding level: its foci are meaningless or NaN, and no threshold is applied
+    here.  Groups without rays give NaN."""
+    raw = np.asarray(raw, dtype=np.float64)
+    out = summarize(raw[..., :7])
+    out["raw"] = raw
+    n = raw[..., 0]
+    col = {k: raw[..., i] for i, k in enumerate(FOCUS_STAT_NAMES)}
+    with np.errstate(invalid="ignore", divide="ignore"):
+        mean = {"x": col["sum_x"] / n, "y": col["sum_y"] / n, "u": col["sum_u"] / n, "v": col["sum_v"] / n}
+        cov = np.empty(raw.shape[:-1] + (4, 4))
+        for i, a in enumerate("xyuv"):
+            for j, b in enumerate("xyuv"):
+                s = col.get("sum_" + a + b, col.get("sum_" + b + a))
+                cov[..., i, j] = s / n - mean[a] * mean[b]
+        A = cov[..., 0, 2] + cov[..., 1, 3]
+        B = cov[..., 2, 2] + cov[..., 3, 3]
+        defocus = np.where(B > 0, -A / B, np.nan)
+        zbar = col["sum_z"] / n
+        fx = zbar - cov[..., 0, 2] / cov[..., 2, 2]
+        fy = zbar - cov[..., 1, 3] / cov[..., 3, 3]
+        best = np.sqrt(np.maximum(cov[..., 0, 0] + cov[..., 1, 1] - A * A / B, 0.0))
+    out.update(mean_slope=np.stack((mean["u"], mean["v"]), axis=-1), cov=cov, defocus=defocus,
+               best_focus_z=zbar + defocus, rms_radius_best=np.where(B > 0, best, np.nan), focus_x_z=fx,
+               focus_y_z=fy, astigmatism=fx - fy)
+    return out
+
+
+def rms_radius_at(summary, dz):
+    """The through-focus curve: RMS spot radius on the plane displaced by ``dz`` along z from the plane the
+    summary (:func:`summarize_focus`) was taken on; ``dz`` broadcasts over the groups."""
+    cov = summary["cov"]
+    dz = np.asarray(dz, dtype=np.float64)
+    A = cov[..., 0, 2] + cov[..., 1, 3]
+    B = cov[..., 2, 2] + cov[..., 3, 3]
+    with np.errstate(invalid="ignore"):
+        return np.sqrt(np.maximum(cov[..., 0, 0] + cov[..., 1, 1] + 2.0 * dz * A + dz * dz * B, 0.0))
+
+
 def spot_stats(plane, group_size):
     """Spot summary per contiguous group of ``group_size`` rays of a torch CUDA (N, 8) plane."""
     return summarize(spot_stats_raw(plane, group_size).cpu().numpy())
+
+
+def focus_stats(plane, group_size):
+    """Through-focus summary per contiguous group of ``group_size`` rays of a torch CUDA (N, 8) plane."""
+    return summarize_focus(focus_stats_raw(plane, group_size).cpu().numpy())
+
+
+# the two sweeps: (fused entry point, unfused plane reduction, columns, host summary)
+_SPOT = ("rtpb_spot_sweep", spot_stats_raw, 7, summarize)
+_FOCUS = ("rtpb_focus_sweep", focus_stats_raw, 16, summarize_focus)
 
 
 def spot_sweep(system, initial_material, final_material, field_points, wavelengths, theta_max, n_thetas, nphis=1,
@@ -64,7 +141,45 @@ def spot_sweep(system, initial_material, final_material, field_points, wavelengt
     give bit-identical statistics.  ``devices`` (fused only): the (field, wavelength) groups are split into
     contiguous ranges, one per GPU, swept concurrently from this thread (per-device kernel times in the
     timing dict).  Returns (summary dict with arrays shaped (n_fields, n_wavelengths, ...), timing dict)."""
+    return _sweep(_SPOT, system, initial_material, final_material, field_points, wavelengths, theta_max, n_thetas,
+                  nphis, center_ray, device, dtype, groups_per_batch, fused, devices)
+
+
+def _image_plane_normal_to_z(system):
+    from .raytrace import FlatSurface, PlaneMirror
+    last = system.surfaces[-1] if len(system.surfaces) else None
+    if not isinstance(last, (FlatSurface, PlaneMirror)):
+        return False
+    n = np.asarray(last.normal, dtype=float).ravel()
+    return n.shape == (3,) and n[0] == 0 and n[1] == 0 and abs(n[2]) == 1
+
+
+def focus_sweep(system, initial_material, final_material, field_points, wavelengths, theta_max, n_thetas, nphis=1,
+                center_ray=(0, 0, 1), device="cuda:0", dtype="float64", groups_per_batch=None, fused=True,
+                devices=None, require_image_plane=True):
+    """Through-focus analysis for every (field point, wavelength): :func:`spot_sweep`'s fans, with the 16 focus
+    sums taken from each ray's final position and direction in the same pass (``rtpb_focus_sweep``, or with
+    ``fused=False`` fan generation -> trace planes='final' -> ``rtpb_focus_stats``; bit-identical).  Returns
+    (:func:`summarize_focus` summary with arrays shaped (n_fields, n_wavelengths, ...), timing dict as
+    :func:`spot_sweep`'s): best focus, the RMS radius there, the line foci and astigmatism per group, the focal
+    shift between wavelengths as differences of ``best_focus_z``, the whole curve from :func:`rms_radius_at`.
+
+    The focus is sought along z from the last surface.  ``require_image_plane=True`` (default) raises
+    ``ValueError`` unless that surface is a ``FlatSurface`` or ``PlaneMirror`` with normal exactly (0, 0, +-1);
+    with ``False`` the raw moments are returned for any system, and the focus quantities describe the bundle only
+    as far as the last surface is a z-plane."""
+    if require_image_plane and not _image_plane_normal_to_z(system):
+        raise ValueError("focus_sweep: the last surface must be an image plane normal to z (a FlatSurface or "
+                         "PlaneMirror with normal (0, 0, +-1)); append an image plane to the system, or pass "
+                         "require_image_plane=False for the raw moments on the last surface")
+    return _sweep(_FOCUS, system, initial_material, final_material, field_points, wavelengths, theta_max, n_thetas,
+                  nphis, center_ray, device, dtype, groups_per_batch, fused, devices)
+
+
+def _sweep(kind, system, initial_material, final_material, field_points, wavelengths, theta_max, n_thetas, nphis,
+           center_ray, device, dtype, groups_per_batch, fused, devices):
     import torch
+    entry, plane_raw, ncols, summary = kind
     dev = torch.device(device)
     tdt = torch.float64 if dtype in ("float64", np.float64) else torch.float32
     code = C.RTPB_F64 if tdt == torch.float64 else C.RTPB_F32
@@ -83,7 +198,7 @@ def spot_sweep(system, initial_material, final_material, field_points, wavelengt
     if fused:
         devs = [dev] if devices is None else [torch.device("cuda", int(d)) for d in devices]
         return _spot_sweep_fused(low, S, field_points, wavelengths, theta_max, n_thetas, nphis, center_ray, devs,
-                                 groups_per_batch)
+                                 groups_per_batch, entry, ncols, summary)
     if devices is not None:
         raise ValueError("devices= needs the fused sweep")
     if groups_per_batch is None:
@@ -91,7 +206,7 @@ def spot_sweep(system, initial_material, final_material, field_points, wavelengt
     sel = E.resolve_planes("final", len(system.surfaces))
     rays = torch.empty((groups_per_batch * per, 8), dtype=tdt, device=dev)
     out = torch.empty((1, groups_per_batch * per, 8), dtype=tdt, device=dev)
-    raw = np.zeros((G, 7))
+    raw = np.zeros((G, ncols))
     jobs = [(f, w) for f in range(field_points.shape[0]) for w in range(wavelengths.size)]
     torch.cuda.synchronize(dev)
     t0 = time.perf_counter()
@@ -102,15 +217,17 @@ def spot_sweep(system, initial_material, final_material, field_points, wavelengt
                       center_ray, code)
         m = len(batch) * per
         E.trace_device(low, rays[:m], sel, out=out[:, :m])
-        raw[b0:b0 + len(batch)] = spot_stats_raw(out[0, :m], per).cpu().numpy()
+        raw[b0:b0 + len(batch)] = plane_raw(out[0, :m], per).cpu().numpy()
     torch.cuda.synchronize(dev)
     dt = time.perf_counter() - t0
-    summ = summarize(raw.reshape(field_points.shape[0], wavelengths.size, 7))
+    summ = summary(raw.reshape(field_points.shape[0], wavelengths.size, ncols))
     return summ, {"seconds": dt, "rays": G * per, "ray_surface_per_s": G * per * S / dt}
 
 
 def _spot_sweep_fused(low, S, field_points, wavelengths, theta_max, n_thetas, nphis, center_ray, devs,
-                      groups_per_batch):
+                      groups_per_batch, entry="rtpb_spot_sweep", ncols=7, summary=summarize):
+    """The fused sweep of both statistics sets: ``entry`` is the C entry point (``rtpb_spot_sweep`` /
+    ``rtpb_focus_sweep``), ``ncols`` its statistics per group, ``summary`` the host summary of the raw sums."""
     import torch
     from .raytrace import _fan_tables, shard_bounds
     c = np.array(center_ray)
@@ -123,7 +240,7 @@ def _spot_sweep_fused(low, S, field_points, wavelengths, theta_max, n_thetas, np
     per = n_thetas * nphis
     tiles = -(-per // 256)
     if groups_per_batch is None:
-        groups_per_batch = max(1, min(G, 65535, (1 << 26) // (tiles * 7)))   # workspace <= 512 MB
+        groups_per_batch = max(1, min(G, 65535, (1 << 26) // (tiles * ncols)))   # workspace <= 512 MB
         # whole field points per batch: a field point's groups share each ray's generation and first surface
         # (the kernel's bundle rows), so batches do not split them
         if groups_per_batch >= nw:
@@ -137,13 +254,14 @@ def _spot_sweep_fused(low, S, field_points, wavelengths, theta_max, n_thetas, np
         bounds = shard_bounds(G, len(devs))
     work = []
     for (g0, g1), dev in zip(bounds, devs):
-        ws = torch.empty(groups_per_batch * tiles * 7, dtype=torch.float64, device=dev)
-        stats = torch.empty((max(g1 - g0, 1), 7), dtype=torch.float64, device=dev)
+        ws = torch.empty(groups_per_batch * tiles * ncols, dtype=torch.float64, device=dev)
+        stats = torch.empty((max(g1 - g0, 1), ncols), dtype=torch.float64, device=dev)
         ev = (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
         work.append((dev, g0, g1, ws, stats, ev, torch.cuda.current_stream(dev)))
     for dev in devs:
         torch.cuda.synchronize(dev)
     t0 = time.perf_counter()
+    sweep = getattr(C.lib(), entry)
     with E.plan_ref(low) as plan:
         for dev, g0, g1, ws, stats, ev, st in work:
             ev[0].record(st)
@@ -156,10 +274,10 @@ def _spot_sweep_fused(low, S, field_points, wavelengths, theta_max, n_thetas, np
                 if b0 >= b1:
                     continue
                 gp = np.ascontiguousarray(params[b0:b1])
-                C.check(C.lib().rtpb_spot_sweep(plan, dev.index or 0, b1 - b0, gp.ctypes.data, int(n_thetas),
-                                                int(nphis), vec[0].ctypes.data, vec[1].ctypes.data,
-                                                vec[2].ctypes.data, tcs.ctypes.data, pcs.ctypes.data, ws.data_ptr(),
-                                                ws.numel(), stats[b0 - g0:b1 - g0].data_ptr(), st.cuda_stream))
+                C.check(sweep(plan, dev.index or 0, b1 - b0, gp.ctypes.data, int(n_thetas), int(nphis),
+                              vec[0].ctypes.data, vec[1].ctypes.data, vec[2].ctypes.data, tcs.ctypes.data,
+                              pcs.ctypes.data, ws.data_ptr(), ws.numel(), stats[b0 - g0:b1 - g0].data_ptr(),
+                              st.cuda_stream))
         for dev, g0, g1, ws, stats, ev, st in work:
             ev[1].record(st)
         raw = np.concatenate([stats[:g1 - g0].cpu().numpy() for _, g0, g1, _, stats, _, _ in work])
@@ -169,11 +287,11 @@ def _spot_sweep_fused(low, S, field_points, wavelengths, theta_max, n_thetas, np
         ms = ev[0].elapsed_time(ev[1])
         # HBM bytes of the fused sweep: the per-tile partial sums written and read back (the rays never
         # leave the registers)
-        nbytes = (g1 - g0) * tiles * 7 * 8 * 2 + (g1 - g0) * 7 * 8
+        nbytes = (g1 - g0) * tiles * ncols * 8 * 2 + (g1 - g0) * ncols * 8
         per_dev.append({"device": dev.index or 0, "groups": g1 - g0, "rays": (g1 - g0) * per, "kernel_ms": ms,
                         "ray_surface_per_s": (g1 - g0) * per * S / (ms * 1e-3) if ms > 0 else None,
                         "hbm_bytes": nbytes, "hbm_GBps": nbytes / (ms * 1e-3) / 1e9 if ms > 0 else None})
-    summ = summarize(raw.reshape(nf, nw, 7))
+    summ = summary(raw.reshape(nf, nw, ncols))
     return summ, {"seconds": dt, "rays": G * per, "ray_surface_per_s": G * per * S / dt, "per_device": per_dev}
 
 

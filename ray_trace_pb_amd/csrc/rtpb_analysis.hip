@@ -57,6 +57,47 @@ __global__ __launch_bounds__(kBlock) void intersect_kernel(IsectArgs a) {
 // pass 1 reduces each 256-ray tile of a group in a fixed tree order into partials[group][tile];
 // pass 2 sums a group's partials in a fixed order.  Stats: n, Sx, Sy, Sz, Sxx, Syy, Sxy.
 constexpr int kStats = 7;
+
+// Focus statistics (through-focus analysis): the seven spot sums, then the sums of u, v, u u, v v, u v, x u, y v,
+// x v, y u with the slopes u = dx / dz and v = dy / dz (IEEE division).  On a plane displaced by delta along z the ray
+// is at (x + u delta, y + v delta), so the RMS spot radius is an exact quadratic in delta whose coefficients are these
+// second moments: best focus, the line foci and the through-focus curve follow on the host (analysis.summarize_focus).
+// The one definition of a ray's contribution, for the plane kernel and the fused sweep alike: the arguments are the
+// ray's final state rounded to the storage type; a ray counts when x, y, u and v are all finite (dz = 0 and NaN or
+// infinite directions drop it); each product is one rounded multiply.
+// focus_ray gives the counted ray as (n, x, y, z, u, v) with n = 1, or all +0 for a ray that does not count, and
+// focus_term its k-th statistic: a dropped ray's products are +0 * +0 = +0, so the kernels carry six values per ray
+// to the reduction and form the products chunk by chunk instead of holding sixteen.
+constexpr int kFocusStats = 16;
+struct FocusRay {
+    double n, x, y, z, u, v;
+};
+RTPB_HD FocusRay focus_ray(double x, double y, double z, double dx, double dy, double dz) {
+    const double u = dx / dz, v = dy / dz;
+    if (x - x == 0.0 && y - y == 0.0 && u - u == 0.0 && v - v == 0.0) return FocusRay{1.0, x, y, z, u, v};
+    return FocusRay{0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+}
+RTPB_HD double focus_term(const FocusRay& f, int k) {
+    switch (k) {
+    case 0: return f.n;
+    case 1: return f.x;
+    case 2: return f.y;
+    case 3: return f.z;
+    case 4: return f.x * f.x;
+    case 5: return f.y * f.y;
+    case 6: return f.x * f.y;
+    case 7: return f.u;
+    case 8: return f.v;
+    case 9: return f.u * f.u;
+    case 10: return f.v * f.v;
+    case 11: return f.u * f.v;
+    case 12: return f.x * f.u;
+    case 13: return f.y * f.v;
+    case 14: return f.x * f.v;
+    default: return f.y * f.u;
+    }
+}
+
 struct SpotArgs {
     const void* __restrict__ plane;
     double* __restrict__ partials;
@@ -117,20 +158,51 @@ __global__ __launch_bounds__(kBlock) void spot_partial_kernel(SpotArgs a) {
     }
 }
 
+// The focus statistics of an (N, 8) plane: spot_partial_kernel's tiles and tree, eight statistics at a time (16 KB
+// of LDS instead of 32)
+template <typename T>
+__global__ __launch_bounds__(kBlock) void focus_partial_kernel(SpotArgs a) {
+    constexpr int kRows = 8;
+    __shared__ double red[kRows][kBlock];
+    const int64_t g = blockIdx.y, tile = blockIdx.x;
+    const int64_t j = tile * kBlock + threadIdx.x;
+    FocusRay f{0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+    if (j < a.gsize) {
+        const T* r = static_cast<const T*>(a.plane) + (g * a.gsize + j) * 8;
+        f = focus_ray(r[0], r[1], r[2], r[3], r[4], r[5]);
+    }
+#pragma unroll
+    for (int k0 = 0; k0 < kFocusStats; k0 += kRows) {
+        double u[kRows];
+#pragma unroll
+        for (int k = 0; k < kRows; ++k) u[k] = focus_term(f, k0 + k);
+        // (no barrier between chunks: a tree's stores to slots 128..255 and 64..127 each follow a barrier that every
+        // reader of the chunk before has passed, as in the sweep's reduce)
+        block_tree_sum<kRows>(u, red);
+        if (threadIdx.x == 0) {
+#pragma unroll
+            for (int k = 0; k < kRows; ++k) a.partials[(g * a.tiles + tile) * kFocusStats + k0 + k] = u[k];
+        }
+    }
+}
+
+// NS statistics per group (kStats or kFocusStats): thread t adds tiles t, t + 256, ... in order, then one tree over
+// the 256 threads
+template <int NS>
 __global__ __launch_bounds__(kBlock) void spot_final_kernel(SpotArgs a) {
-    __shared__ double red[kStats][kBlock];
+    __shared__ double red[NS][kBlock];
     const int64_t g = blockIdx.x;
-    double v[kStats] = {0, 0, 0, 0, 0, 0, 0};
+    double v[NS] = {};
     for (int64_t t = threadIdx.x; t < a.tiles; t += kBlock)
-        for (int k = 0; k < kStats; ++k) v[k] += a.partials[(g * a.tiles + t) * kStats + k];
-    for (int k = 0; k < kStats; ++k) red[k][threadIdx.x] = v[k];
+        for (int k = 0; k < NS; ++k) v[k] += a.partials[(g * a.tiles + t) * NS + k];
+    for (int k = 0; k < NS; ++k) red[k][threadIdx.x] = v[k];
     __syncthreads();
     for (int w = kBlock / 2; w > 0; w >>= 1) {
         if (threadIdx.x < w)
-            for (int k = 0; k < kStats; ++k) red[k][threadIdx.x] += red[k][threadIdx.x + w];
+            for (int k = 0; k < NS; ++k) red[k][threadIdx.x] += red[k][threadIdx.x + w];
         __syncthreads();
     }
-    if (threadIdx.x < kStats) a.stats[g * kStats + threadIdx.x] = red[threadIdx.x][0];
+    if (threadIdx.x < NS) a.stats[g * NS + threadIdx.x] = red[threadIdx.x][0];
 }
 
 // Spot-diagram sweep, fused (C5).  Group g is the fan get_ray_fan(pt_g, ..., wl_g)
@@ -190,10 +262,22 @@ constexpr int kStateRows = 11;                     // bundle state per lane: x y
 #define RTPB_SWEEP_WPE 6
 #endif
 #define RTPB_SWEEP_ATTR __attribute__((amdgpu_waves_per_eu(RTPB_SWEEP_WPE, 8)))
-template <typename TS, int FEAT, bool BUNDLE>
+// An optimisation fence on three per-lane values: the compiler moves no computation on them across it
+#if defined(__HIP_DEVICE_COMPILE__)
+#define RTPB_PIN3(a, b, c) asm volatile("" : "+v"(a), "+v"(b), "+v"(c))
+#else
+#define RTPB_PIN3(a, b, c) ((void)0)
+#endif
+// NS = kStats: the spot statistics.  NS = kFocusStats (rtpb_focus_sweep): focus_ray of the final state, so the whole
+// final direction stays alive to the end.  kPosOnly leaves no part of it unfinished on any surface kind -- snell_apply,
+// reflect and lens_step compute dx, dy and dz in full whatever the mode, and a killed row is all NaN (the mode only
+// skips the position fill after a NaN direction and the at-plane) -- so the last surface runs the same step as the
+// others.  Single rows reduce eight of the sixteen statistics at a time (16 KB of LDS), bundle rows two as before.
+template <typename TS, int FEAT, bool BUNDLE, int NS = kStats>
 __global__ __launch_bounds__(kBlock) RTPB_SWEEP_ATTR void sweep_kernel(SweepArgs a) {
     static_assert(!BUNDLE || (FEAT & 16) != 0, "bundles: host-evaluated media");
-    constexpr int kRedRows = BUNDLE ? 2 : kStats;
+    static_assert(NS == kStats || NS == kFocusStats, "spot or focus statistics");
+    constexpr int kRedRows = BUNDLE ? 2 : NS == kStats ? kStats : 8;
     __shared__ double red[kRedRows][kBlock];
     __shared__ double state[BUNDLE ? kStateRows : 1][kBlock];
     const int tid = threadIdx.x;
@@ -297,25 +381,37 @@ __global__ __launch_bounds__(kBlock) RTPB_SWEEP_ATTR void sweep_kernel(SweepArgs
     // one ray's contribution to its group's tile partial: spot_partial_kernel's tree (block_tree_sum), kRedRows
     // statistics at a time
     auto reduce = [&](const Ray<double>& rr, bool ok, int64_t g, int64_t t) {
-        double v[kStats] = {0, 0, 0, 0, 0, 0, 0};
+        double v[kStats] = {};
+        FocusRay f{0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
         // the reference's position rule of the last surface (RT:1221 / RT:1289; a PerfectLens's after-plane
         // propagation gives a NaN position for a NaN direction by itself): NaN direction -> no spot point
         if (ok && !is_nan(rr.dx)) {
             const double x = stored<TS>(rr.x), y = stored<TS>(rr.y), z = stored<TS>(rr.z);
-            if (x - x == 0.0 && y - y == 0.0) {
-                v[0] = 1.0; v[1] = x; v[2] = y; v[3] = z; v[4] = x * x; v[5] = y * y; v[6] = x * y;
+            if constexpr (NS == kStats) {
+                if (x - x == 0.0 && y - y == 0.0) {
+                    v[0] = 1.0; v[1] = x; v[2] = y; v[3] = z; v[4] = x * x; v[5] = y * y; v[6] = x * y;
+                }
+            } else {
+                double dx = stored<TS>(rr.dx), dy = stored<TS>(rr.dy), dz = stored<TS>(rr.dz);
+                // the slopes' divisions stay behind the trace: without the fence the float64 instantiations spill
+                // inside the surface loops (FEAT 17 single rows: 20 spilled VGPRs instead of the spot kernel's 1)
+                RTPB_PIN3(dx, dy, dz);
+                f = focus_ray(x, y, z, dx, dy, dz);
             }
         }
 #pragma unroll
-        for (int k0 = 0; k0 < kStats; k0 += kRedRows) {
+        for (int k0 = 0; k0 < NS; k0 += kRedRows) {
             double u[kRedRows];
 #pragma unroll
-            for (int j = 0; j < kRedRows; ++j) u[j] = k0 + j < kStats ? v[k0 + j] : 0.0;
+            for (int j = 0; j < kRedRows; ++j) {
+                if constexpr (NS == kStats) u[j] = k0 + j < NS ? v[k0 + j] : 0.0;
+                else u[j] = focus_term(f, k0 + j);
+            }
             block_tree_sum<kRedRows>(u, red);
             if (tid == 0 && t < a.tiles) {
 #pragma unroll
                 for (int j = 0; j < kRedRows; ++j)
-                    if (k0 + j < kStats) a.partials[(g * a.tiles + t) * kStats + k0 + j] = u[j];
+                    if (k0 + j < NS) a.partials[(g * a.tiles + t) * NS + k0 + j] = u[j];
             }
         }
     };
@@ -478,6 +574,43 @@ __global__ __launch_bounds__(kBlock) void grid_interp_kernel(rtpb_triangulation 
     }
 }
 
+// rtpb_spot_stats (NS = kStats) and rtpb_focus_stats (NS = kFocusStats): the argument checks ...
+template <int NS>
+int plane_stats_check(int32_t dtype, const void* plane, int64_t group_size, int64_t n_groups, double* workspace,
+                      int64_t workspace_len, double* stats_out) {
+    constexpr bool kFocus = NS == kFocusStats;
+    if (dtype != RTPB_F64 && dtype != RTPB_F32) return fail(RTPB_E_INVALID, "bad dtype");
+    if (group_size <= 0 || n_groups <= 0 || !plane || !stats_out || !workspace)
+        return fail(RTPB_E_INVALID, kFocus ? "bad focus-stats arguments" : "bad spot-stats arguments");
+    const int64_t tiles = (group_size + kBlock - 1) / kBlock;
+    if (workspace_len < n_groups * tiles * NS)
+        return fail(RTPB_E_INVALID, kFocus ? "workspace too small: need n_groups * ceil(group_size/256) * 16 doubles"
+                                           : "workspace too small: need n_groups * ceil(group_size/256) * 7 doubles");
+    if (tiles > 65535 * 16384ll || n_groups > 65535) return fail(RTPB_E_LIMIT, "too many groups");
+    return RTPB_OK;
+}
+
+// ... and the two launches (checked arguments)
+template <int NS>
+int plane_stats_launch(int32_t device, int32_t dtype, const void* plane, int64_t group_size, int64_t n_groups,
+                       double* workspace, double* stats_out, void* stream) {
+    const int64_t tiles = (group_size + kBlock - 1) / kBlock;
+    SpotArgs a{plane, workspace, stats_out, group_size, n_groups, tiles};
+    DeviceGuard g(device);
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    dim3 grid(static_cast<unsigned>(tiles), static_cast<unsigned>(n_groups));
+    if constexpr (NS == kStats) {
+        if (dtype == RTPB_F64) hipLaunchKernelGGL(spot_partial_kernel<double>, grid, dim3(kBlock), 0, st, a);
+        else hipLaunchKernelGGL(spot_partial_kernel<float>, grid, dim3(kBlock), 0, st, a);
+    } else {
+        if (dtype == RTPB_F64) hipLaunchKernelGGL(focus_partial_kernel<double>, grid, dim3(kBlock), 0, st, a);
+        else hipLaunchKernelGGL(focus_partial_kernel<float>, grid, dim3(kBlock), 0, st, a);
+    }
+    HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(spot_final_kernel<NS>, dim3(static_cast<unsigned>(n_groups)), dim3(kBlock), 0, st, a);
+    HIP_TRY(hipGetLastError());
+    return RTPB_OK;
+}
 
 }  // namespace
 
@@ -508,41 +641,50 @@ int rtpb_spot_stats(int32_t device, int32_t dtype, const void* plane, int64_t gr
                     double* workspace, int64_t workspace_len, double* stats_out, void* stream) {
     int rc = check_device(device);
     if (rc) return rc;
-    if (dtype != RTPB_F64 && dtype != RTPB_F32) return fail(RTPB_E_INVALID, "bad dtype");
-    if (group_size <= 0 || n_groups <= 0 || !plane || !stats_out || !workspace)
-        return fail(RTPB_E_INVALID, "bad spot-stats arguments");
-    const int64_t tiles = (group_size + kBlock - 1) / kBlock;
-    if (workspace_len < n_groups * tiles * kStats)
-        return fail(RTPB_E_INVALID, "workspace too small: need n_groups * ceil(group_size/256) * 7 doubles");
-    if (tiles > 65535 * 16384ll || n_groups > 65535) return fail(RTPB_E_LIMIT, "too many groups");
-    SpotArgs a{plane, workspace, stats_out, group_size, n_groups, tiles};
-    DeviceGuard g(device);
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    dim3 grid(static_cast<unsigned>(tiles), static_cast<unsigned>(n_groups));
-    if (dtype == RTPB_F64) hipLaunchKernelGGL(spot_partial_kernel<double>, grid, dim3(kBlock), 0, st, a);
-    else hipLaunchKernelGGL(spot_partial_kernel<float>, grid, dim3(kBlock), 0, st, a);
-    HIP_TRY(hipGetLastError());
-    hipLaunchKernelGGL(spot_final_kernel, dim3(static_cast<unsigned>(n_groups)), dim3(kBlock), 0, st, a);
-    HIP_TRY(hipGetLastError());
-    return RTPB_OK;
+    rc = plane_stats_check<kStats>(dtype, plane, group_size, n_groups, workspace, workspace_len, stats_out);
+    if (rc) return rc;
+    return plane_stats_launch<kStats>(device, dtype, plane, group_size, n_groups, workspace, stats_out, stream);
 }
 
-int rtpb_spot_sweep(const rtpb_plan* plan_c, int32_t device, int64_t n_groups, const double* group_params,
-                    int64_t n_thetas, int64_t nphis, const double center_ray[3], const double ex[3],
-                    const double ey[3], const double* theta_cos_sin, const double* phi_cos_sin, double* workspace,
-                    int64_t workspace_len, double* stats_out, void* stream) {
+int rtpb_focus_stats(int32_t device, int32_t dtype, const void* plane, int64_t group_size, int64_t n_groups,
+                     double* workspace, int64_t workspace_len, double* stats_out, void* stream) {
+    // (the arguments first: a bad call is RTPB_E_INVALID / RTPB_E_LIMIT with or without a GPU)
+    int rc = plane_stats_check<kFocusStats>(dtype, plane, group_size, n_groups, workspace, workspace_len, stats_out);
+    if (rc) return rc;
+    rc = check_device(device);
+    if (rc) return rc;
+    return plane_stats_launch<kFocusStats>(device, dtype, plane, group_size, n_groups, workspace, stats_out, stream);
+}
+
+}  // extern "C"
+
+namespace {
+
+// rtpb_spot_sweep (NS = kStats) and rtpb_focus_sweep (NS = kFocusStats): the same checks, row planning and upload,
+// the sweep kernels of the statistics set.  The focus entry point checks its arguments before the device, so a bad
+// call is RTPB_E_INVALID / RTPB_E_LIMIT with or without a GPU.
+template <int NS>
+int sweep_impl(const rtpb_plan* plan_c, int32_t device, int64_t n_groups, const double* group_params,
+               int64_t n_thetas, int64_t nphis, const double center_ray[3], const double ex[3], const double ey[3],
+               const double* theta_cos_sin, const double* phi_cos_sin, double* workspace, int64_t workspace_len,
+               double* stats_out, void* stream) {
+    constexpr bool kFocus = NS == kFocusStats;
     auto* plan = const_cast<rtpb_plan*>(plan_c);
     if (!plan) return fail(RTPB_E_INVALID, "plan is NULL");
-    int rc = check_device(device);
+    int rc = kFocus ? 0 : check_device(device);
     if (rc) return rc;
     if (n_groups <= 0 || n_thetas <= 0 || nphis <= 0 || !group_params || !center_ray || !ex || !ey ||
         !theta_cos_sin || !phi_cos_sin || !workspace || !stats_out)
-        return fail(RTPB_E_INVALID, "bad spot-sweep arguments");
+        return fail(RTPB_E_INVALID, kFocus ? "bad focus-sweep arguments" : "bad spot-sweep arguments");
     const int64_t gsize = n_thetas * nphis;
     const int64_t tiles = (gsize + kBlock - 1) / kBlock;
-    if (workspace_len < n_groups * tiles * kStats)
-        return fail(RTPB_E_INVALID, "workspace too small: need n_groups * ceil(n_thetas*nphis/256) * 7 doubles");
+    if (workspace_len < n_groups * tiles * NS)
+        return fail(RTPB_E_INVALID,
+                    kFocus ? "workspace too small: need n_groups * ceil(n_thetas*nphis/256) * 16 doubles"
+                           : "workspace too small: need n_groups * ceil(n_thetas*nphis/256) * 7 doubles");
     if (tiles > 0x7fffffffll || n_groups > 65535) return fail(RTPB_E_LIMIT, "too many groups or rays per group");
+    rc = kFocus ? check_device(device) : 0;
+    if (rc) return rc;
     DeviceGuard g(device);
     void* blob = nullptr;
     rc = plan_device_blob(plan, device, &blob);
@@ -644,27 +786,47 @@ int rtpb_spot_sweep(const rtpb_plan* plan_c, int32_t device, int64_t n_groups, c
             ap.gidx = didx;
             ap.rows = didx + bundles.size() + singles.size();
             const dim3 grid(static_cast<unsigned>(tiles), static_cast<unsigned>(rows.size() / 2));
-            if (f == 0) hipLaunchKernelGGL((sweep_kernel<TS, 16, true>), grid, dim3(kBlock), 0, st, ap);
-            else hipLaunchKernelGGL((sweep_kernel<TS, 17, true>), grid, dim3(kBlock), 0, st, ap);
+            if (f == 0) hipLaunchKernelGGL((sweep_kernel<TS, 16, true, NS>), grid, dim3(kBlock), 0, st, ap);
+            else hipLaunchKernelGGL((sweep_kernel<TS, 17, true, NS>), grid, dim3(kBlock), 0, st, ap);
         }
         if (!singles.empty()) {
             SweepArgs as = a;
             as.gidx = didx + bundles.size();
             const dim3 grid(static_cast<unsigned>((tiles + kSweepRays - 1) / kSweepRays),
                             static_cast<unsigned>(singles.size()));
-            if (pre_n && f == 0) hipLaunchKernelGGL((sweep_kernel<TS, 16, false>), grid, dim3(kBlock), 0, st, as);
-            else if (pre_n) hipLaunchKernelGGL((sweep_kernel<TS, 17, false>), grid, dim3(kBlock), 0, st, as);
-            else hipLaunchKernelGGL((sweep_kernel<TS, 3, false>), grid, dim3(kBlock), 0, st, as);   // POLY6 media
+            if (pre_n && f == 0) hipLaunchKernelGGL((sweep_kernel<TS, 16, false, NS>), grid, dim3(kBlock), 0, st, as);
+            else if (pre_n) hipLaunchKernelGGL((sweep_kernel<TS, 17, false, NS>), grid, dim3(kBlock), 0, st, as);
+            else hipLaunchKernelGGL((sweep_kernel<TS, 3, false, NS>), grid, dim3(kBlock), 0, st, as);   // POLY6 media
         }
     };
     if (plan->dtype == RTPB_F64) go(double{});
     else go(float{});
     HIP_TRY(hipGetLastError());
     SpotArgs sa{nullptr, workspace, stats_out, gsize, n_groups, tiles};
-    hipLaunchKernelGGL(spot_final_kernel, dim3(static_cast<unsigned>(n_groups)), dim3(kBlock), 0, st, sa);
+    hipLaunchKernelGGL(spot_final_kernel<NS>, dim3(static_cast<unsigned>(n_groups)), dim3(kBlock), 0, st, sa);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipFreeAsync(dbuf, st));
     return RTPB_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int rtpb_spot_sweep(const rtpb_plan* plan, int32_t device, int64_t n_groups, const double* group_params,
+                    int64_t n_thetas, int64_t nphis, const double center_ray[3], const double ex[3],
+                    const double ey[3], const double* theta_cos_sin, const double* phi_cos_sin, double* workspace,
+                    int64_t workspace_len, double* stats_out, void* stream) {
+    return sweep_impl<kStats>(plan, device, n_groups, group_params, n_thetas, nphis, center_ray, ex, ey,
+                              theta_cos_sin, phi_cos_sin, workspace, workspace_len, stats_out, stream);
+}
+
+int rtpb_focus_sweep(const rtpb_plan* plan, int32_t device, int64_t n_groups, const double* group_params,
+                     int64_t n_thetas, int64_t nphis, const double center_ray[3], const double ex[3],
+                     const double ey[3], const double* theta_cos_sin, const double* phi_cos_sin, double* workspace,
+                     int64_t workspace_len, double* stats_out, void* stream) {
+    return sweep_impl<kFocusStats>(plan, device, n_groups, group_params, n_thetas, nphis, center_ray, ex, ey,
+                                   theta_cos_sin, phi_cos_sin, workspace, workspace_len, stats_out, stream);
 }
 
 int rtpb_grid_interpolate(int32_t device, const rtpb_triangulation* tri, const double* xs, int64_t nx,

@@ -1,0 +1,225 @@
+"""GPU: the through-focus statistics (rtpb_focus_stats, rtpb_focus_sweep; analysis.focus_stats_raw / focus_sweep)
+against a NumPy restatement of their reduction, the oracle's trace, the unfused pipeline and the spot sweep."""
+import functools
+
+import numpy as np
+import pytest
+
+torch = pytest.importorskip("torch")
+
+import ray_trace_pb_amd.materials as mat  # noqa: E402
+import ray_trace_pb_amd.raytrace as rt  # noqa: E402
+from ray_trace_pb_amd import analysis  # noqa: E402
+from oracle import rt_numpy as O  # noqa: E402
+from parity import same_bits  # noqa: E402
+from serialize import material_to_dict, surface_to_dict  # noqa: E402
+import systems  # noqa: E402
+
+pytestmark = pytest.mark.gpu
+DEV = "cuda:0"
+NT, NPH = 301, 77                      # 23177 rays per group: 91 tiles, a ragged last one
+
+
+def fixed_order_focus_sums(plane, group_size, tile=256):
+    """The focus kernels' reduction restated in NumPy, operation for operation (csrc/rtpb_analysis.hip focus_ray /
+    focus_term, focus_partial_kernel / sweep_kernel + spot_final_kernel): u = dx / dz, v = dy / dz; a ray counts when
+    x, y, u and v are finite; per 256-ray tile a pairwise tree (red[t] += red[t + w], w = 128 ... 1) of the sixteen
+    terms; per group, thread t adds tiles t, t + 256, ... in order, then the same tree over the 256 threads."""
+    p = np.asarray(plane, dtype=np.float64).reshape(-1, group_size, plane.shape[-1])
+    G = p.shape[0]
+    tiles = -(-group_size // tile)
+    x, y, z = p[..., 0], p[..., 1], p[..., 2]
+    with np.errstate(invalid="ignore", divide="ignore", over="ignore"):
+        u, v = p[..., 3] / p[..., 5], p[..., 4] / p[..., 5]
+        ok = (x - x == 0.0) & (y - y == 0.0) & (u - u == 0.0) & (v - v == 0.0)
+        terms = np.stack((np.ones_like(x), x, y, z, x * x, y * y, x * y, u, v, u * u, v * v, u * v, x * u, y * v,
+                          x * v, y * u), -1)
+    acc = np.zeros((G, tiles * tile, 16))
+    acc[:, :group_size] = np.where(ok[..., None], terms, 0.0)
+    acc = acc.reshape(G, tiles, tile, 16)
+    w = tile // 2
+    while w:
+        acc[:, :, :w] = acc[:, :, :w] + acc[:, :, w:2 * w]
+        w //= 2
+    part = acc[:, :, 0]                                           # (G, tiles, 16)
+    fin = np.zeros((G, tile, 16))
+    for c in range(0, tiles, tile):
+        blk = part[:, c:c + tile]
+        fin[:, :blk.shape[1]] = fin[:, :blk.shape[1]] + blk
+    w = tile // 2
+    while w:
+        fin[:, :w] = fin[:, :w] + fin[:, w:2 * w]
+        w //= 2
+    return fin[:, 0]
+
+
+@pytest.mark.parametrize("dtype,tiles", [("float64", 5), ("float32", 5), ("float64", 300)])
+def test_focus_stats_bitwise_vs_fixed_order_oracle(dtype, tiles):
+    """rtpb_focus_stats: all 16 sums bit-identical to the restatement -- several tiles with a ragged last one, and
+    more than 256 tiles per group (the second stage's sequential chains).  Every group has rows with NaN x and
+    infinite y; groups 1 and 2 also rows with dz = 0 and rows with a NaN direction but a finite position, which
+    only the focus mask drops: there the count falls below the spot count, and in group 0 columns 0-6 are the spot
+    statistics bit for bit."""
+    rng = np.random.default_rng(11)
+    G, per = 3, 256 * tiles + 77
+    plane = rng.normal(size=(G * per, 8)) * np.array([1, 2, 3, 0.1, 0.1, 0.05, 1, 1])
+    plane += np.array([5, 5, 5, 0, 0, 1, 0, 1])
+    plane[rng.random(G * per) < 0.1, 0] = np.nan
+    plane[rng.random(G * per) < 0.01, 1] = np.inf
+    later = np.arange(G * per) >= per
+    plane[later & (rng.random(G * per) < 0.02), 5] = 0.0
+    plane[later & (rng.random(G * per) < 0.02), 3:6] = np.nan
+    plane = plane.astype(dtype)
+    t = torch.from_numpy(plane).to(DEV)
+    raw = analysis.focus_stats_raw(t, per).cpu().numpy()
+    assert raw.shape == (G, 16)
+    assert np.array_equal(raw, fixed_order_focus_sums(plane, per))
+    spot = analysis.spot_stats_raw(t, per).cpu().numpy()
+    assert np.array_equal(raw[0, :7], spot[0])
+    assert (raw[1:, 0] < spot[1:, 0]).all() and raw[:, 0].min() > 0
+    summ = analysis.focus_stats(t, per)
+    exp = analysis.summarize_focus(raw)
+    assert summ.keys() == exp.keys()
+    for k in summ:
+        assert same_bits(summ[k], exp[k]), k
+
+
+def _dicts(system, m0, m1):
+    return ([surface_to_dict(s) for s in system.surfaces],
+            [material_to_dict(m) for m in [m0] + list(system.materials) + [m1]])
+
+
+@functools.lru_cache(maxsize=None)
+def c5_oracle_sums(dtype):
+    """The oracle's final planes of the C5 fans (the reference generator's rays, rounded to the storage type going
+    in and coming out) reduced in the kernels' order: (2 fields, 2 wavelengths, 16).  Computed once per dtype."""
+    system = systems.c5_system(rt, mat)
+    fields, wls = systems.c5_field_points(2)[1:3], [0.405, 0.635]
+    S, M = _dicts(system, mat.Constant(1), mat.Constant(1))
+    finals = []
+    for f in fields:
+        for w in wls:
+            rays = rt.get_ray_fan(f, 0.5 * np.pi / 180, NT, w, nphis=NPH)
+            if dtype == "float32":
+                rays = rays.astype(np.float32).astype(np.float64)
+            fin = O.ray_trace(S, M, rays)[-1]
+            finals.append(fin.astype(np.float32).astype(np.float64) if dtype == "float32" else fin)
+    ref = fixed_order_focus_sums(np.concatenate(finals), NT * NPH).reshape(2, 2, 16)
+    ref.setflags(write=False)
+    return ref
+
+
+@pytest.mark.parametrize("dtype", ["float64", "float32"])
+def test_focus_sweep_sums_bitwise_vs_oracle(dtype):
+    """The fused focus sweep of the C5 system against the oracle: all 16 raw sums bit for bit, hence every entry
+    of the summary."""
+    system = systems.c5_system(rt, mat)
+    fields, wls = systems.c5_field_points(2)[1:3], [0.405, 0.635]
+    summ, timing = analysis.focus_sweep(system, mat.Constant(1), mat.Constant(1), fields, wls, 0.5 * np.pi / 180,
+                                        NT, NPH, device=DEV, dtype=dtype)
+    ref = c5_oracle_sums(dtype)
+    assert summ["raw"].shape == (2, 2, 16)
+    assert np.array_equal(summ["raw"], ref)
+    assert summ["count"].min() > 0
+    exp = analysis.summarize_focus(ref)
+    assert summ.keys() == exp.keys()
+    for k in exp:
+        assert same_bits(summ[k], exp[k]), k
+    assert timing["rays"] == 4 * NT * NPH and timing["per_device"][0]["kernel_ms"] > 0
+
+
+def sweep_case(case):
+    gpb = 4
+    if case == "c5":
+        system, m0, m1 = systems.c5_system(rt, mat), mat.Constant(1), mat.Constant(1)
+        fields, wls, theta = systems.c5_field_points(2), [0.405, 0.532, 0.785], 0.5 * np.pi / 180
+    elif case == "c5_bundles":
+        # batches of 13 groups over 2 fields x 9 wavelengths: bundle rows of 8 and 4 groups and single rows
+        system, m0, m1 = systems.c5_system(rt, mat), mat.Constant(1), mat.Constant(1)
+        fields, wls, theta = systems.c5_field_points(2), list(np.linspace(0.4, 0.8, 9)), 0.5 * np.pi / 180
+        gpb = 13
+    elif case == "c2":
+        system, m0, m1 = systems.c2_system(rt, mat), mat.Vacuum(), mat.Vacuum()
+        fields, wls, theta = [[0.0, 0.0, -5.0], [1.0, -2.0, -5.0]], list(systems.C2_WAVELENGTHS), 0.05
+    elif case == "c4":
+        system, m0, m1 = systems.c4_system(rt, mat), mat.Constant(systems.OPM_N1), mat.Vacuum()
+        fields, wls, theta = [[1e-3, 1e-3, 1e-3 * np.tan(np.pi / 6)], [0.0, 0.0, 0.0]], \
+            [systems.OPM_WAVELENGTH, 0.9 * systems.OPM_WAVELENGTH], np.arcsin(1.35 / systems.OPM_N1)
+    elif case == "xz":
+        from test_axial import tilted_xz_system
+        system, m0, m1 = tilted_xz_system()
+        fields, wls, theta = [[0.0, 0.0, -3.0], [0.4, -0.3, -3.0]], [0.5, 0.6], 0.2
+    elif case in ("tir", "tir_last"):
+        system, _, m0, m1 = systems.tir_prism(rt, mat)
+        if case == "tir_last":
+            system = rt.System(system.surfaces[:2], system.materials[:1])
+        fields, wls, theta = [[0.0, 0.0, -5.0], [2.0, -1.0, -5.0]], [0.45, 0.55, 0.7], 0.5
+    else:
+        system, m0, m1 = systems.stress_system(rt, mat), mat.Vacuum(), mat.Vacuum()
+        fields, wls, theta = [[0.0, 0.0, -10.0], [3.0, -2.0, -10.0], [-1.5, 2.5, -10.0]], [0.5, 0.6328], 0.3
+    return (system, m0, m1, fields, wls, theta, NT, NPH), gpb
+
+
+@pytest.mark.parametrize("dtype", ["float64", "float32"])
+@pytest.mark.parametrize("case", ["c5", "c5_bundles", "c2", "c4", "xz", "tir", "tir_last", "stress"])
+def test_fused_focus_sweep_bitwise_equals_unfused(case, dtype):
+    """One-kernel focus sweep == fan kernel + trace(planes='final') + rtpb_focus_stats, all 16 columns and every
+    summary entry bit for bit, on the systems of the spot sweep's fused == unfused test (bundle and single rows, lens
+    and lens-free instantiations, x-z plane steps, total internal reflection mid-path and at the last surface,
+    every surface kind): the sweep's final direction under its final-position step semantics against the
+    full-semantics trace kernel.  Columns 0-6 are the spot sweep's sums."""
+    args, gpb = sweep_case(case)
+    kw = dict(device=DEV, dtype=dtype)
+    fu, _ = analysis.focus_sweep(*args, groups_per_batch=gpb, fused=True, require_image_plane=False, **kw)
+    un, _ = analysis.focus_sweep(*args, groups_per_batch=5, fused=False, require_image_plane=False, **kw)
+    assert fu.keys() == un.keys()
+    assert np.array_equal(fu["raw"], un["raw"])
+    for k in fu:
+        assert same_bits(fu[k], un[k]), k
+    assert fu["count"].min() > 0
+    if case in ("tir", "tir_last", "stress", "c4"):
+        assert (fu["count"] < NT * NPH).any()
+    spot, _ = analysis.spot_sweep(*args, groups_per_batch=gpb, **kw)
+    assert np.array_equal(fu["raw"][..., :7], spot["raw"])
+
+
+def test_c2_chromatic_focal_shift_and_astigmatism():
+    """The achromat of C2, an object point 5 mm before the first flat: the best focus moves monotonically with the
+    wavelength (the oracle gives a span of 0.076 mm over C2_WAVELENGTHS), there is no astigmatism on axis, and off
+    axis the sagittal and tangential foci separate with the sign the oracle gives."""
+    system = systems.c2_system(rt, mat)
+    wls = list(systems.C2_WAVELENGTHS)
+    summ, _ = analysis.focus_sweep(system, mat.Vacuum(), mat.Vacuum(), [[0.0, 0.0, -5.0], [1.0, -2.0, -5.0]], wls,
+                                   0.05, 61, 12, device=DEV)
+    z = summ["best_focus_z"][0]
+    print("best focus:", summ["best_focus_z"], "astigmatism:", summ["astigmatism"])
+    steps = np.diff(z)
+    assert (steps < 0).all() or (steps > 0).all()
+    assert 0.05 < abs(z[-1] - z[0]) < 0.1
+    assert (np.abs(summ["astigmatism"][0]) < 1e-9).all()
+    S, M = _dicts(system, mat.Vacuum(), mat.Vacuum())
+    fin = np.concatenate([O.ray_trace(S, M, rt.get_ray_fan([1.0, -2.0, -5.0], 0.05, 61, w, nphis=12))[-1]
+                          for w in wls])
+    ref = analysis.summarize_focus(fixed_order_focus_sums(fin, 61 * 12))
+    assert (ref["astigmatism"] != 0).all()
+    assert np.array_equal(np.sign(summ["astigmatism"][1]), np.sign(ref["astigmatism"]))
+    assert (summ["rms_radius_best"] < summ["rms_radius"]).all()
+
+
+def test_focus_sweep_over_devices_is_bitwise_equal():
+    """devices=: the groups split over devices (here: shards on GPU 0, plus every visible GPU when there are
+    several) give the one-device result bit for bit."""
+    system = systems.c5_system(rt, mat)
+    fields = systems.c5_field_points(3)
+    wls = [0.405, 0.532, 0.785]
+    args = (system, mat.Constant(1), mat.Constant(1), fields, wls, 0.5 * np.pi / 180, 101, 37)
+    one, t1 = analysis.focus_sweep(*args, device=DEV, groups_per_batch=4)
+    lists = [[0, 0, 0]] + ([list(range(torch.cuda.device_count()))] if torch.cuda.device_count() > 1 else [])
+    for devs in lists:
+        many, tm = analysis.focus_sweep(*args, devices=devs, groups_per_batch=4)
+        assert many.keys() == one.keys()
+        for k in one:
+            assert same_bits(many[k], one[k]), (devs, k)
+        assert [p["device"] for p in tm["per_device"]] == devs
+        assert sum(p["rays"] for p in tm["per_device"]) == t1["rays"]
+        assert all(p["kernel_ms"] > 0 for p in tm["per_device"])

@@ -336,12 +336,12 @@ def guarded_walk(blks, header):
 
 
 def sweep_main(show):
-    """The C5 sweep kernel (bundle rows, host-evaluated media, PerfectLens code: sweep_kernel<double, 17, true>) with
+    """The C5 sweep kernel (bundle rows, host-evaluated media, PerfectLens code: sweep_kernel<double, 17, true, 7>) with
     every surface one form: the innermost loop is one run step for kSweepRays rays per lane."""
     for case in ("sphere_ax", "sphere_gen", "flat_ax", "flat_xz", "lens_ax"):
         kind, geo = CASES[case]
         funcs = {n: b for n, b in functions(compile_kernel(kind, geo, sweep=True)).items()
-                 if "sweep_kernelIdLi17ELb1E" in n}
+                 if "sweep_kernelIdLi17ELb1ELi7E" in n}
         (name, body), = funcs.items()
         depth = max(int(m.group(1)) for m in re.finditer(r"Depth=(\d+)", "\n".join(body)))
         blks = loop_blocks(body, depth)
@@ -350,7 +350,7 @@ def sweep_main(show):
         f64 = sum(v for op, v in hist.items() if "_f64" in op and not op.startswith(("v_cmp", "v_frexp", "v_cvt")))
         movs = sum(v for op, v in hist.items() if op.startswith("v_mov"))
         g_body = {n: b for n, b in functions(compile_kernel(kind, geo, sweep=True, guards=True)).items()
-                  if "sweep_kernelIdLi17ELb1E" in n}
+                  if "sweep_kernelIdLi17ELb1ELi7E" in n}
         (gname, gbody), = g_body.items()
         gdepth = max(int(m.group(1)) for m in re.finditer(r"Depth=(\d+)", "\n".join(gbody)))
         guarded = guarded_walk(loop_blocks(gbody, gdepth), header_of(gbody, gdepth))
