@@ -414,6 +414,58 @@ def lightsheet(rt, mat, rad_curv, nrays=1001):
     return osys, rays, mat.Vacuum(), mat.Vacuum()
 
 
+# ------------------------------------------------------------------ sweep edge rays (tests/sweep_cases.py)
+def c5_tail(rt, mat, k):
+    """C5 from surface k on (k = 2, 5: the spheres concave towards the source, vertex z = 207.2, R = -106.2 and
+    vertex z = 516.2, R = -71.1), entered from the medium before that surface: a point source just past the
+    vertex has both roots of the first sphere behind it, the larger one on the cap inside the aperture.
+    Returns (system, initial material, final material, vertex z)."""
+    c5 = c5_system(rt, mat)
+    s = c5.surfaces[k]
+    zv = float(np.asarray(s.center, dtype=float).ravel()[2] - s.radius)
+    return rt.System(c5.surfaces[k:], c5.materials[k:]), c5.materials[k - 1], mat.Constant(1), zv
+
+
+def tail_fields(zv, dz):
+    return [[0.0, 0.0, zv + dz], [0.7, -0.4, zv + dz]]
+
+
+def sweep_edge_tail(rt, mat, n_thetas=21, nphis=5):
+    """The k = 2 tail of C5 with point sources 3 mm before the first vertex (u2 < 0 <= u1: the rays go on) and
+    3 mm past it (both roots backward, the larger on the cap: the reference drops every ray at plane 1)."""
+    system, m0, m1, zv = c5_tail(rt, mat, 2)
+    rays = np.concatenate([rt.get_ray_fan(f, 0.5 * np.pi / 180, n_thetas, wl, nphis=nphis)
+                           for f in tail_fields(zv, -3.0) + tail_fields(zv, 3.0) for wl in (0.405, 0.785)], axis=0)
+    return system, rays, m0, m1
+
+
+def tangent_system(rt, mat, leading_flat=False):
+    """A sphere of radius 4 (vertex z = 0, centre z = 4) before a wide flat, in vacuum: a ray along +z at distance
+    exactly 4 from the axis grazes it at the equator, B B - 4 C = +0 exactly, and the reference keeps it.
+    ``leading_flat``: a vacuum-vacuum flat at z = 2 first, which hands those rays on bit for bit."""
+    surfaces = [rt.SphericalSurface.get_on_axis(4.0, 0.0, 5.0), rt.FlatSurface([0, 0, 10], [0, 0, 1], 50)]
+    materials = [mat.Bk7()]
+    if leading_flat:
+        surfaces = [rt.FlatSurface([0, 0, 2], [0, 0, 1], 50)] + surfaces
+        materials = [mat.Vacuum()] + materials
+    return rt.System(surfaces, materials)
+
+
+TANGENT_FIELDS = ([4.0, 0.0, 1.0], [0.0, -4.0, 1.0])
+
+
+def sweep_edge_tangent(rt, mat, n_thetas=21, nphis=5):
+    rays = np.concatenate([rt.get_ray_fan(f, 0.3, n_thetas, 0.5, nphis=nphis) for f in TANGENT_FIELDS], axis=0)
+    return tangent_system(rt, mat), rays, mat.Vacuum(), mat.Vacuum()
+
+
+def sweep_edge_far(rt, mat, n_thetas=21, nphis=5):
+    """C5 from a point source 1e200 mm away: B B and C of the first sphere both overflow, the discriminant is
+    inf - inf, and the reference drops every ray at plane 1."""
+    rays = rt.get_ray_fan([0.0, 0.0, -1e200], 0.5 * np.pi / 180, n_thetas, 0.405, nphis=nphis)
+    return c5_system(rt, mat), rays, mat.Constant(1), mat.Constant(1)
+
+
 # ------------------------------------------------------------------ randomised systems (fuzz)
 FUZZ_GLASSES = ("Bk7", "Sf10", "Sf2", "Nsf11", "Nbaf10", "FusedSilica", "Nlak22", "Nsf6ht", "Nsk11")
 N_FUZZ = 32
@@ -518,6 +570,11 @@ RECIPES = {
     "lightsheet_r8": lambda rt, mat: lightsheet(rt, mat, 8.0),
     "lightsheet_r120": lambda rt, mat: lightsheet(rt, mat, 120.0),
     "lightsheet_r1e9": lambda rt, mat: lightsheet(rt, mat, 1e9),
+    # edge rays of the sweeps' positions-only steps: a first-surface backward root that lands on the cap, a +0
+    # discriminant on a surviving ray, an overflowing discriminant
+    "sweep_edge_tail": sweep_edge_tail,
+    "sweep_edge_tangent": sweep_edge_tangent,
+    "sweep_edge_far": sweep_edge_far,
 }
 RECIPES.update({"fuzz_%02d" % k: (lambda rt, mat, k=k: fuzz(rt, mat, k)) for k in range(N_FUZZ)})
 

@@ -209,7 +209,11 @@ def test_float32_storage_of_float64_input_is_the_rounded_reference(name):
     exp = ref.astype(np.float32)
     got = system.ray_trace(rays, m0, m1, dtype="float32")
     assert got.dtype == np.float32 and same_bits(got, exp)
-    ok, rep = compare(got, ref, rtol=1e-5)
+    # a reference value beyond float32's range rounds to an infinity (sweep_edge_far's source at z = -1e200): the
+    # tolerance applies to the values float32 can hold, the rounded reference stands for the others
+    with np.errstate(invalid="ignore"):
+        beyond = np.abs(ref) > np.finfo(np.float32).max
+    ok, rep = compare(got, np.where(beyond, exp.astype(np.float64), ref), rtol=1e-5)
     assert ok and rep["mask_flips"] == 0, rep
     x = torch.from_numpy(rays).to(DEV)
     got_t = system.ray_trace(x, m0, m1, dtype="float32")
