@@ -112,23 +112,24 @@ __global__ __launch_bounds__(kTraceBlock) void collimated_kernel(CollArgs a) {
 
 // Generator tables on the device: (cos, sin) pairs [n_a] then [n_b].  With host tables (the caller's
 // own np.cos / np.sin / np.linspace values) they are copied; otherwise trig_table_kernel evaluates
-// them with the device's libm (within an ulp of the host's).
-int gen_tables(double2** tab, int64_t n_a, int64_t n_b, const double* host_a, const double* host_b, int a_pairs,
+// them with the device's libm (within an ulp of the host's).  The caller owns the block.
+int gen_tables(StreamScratch& tab, int64_t n_a, int64_t n_b, const double* host_a, const double* host_b, int a_pairs,
                const TrigArgs& ta, hipStream_t st) {
     const size_t bytes = size_t(n_a + n_b) * sizeof(double2);
-    HIP_TRY(hipMallocAsync(reinterpret_cast<void**>(tab), bytes, st));
+    int rc = tab.alloc(bytes, st);
+    if (rc) return rc;
     if (host_a || host_b) {
         PinnedStaging& g_pinned = pinned_staging();
-        int rc = g_pinned.reserve(bytes);
+        rc = g_pinned.reserve(bytes);
         if (rc) return rc;
         double2* h = reinterpret_cast<double2*>(g_pinned.buf);
         for (int64_t j = 0; j < n_a; ++j)
             h[j] = a_pairs ? make_double2(host_a[2 * j], host_a[2 * j + 1]) : make_double2(host_a[j], 0.0);
         for (int64_t j = 0; j < n_b; ++j) h[n_a + j] = make_double2(host_b[2 * j], host_b[2 * j + 1]);
-        return g_pinned.upload(*tab, bytes, st);
+        return g_pinned.upload(tab.p, bytes, st);
     }
     TrigArgs a = ta;
-    a.tab = *tab;
+    a.tab = static_cast<double2*>(tab.p);
     hipLaunchKernelGGL(trig_table_kernel, dim3(static_cast<unsigned>((n_a + n_b + kBlock - 1) / kBlock)),
                        dim3(kBlock), 0, st, a);
     HIP_TRY(hipGetLastError());
@@ -166,15 +167,15 @@ int fan_impl(int32_t device, int32_t dtype, void* rays_out, const double pt[3], 
     ta.step = n_thetas > 1 ? (theta_max - (-theta_max)) / double(n_thetas - 1) : 0.0;
     ta.phi_start = 0.0;
     ta.want_a = 1;
-    double2* tab = nullptr;
-    rc = gen_tables(&tab, n_thetas, nphis, theta_cs, phi_cs, 1, ta, st);
+    StreamScratch tab;
+    rc = gen_tables(tab, n_thetas, nphis, theta_cs, phi_cs, 1, ta, st);
     if (rc) return rc;
     const unsigned blocks = static_cast<unsigned>((total + kTraceBlock - 1) / kTraceBlock);
     auto go = [&](auto tag) {
         using T = decltype(tag);
         FanArgs<T> a{};
         a.out = static_cast<T*>(rays_out);
-        a.tab = tab;
+        a.tab = static_cast<const double2*>(tab.p);
         a.n_thetas = n_thetas;
         a.nphis = nphis;
         for (int j = 0; j < 3; ++j) {
@@ -187,8 +188,7 @@ int fan_impl(int32_t device, int32_t dtype, void* rays_out, const double pt[3], 
     if (dtype == RTPB_F64) go(double{});
     else go(float{});
     HIP_TRY(hipGetLastError());
-    HIP_TRY(hipFreeAsync(tab, st));
-    return RTPB_OK;
+    return tab.release();
 }
 
 int collimated_impl(int32_t device, int32_t dtype, void* rays_out, const double pt[3], double displacement_max,
@@ -241,16 +241,15 @@ int collimated_impl(int32_t device, int32_t dtype, void* rays_out, const double 
     ta.n_b = nphis;
     ta.phi_start = phi_start;
     ta.want_a = 0;
-    double2* tab = nullptr;
-    rc = gen_tables(&tab, n_disps, nphis, offsets, phi_cs, 0, ta, st);
+    StreamScratch tab;
+    rc = gen_tables(tab, n_disps, nphis, offsets, phi_cs, 0, ta, st);
     if (rc) return rc;
-    a.tab = tab;
+    a.tab = static_cast<const double2*>(tab.p);
     const unsigned blocks = static_cast<unsigned>((n_disps * nphis + kTraceBlock - 1) / kTraceBlock);
     if (dtype == RTPB_F64) hipLaunchKernelGGL(collimated_kernel<double>, dim3(blocks), dim3(kTraceBlock), 0, st, a);
     else hipLaunchKernelGGL(collimated_kernel<float>, dim3(blocks), dim3(kTraceBlock), 0, st, a);
     HIP_TRY(hipGetLastError());
-    HIP_TRY(hipFreeAsync(tab, st));
-    return RTPB_OK;
+    return tab.release();
 }
 
 }  // namespace

@@ -7,7 +7,9 @@
 //   rtpb_core.hip          errors, plans (lowering to device blobs), device queries
 //   rtpb_trace.hip         the fused trace kernel, rtpb_trace / rtpb_trace_host, tuning and timing
 //   rtpb_generators.hip    device ray fans and collimated bundles (RT:45-161)
-//   rtpb_analysis.hip      intersect_rays, spot statistics, the fused spot sweep, grid interpolation
+//   rtpb_analysis.hip      intersect_rays, the plane statistics (spot and focus), grid interpolation
+//   rtpb_sweep.hip         the fused spot / focus sweep (rtpb_stats.h: what it shares with the plane statistics;
+//                          rtpb_sweep_host.h: its row planning, media table and upload layout, plain C++)
 //   rtpb_surface_ops.hip   propagate_ray2plane and the user-geometry hook kernels
 #pragma once
 
@@ -417,6 +419,36 @@ struct PinnedStaging {
     }
 };
 PinnedStaging& pinned_staging();     // this thread's buffer
+
+// A stream-ordered scratch block (hipMallocAsync) that is freed on its stream when the holder goes out of scope, so
+// an early return cannot leak it.  The success path calls release() itself: a failed free is an error to report,
+// which a destructor cannot do.
+struct StreamScratch {
+    void* p = nullptr;
+    hipStream_t st = nullptr;
+
+    StreamScratch() = default;
+    StreamScratch(const StreamScratch&) = delete;
+    StreamScratch& operator=(const StreamScratch&) = delete;
+    ~StreamScratch() {
+        if (p) (void)hipFreeAsync(p, st);
+    }
+    int alloc(size_t bytes, hipStream_t stream) {
+        st = stream;
+        HIP_TRY(hipMallocAsync(&p, bytes, st));
+        return RTPB_OK;
+    }
+    int release() {
+        void* q = p;
+        p = nullptr;
+        HIP_TRY(hipFreeAsync(q, st));
+        return RTPB_OK;
+    }
+};
+
+// The second pass of the plane statistics and of the sweeps (spot_final_kernel, rtpb_analysis.hip): n_stats is 7
+// (spot) or 16 (focus) sums per group, from partials[n_groups][tiles][n_stats].
+int launch_stats_final(int n_stats, double* partials, double* stats, int64_t n_groups, int64_t tiles, hipStream_t st);
 
 }  // namespace rtpbi
 

@@ -9,19 +9,16 @@
 
 #include "rtpb.h"
 #include "../../ray_trace_pb_amd/csrc/rtpb_math.h"
+#include "../../ray_trace_pb_amd/csrc/rtpb_sweep_host.h"
 
 using namespace rtpb;
 
-// TS = storage type of the ray buffers; arithmetic is float64 like the kernel
-template <typename TS>
-static int harness_trace(const rtpb_surface* surfaces, int32_t nsurf, const rtpb_material* materials, const TS* in,
-                         int64_t n, TS* out) {
+// the material descriptors the kernels see, and the sorted tables of the TABLE materials
+static void lower_materials(const rtpb_material* materials, int nmat, std::vector<DevMaterial<double>>& M,
+                            std::vector<double>& table) {
     using T = double;
-    std::vector<DevSurface<T>> S(nsurf);
-    for (int k = 0; k < nsurf; ++k) S[k] = lower_surface(surfaces[k]);
-    std::vector<DevMaterial<T>> M(nsurf + 1);
-    std::vector<T> table;
-    for (int k = 0; k <= nsurf; ++k) {
+    M.resize(nmat);
+    for (int k = 0; k < nmat; ++k) {
         const rtpb_material& m = materials[k];
         DevMaterial<T>& d = M[k];
         d.kind = m.kind;
@@ -35,6 +32,18 @@ static int harness_trace(const rtpb_surface* surfaces, int32_t nsurf, const rtpb
             sort_table(table.data() + table.size() - 2 * m.table_len, m.table_len);
         }
     }
+}
+
+// TS = storage type of the ray buffers; arithmetic is float64 like the kernel
+template <typename TS>
+static int harness_trace(const rtpb_surface* surfaces, int32_t nsurf, const rtpb_material* materials, const TS* in,
+                         int64_t n, TS* out) {
+    using T = double;
+    std::vector<DevSurface<T>> S(nsurf);
+    for (int k = 0; k < nsurf; ++k) S[k] = lower_surface(surfaces[k]);
+    std::vector<DevMaterial<T>> M;
+    std::vector<T> table;
+    lower_materials(materials, nsurf + 1, M, table);
     for (int k = 0; k < nsurf; ++k) lower_surface_media(S[k], M[k], M[k + 1]);
     const int64_t P = 2 * nsurf + 1;
     for (int64_t i = 0; i < n; ++i) {
@@ -183,4 +192,28 @@ extern "C" int harness_pos_vs_full(const rtpb_surface* s, double ratio, const do
 // the sweep's fan-index division (rtpb_spot_sweep): multiplier and shift for divisor d and group size g
 extern "C" void harness_sweep_divisor(int64_t d, int64_t g, uint32_t* mul, int32_t* shift) {
     sweep_divisor(d, g, *mul, *shift);
+}
+
+// the sweep's block rows (rtpb_sweep_host.h plan_sweep_rows): bundles and singles hold up to n_groups entries, rows
+// up to n_groups (a row has at least two groups); counts = the three lengths
+extern "C" void harness_sweep_rows(const double* group_params, int64_t n_groups, int bundles_allowed, int rays_per_lane,
+                                   int max_bundle, int32_t* bundles, int32_t* rows, int32_t* singles, int64_t* counts) {
+    const rtpbi::SweepRows r = rtpbi::plan_sweep_rows(group_params, n_groups, bundles_allowed != 0, rays_per_lane,
+                                                      max_bundle);
+    std::copy(r.bundles.begin(), r.bundles.end(), bundles);
+    std::copy(r.rows.begin(), r.rows.end(), rows);
+    std::copy(r.singles.begin(), r.singles.end(), singles);
+    counts[0] = static_cast<int64_t>(r.bundles.size());
+    counts[1] = static_cast<int64_t>(r.rows.size());
+    counts[2] = static_cast<int64_t>(r.singles.size());
+}
+
+// the sweep's per-group media (rtpb_sweep_host.h fill_group_media) of nmat lowered materials:
+// out[n_groups][nmat + 3 (nmat - 1)]
+extern "C" void harness_sweep_media(const rtpb_material* materials, int32_t nmat, const double* group_params,
+                                    int64_t n_groups, int32_t dtype, double* out) {
+    std::vector<DevMaterial<double>> M;
+    std::vector<double> table;
+    lower_materials(materials, nmat, M, table);
+    rtpbi::fill_group_media(M.data(), M.size(), table.data(), group_params, n_groups, dtype, out);
 }

@@ -10,6 +10,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 SRC = os.path.join(HERE, "native", "math_harness.cpp")
 OUT = os.path.join(HERE, "native", "_build", "libmath_harness.so")
 DEPS = [SRC, os.path.join(HERE, "..", "ray_trace_pb_amd", "csrc", "rtpb_math.h"),
+        os.path.join(HERE, "..", "ray_trace_pb_amd", "csrc", "rtpb_sweep_host.h"),
         os.path.join(HERE, "..", "include", "rtpb.h")]
 
 _lib = None

@@ -181,6 +181,29 @@ def test_fused_sweep_bitwise_on_golden_systems(case):
         assert fu["count"].sum() > 0
 
 
+@pytest.mark.parametrize("dtype", ["float64", "float32"])
+@pytest.mark.parametrize("sweep", ["spot_sweep", "focus_sweep"])
+def test_sweep_row_shapes_bitwise(sweep, dtype):
+    """Every shape of block row the host plans (csrc/rtpb_sweep_host.h): C5 with an on-axis and an off-axis field
+    point and nw wavelengths each in one batch -- nw = 1: single rows only; 2, 10: bundle rows only; 3, 5, 9, 11: a
+    bundle row of 2, 4 or 8 (and 8 + 2) and a single per point.  667 rays per group: three tiles, the last one
+    ragged, so a single row's second block holds a tile index past the end.  fused == unfused on the raw sums, bit
+    for bit."""
+    system, m0, m1 = systems.c5_system(rt, mat), mat.Constant(1), mat.Constant(1)
+    fields = np.array([[0.0, 0.0, 0.0], systems.c5_field_points(2)[0]])
+    kw = dict(device=DEV, dtype=dtype)
+    if sweep == "focus_sweep":
+        kw["require_image_plane"] = False
+    run = getattr(analysis, sweep)
+    for nw in (1, 2, 3, 5, 9, 10, 11):
+        args = (system, m0, m1, fields, list(np.linspace(0.4, 0.8, nw)), 0.5 * np.pi / 180, 23, 29)
+        fu, _ = run(*args, fused=True, **kw)
+        un, _ = run(*args, fused=False, **kw)
+        assert fu["raw"].shape == (2, nw, 7 if sweep == "spot_sweep" else 16)
+        assert same_bits(fu["raw"], un["raw"]), nw
+        assert fu["count"].min() > 0
+
+
 def test_dist_pt2plane_bitwise_vs_reference():
     g = np.load(os.path.join(GOLDEN, "generators.npz"))
     dist, near = rt.dist_pt2plane(g["intersect_in1"][:, :3], np.array([0., 0.6, 0.8]), np.array([1., 2., 3.]))
@@ -314,7 +337,7 @@ def test_spot_sweep_group_order_does_not_matter():
 
 def fixed_order_sums(plane, group_size, tile=256):
     """The spot kernels' reduction restated in NumPy, operation for operation (csrc/rtpb_analysis.hip
-    spot_partial_kernel / sweep_kernel + spot_final_kernel): per 256-ray tile a pairwise tree
+    spot_partial_kernel + spot_final_kernel, csrc/rtpb_sweep.hip sweep_kernel): per 256-ray tile a pairwise tree
     (red[t] += red[t + w], w = 128 ... 1) of (1, x, y, z, x*x, y*y, x*y) over rays with finite x and y;
     per group, thread t adds tiles t, t + 256, ... in order, then the same tree over the 256 threads."""
     p = np.asarray(plane, dtype=np.float64).reshape(-1, group_size, plane.shape[-1])

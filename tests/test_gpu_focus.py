@@ -21,10 +21,10 @@ NT, NPH = 301, 77                      # 23177 rays per group: 91 tiles, a ragge
 
 
 def fixed_order_focus_sums(plane, group_size, tile=256):
-    """The focus kernels' reduction restated in NumPy, operation for operation (csrc/rtpb_analysis.hip focus_ray /
-    focus_term, focus_partial_kernel / sweep_kernel + spot_final_kernel): u = dx / dz, v = dy / dz; a ray counts when
-    x, y, u and v are finite; per 256-ray tile a pairwise tree (red[t] += red[t + w], w = 128 ... 1) of the sixteen
-    terms; per group, thread t adds tiles t, t + 256, ... in order, then the same tree over the 256 threads."""
+    """The focus kernels' reduction restated in NumPy, operation for operation (csrc/rtpb_stats.h focus_ray /
+    focus_term, rtpb_analysis.hip focus_partial_kernel + spot_final_kernel, rtpb_sweep.hip sweep_kernel):
+    u = dx / dz, v = dy / dz; a ray counts when x, y, u and v are finite; per 256-ray tile a pairwise tree
+    (red[t] += red[t + w], w = 128 ... 1) of the sixteen terms; per group, thread t adds tiles t, t + 256, ... in order, then the same tree over the 256 threads."""
     p = np.asarray(plane, dtype=np.float64).reshape(-1, group_size, plane.shape[-1])
     G = p.shape[0]
     tiles = -(-group_size // tile)

@@ -35,9 +35,14 @@ def dump(outdir, csrc=_build.CSRC):
 LABEL = re.compile(r"BB\d+_")
 
 
+COMMENT = re.compile(r"\s*;.*$")
+KERNEL = re.compile(r"^\s*\.amdhsa_kernel\s+(\S+)")
+
+
 def functions(path):
     """{symbol: body} with basic-block labels renumbered per function (.LBB<function index>_<block>
-    depends on the function's position in its file, not on its code)."""
+    depends on the function's position in its file, not on its code) and without comments: the column of a
+    trailing comment moves with the width of that index, and comment-only lines are no instructions."""
     funcs, cur, body = {}, None, []
     for line in open(path):
         m = FUNC.match(line)
@@ -49,18 +54,39 @@ def functions(path):
                 funcs[cur] = "".join(body)
                 cur = None
             else:
-                body.append(LABEL.sub("BB_", line))
+                line = COMMENT.sub("", line).rstrip()
+                if line:
+                    body.append(LABEL.sub("BB_", line) + "\n")
     return funcs
+
+
+def descriptors(path):
+    """{symbol: the kernel's .amdhsa_kernel ... .end_amdhsa_kernel block}: registers, LDS and scratch bytes."""
+    desc, cur, body = {}, None, []
+    for line in open(path):
+        m = KERNEL.match(line)
+        if m:
+            cur, body = m.group(1), []
+        elif cur is not None:
+            if line.strip() == ".end_amdhsa_kernel":
+                desc[cur] = "".join(body)
+                cur = None
+            else:
+                body.append(COMMENT.sub("", line).rstrip() + "\n")
+    return desc
 
 
 def compare(a, b):
     fa, fb = {}, {}
+    da, db = {}, {}
     for p in glob.glob(os.path.join(a, "*.s")):
         fa.update(functions(p))
+        da.update(descriptors(p))
     for p in glob.glob(os.path.join(b, "*.s")):
         fb.update(functions(p))
-    same = [k for k in fa if k in fb and fa[k] == fb[k]]
-    diff = [k for k in fa if k in fb and fa[k] != fb[k]]
+        db.update(descriptors(p))
+    same = [k for k in fa if k in fb and fa[k] == fb[k] and da.get(k) == db.get(k)]
+    diff = [k for k in fa if k in fb and k not in same]
     only_a = [k for k in fa if k not in fb]
     only_b = [k for k in fb if k not in fa]
     print(f"functions: {len(fa)} before, {len(fb)} after; identical {len(same)}, different {len(diff)}, "
@@ -71,7 +97,7 @@ def compare(a, b):
         print("removed", k)
     for k in only_b:
         print("added", k)
-    return not diff
+    return not (diff or only_a or only_b)
 
 
 def valu(a, b, pattern="."):

@@ -91,7 +91,7 @@ def compile_all():
 
 SWEEP_SRC = r'''
 #define __builtin_expect(c, v) ({ const bool c_ = (c); if (c_ != static_cast<bool>(v)) __builtin_unreachable(); c_; })
-#include "rtpb_analysis.hip"
+#include "rtpb_sweep.hip"
 '''
 
 
