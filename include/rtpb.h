@@ -54,7 +54,9 @@ extern "C" {
                                    never synchronises the device (retired mappings are released by the
                                    next allocation that maps new memory, or by rtpb_buffer_trim)
                                 9: + rtpb_trace_packed (rtpb_trace_checked's arguments in one struct)
-                                10: + rtpb_focus_stats / rtpb_focus_sweep (through-focus statistics) */
+                                10: + rtpb_focus_stats / rtpb_focus_sweep (through-focus statistics);
+                                    rtpb_spot_image / rtpb_image_sweep (spot images) joined within 10: new
+                                    symbols only, nothing existing changed */
 
 /* ---- error codes ---------------------------------------------------------------------------- */
 #define RTPB_OK 0
@@ -391,6 +393,34 @@ int rtpb_focus_sweep(const rtpb_plan* plan, int32_t device, int64_t n_groups, co
                      int64_t n_thetas, int64_t nphis, const double center_ray[3], const double ex[3],
                      const double ey[3], const double* theta_cos_sin, const double* phi_cos_sin, double* workspace,
                      int64_t workspace_len, double* stats_out, void* stream);
+
+/* Spot images: per group, a 2-D histogram of the final positions -- what a spot diagram shows when the rays are
+   too many to scatter-plot or to store.  A group's window is four doubles {x_lo, y_lo, x_scale, y_scale}; the
+   image has nx columns and ny rows, both at most RTPB_MAX_IMAGE_SIDE.  A ray COUNTS exactly when it counts for
+   rtpb_spot_stats / rtpb_spot_sweep (x and y finite, in the storage type).  For a counting ray
+   tx = (x - x_lo) * x_scale and ty = (y - y_lo) * y_scale (one rounded subtract, one rounded multiply); it is
+   INSIDE iff 0 <= tx < nx and 0 <= ty < ny, compared in floating point, so NaN or infinite windows and
+   overflowing products are outside; only then ix = (int)tx, iy = (int)ty and image[g][iy][ix] += 1.  A counting
+   ray that is not inside adds 1 to outside[g]: image[g].sum() + outside[g] is the group's spot count, exactly.
+   Integer counts: the result does not depend on the order in which rays arrive.
+   image_out (device, n_groups*ny*nx int32) and outside_out (device, n_groups int32): each call zeroes its
+   n_groups slices on `stream` before counting; no workspace.  At most 2^31 - 1 rays per group (RTPB_E_LIMIT).
+   The arguments are checked before the device is.
+   rtpb_spot_image: one (N, 8) AOS plane split into groups as for rtpb_spot_stats; windows: DEVICE, n_groups x 4. */
+#define RTPB_MAX_IMAGE_SIDE 4096
+int rtpb_spot_image(int32_t device, int32_t dtype, const void* plane, int64_t group_size, int64_t n_groups,
+                    const double* windows, int32_t nx, int32_t ny, int32_t* image_out, int32_t* outside_out,
+                    void* stream);
+
+/* Fused spot-image sweep: rtpb_spot_sweep with each counted ray binned into its group's image instead of summed --
+   the same arguments, row planning and kernel, and its group and tile limits.  windows: HOST, n_groups x 4 (it
+   rides in the sweep's one upload).  The images are identical to rtpb_ray_fan_tables + rtpb_trace (final plane)
+   + rtpb_spot_image in the plan's storage type. */
+int rtpb_image_sweep(const rtpb_plan* plan, int32_t device, int64_t n_groups, const double* group_params,
+                     int64_t n_thetas, int64_t nphis, const double center_ray[3], const double ex[3],
+                     const double ey[3], const double* theta_cos_sin, const double* phi_cos_sin,
+                     const double* windows, int32_t nx, int32_t ny, int32_t* image_out, int32_t* outside_out,
+                     void* stream);
 
 /* ---- pupil-phase interpolation (scripts/2022_02_06_perfect_imaging_system_psf.py:90-105) */
 /* A 2-D Delaunay triangulation with one value per vertex, in scipy.spatial.Delaunay's representation,

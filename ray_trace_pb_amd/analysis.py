@@ -3,7 +3,8 @@ group and a chunked spot-diagram sweep that never leaves HBM (BASELINE configs[4
 
 The reference computes spot diagrams in user scripts with NumPy on the full host history; here the
 fans are generated on the GPU (``rtpb_ray_fan_tables``), traced with only the final plane stored, and reduced
-on the GPU with a deterministic fixed-order reduction (``rtpb_spot_stats``).
+on the GPU with a deterministic fixed-order reduction (``rtpb_spot_stats``) -- or binned into per-group spot
+images of integer counts (``rtpb_spot_image``, :func:`image_sweep`).
 """
 import time
 
@@ -293,6 +294,235 @@ def _spot_sweep_fused(low, S, field_points, wavelengths, theta_max, n_thetas, np
                         "hbm_bytes": nbytes, "hbm_GBps": nbytes / (ms * 1e-3) / 1e9 if ms > 0 else None})
     summ = summary(raw.reshape(nf, nw, ncols))
     return summ, {"seconds": dt, "rays": G * per, "ray_surface_per_s": G * per * S / dt, "per_device": per_dev}
+
+
+def _bins(bins):
+    """(nx, ny) from an int or a pair."""
+    try:
+        nx, ny = (bins, bins) if np.ndim(bins) == 0 else bins
+        ok = all(float(b) == int(b) for b in (nx, ny))
+    except (TypeError, ValueError):
+        ok = False
+    if not ok or not (1 <= int(nx) <= C.RTPB_MAX_IMAGE_SIDE and 1 <= int(ny) <= C.RTPB_MAX_IMAGE_SIDE):
+        raise ValueError(f"bins must be an int or a pair (nx, ny) of ints in 1 ... {C.RTPB_MAX_IMAGE_SIDE}")
+    return int(nx), int(ny)
+
+
+def image_windows(centers, half_widths, bins):
+    """Windows (..., 4) float64 {x_lo, y_lo, x_scale, y_scale} of spot images with ``bins`` (an int, or (nx, ny))
+    bins: ``centers`` (..., 2) -- or (..., 3), the z ignored, as ``summary["centroid"]`` -- and ``half_widths``,
+    a scalar, (...) or (..., 2) for (hx, hy).  x_lo = cx - hx and x_scale = nx / (2 * hx), the same for y: bin ix
+    covers x_lo + ix / x_scale <= x < x_lo + (ix + 1) / x_scale up to rounding (the rule itself is
+    tx = (x - x_lo) * x_scale, inside iff 0 <= tx < nx, ix = int(tx))."""
+    nx, ny = _bins(bins)
+    c = np.asarray(centers, dtype=np.float64)
+    if c.ndim == 0 or c.shape[-1] not in (2, 3):
+        raise ValueError("centers must have shape (..., 2) or (..., 3)")
+    h = np.asarray(half_widths, dtype=np.float64)
+    if h.ndim == c.ndim and h.shape[-1] == 2:
+        hx, hy = h[..., 0], h[..., 1]
+    else:
+        hx = hy = h
+    try:
+        out = np.empty(np.broadcast_shapes(c.shape[:-1], hx.shape) + (4,))
+    except ValueError:
+        raise ValueError("half_widths must be a scalar, or shaped as the groups of centers, or that with (hx, hy)")
+    out[..., 0] = c[..., 0] - hx
+    out[..., 1] = c[..., 1] - hy
+    with np.errstate(divide="ignore", invalid="ignore"):
+        out[..., 2] = nx / (2 * hx)
+        out[..., 3] = ny / (2 * hy)
+    return out
+
+
+def image_edges(windows, bins):
+    """(x_edges (..., nx + 1), y_edges (..., ny + 1)) of the windows' bins: lo + i / scale."""
+    nx, ny = _bins(bins)
+    w = np.asarray(windows, dtype=np.float64)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        return (w[..., 0, None] + np.arange(nx + 1) / w[..., 2, None],
+                w[..., 1, None] + np.arange(ny + 1) / w[..., 3, None])
+
+
+def spot_image_raw(plane, group_size, windows, bins, stream=None):
+    """Spot images of a torch CUDA (N, 8) plane, N = n_groups * group_size (``rtpb_spot_image``): per group the
+    counts of the rays' (x, y) in ``bins`` (an int, or (nx, ny)) bins of its window, ``windows`` (n_groups, 4) as
+    :func:`image_windows` gives them.  Returns (image (n_groups, ny, nx), outside (n_groups,)), torch int32: a ray
+    with finite x and y lands in exactly one bin or in ``outside``; the others are not counted."""
+    import torch
+    nx, ny = _bins(bins)
+    n = plane.shape[0]
+    if n % group_size:
+        raise ValueError("plane length must be a multiple of group_size")
+    ngroups = n // group_size
+    if torch.is_tensor(windows):
+        w = windows.to(device=plane.device, dtype=torch.float64).contiguous()
+    else:
+        w = torch.from_numpy(np.array(windows, dtype=np.float64)).to(plane.device)
+    if tuple(w.shape) != (ngroups, 4):
+        raise ValueError("windows must have shape (n_groups, 4)")
+    plane = plane.contiguous()
+    image = torch.empty((ngroups, ny, nx), dtype=torch.int32, device=plane.device)
+    outside = torch.empty((ngroups,), dtype=torch.int32, device=plane.device)
+    if stream is None:
+        stream = torch.cuda.current_stream(plane.device).cuda_stream
+    C.check(C.lib().rtpb_spot_image(plane.device.index or 0,
+                                    C.RTPB_F64 if plane.dtype == torch.float64 else C.RTPB_F32, plane.data_ptr(),
+                                    group_size, ngroups, w.data_ptr(), nx, ny, image.data_ptr(), outside.data_ptr(),
+                                    stream))
+    return image, outside
+
+
+def auto_image_windows(summary, bins, sigmas=4.0):
+    """The windows :func:`image_sweep` chooses from a :func:`spot_sweep` summary: centred on each group's centroid,
+    half-width ``sigmas * rms_radius`` -- or 1.0 where the group is empty or its RMS radius is not a positive finite
+    number (a dead group's centroid is NaN: its window holds nothing, as there is nothing to hold)."""
+    rms = np.asarray(summary["rms_radius"], dtype=np.float64)
+    with np.errstate(invalid="ignore"):
+        half = sigmas * rms
+        good = (np.asarray(summary["count"]) > 0) & np.isfinite(half) & (half > 0)
+    return image_windows(summary["centroid"], np.where(good, half, 1.0), bins)
+
+
+def image_sweep(system, initial_material, final_material, field_points, wavelengths, theta_max, n_thetas, nphis=1,
+                center_ray=(0, 0, 1), device="cuda:0", dtype="float64", bins=64, windows=None, sigmas=4.0,
+                groups_per_batch=None, fused=True, devices=None):
+    """Spot-diagram IMAGES for every (field point, wavelength): :func:`spot_sweep`'s fans, each ray's final (x, y)
+    counted into the group's ``bins`` (an int, or (nx, ny)) image in the same pass (``rtpb_image_sweep``; with
+    ``fused=False`` fan generation -> trace planes='final' -> ``rtpb_spot_image``; identical counts).
+
+    ``windows`` (n_fields, n_wavelengths, 4), as :func:`image_windows` gives them, says what each image covers.
+    With ``windows=None`` a :func:`spot_sweep` with the same arguments runs first and each window is centred on the
+    group's centroid with half-width ``sigmas * rms_radius`` (:func:`auto_image_windows`), so the rays are traced
+    twice.  ``devices`` and ``groups_per_batch`` as for :func:`spot_sweep`.
+
+    Returns (summary, timing): ``image`` (n_fields, n_wavelengths, ny, nx) int32, ``outside`` -- the rays that
+    count for the spot statistics but fall outside the window -- and ``count`` = image.sum + outside, both
+    (n_fields, n_wavelengths) int64, ``windows``, and ``x_edges`` (..., nx + 1) / ``y_edges`` (..., ny + 1), the bin
+    edges lo + i / scale; the timing dict has :func:`spot_sweep`'s shape and covers the image pass alone."""
+    import torch
+    nx, ny = _bins(bins)
+    fp = np.atleast_2d(np.asarray(field_points, dtype=float))
+    wl = np.atleast_1d(np.asarray(wavelengths, dtype=float))
+    nf, nw = fp.shape[0], wl.size
+    if windows is None:
+        spot, _ = spot_sweep(system, initial_material, final_material, field_points, wavelengths, theta_max,
+                             n_thetas, nphis, center_ray=center_ray, device=device, dtype=dtype,
+                             groups_per_batch=groups_per_batch, fused=fused, devices=devices)
+        windows = auto_image_windows(spot, (nx, ny), sigmas)
+    windows = np.ascontiguousarray(windows, dtype=np.float64)
+    if windows.shape != (nf, nw, 4):
+        raise ValueError("windows must have shape (n_fields, n_wavelengths, 4)")
+    if np.linalg.norm(np.asarray(center_ray, dtype=float)) != 1:
+        raise ValueError("center_ray must be a unit vector")
+    if devices is not None and not fused:
+        raise ValueError("devices= needs the fused sweep")
+    dev = torch.device(device)
+    tdt = torch.float64 if dtype in ("float64", np.float64) else torch.float32
+    code = C.RTPB_F64 if tdt == torch.float64 else C.RTPB_F32
+    mats = [initial_material] + list(system.materials) + [final_material]
+    keys = wl if tdt == torch.float64 else wl.astype(np.float32).astype(np.float64)    # (as _sweep lowers them)
+    low = E.lower(system.surfaces, mats, lambda: np.unique(keys), code)
+    S = len(system.surfaces)
+    G, per = nf * nw, n_thetas * nphis
+    win = windows.reshape(G, 4)
+    if fused:
+        devs = [dev] if devices is None else [torch.device("cuda", int(d)) for d in devices]
+        image, outside, timing = _image_sweep_fused(low, S, fp, wl, theta_max, n_thetas, nphis, center_ray, devs,
+                                                    groups_per_batch, win, nx, ny)
+    else:
+        if groups_per_batch is None:
+            groups_per_batch = max(1, min(G, (1 << 27) // per))     # ~128M rays in flight
+        sel = E.resolve_planes("final", S)
+        rays = torch.empty((groups_per_batch * per, 8), dtype=tdt, device=dev)
+        out = torch.empty((1, groups_per_batch * per, 8), dtype=tdt, device=dev)
+        image = np.zeros((G, ny, nx), dtype=np.int32)
+        outside = np.zeros(G, dtype=np.int32)
+        torch.cuda.synchronize(dev)
+        t0 = time.perf_counter()
+        for b0 in range(0, G, groups_per_batch):
+            nb = min(groups_per_batch, G - b0)
+            for k in range(nb):                      # generate each fan in place in the batch buffer
+                _fan_into(rays[k * per:(k + 1) * per], fp[(b0 + k) // nw], theta_max, n_thetas, wl[(b0 + k) % nw],
+                          nphis, center_ray, code)
+            m = nb * per
+            E.trace_device(low, rays[:m], sel, out=out[:, :m])
+            im, outs = spot_image_raw(out[0, :m], per, win[b0:b0 + nb], (nx, ny))
+            image[b0:b0 + nb], outside[b0:b0 + nb] = im.cpu().numpy(), outs.cpu().numpy()
+        torch.cuda.synchronize(dev)
+        dt = time.perf_counter() - t0
+        timing = {"seconds": dt, "rays": G * per, "ray_surface_per_s": G * per * S / dt}
+    image = image.reshape(nf, nw, ny, nx)
+    outside = outside.reshape(nf, nw).astype(np.int64)
+    xe, ye = image_edges(windows, (nx, ny))
+    return {"image": image, "outside": outside, "count": image.sum(axis=(-2, -1), dtype=np.int64) + outside,
+            "windows": windows, "x_edges": xe, "y_edges": ye}, timing
+
+
+def _image_sweep_fused(low, S, field_points, wavelengths, theta_max, n_thetas, nphis, center_ray, devs,
+                       groups_per_batch, win, nx, ny):
+    """The fused image sweep over the devices: :func:`_spot_sweep_fused`'s group order, sharding and batches, with
+    ``rtpb_image_sweep`` and per device the images in place of the workspace and statistics."""
+    import torch
+    from .raytrace import _fan_tables, shard_bounds
+    c = np.array(center_ray)
+    enx, eny, tcs, pcs = _fan_tables(float(theta_max), int(n_thetas), int(nphis), tuple(c.tolist()), c.dtype.str)
+    nf, nw = field_points.shape[0], wavelengths.size
+    params = np.empty((nf * nw, 4))
+    params[:, 0:3] = np.repeat(field_points, nw, axis=0)          # group = field * nw + wavelength
+    params[:, 3] = np.tile(wavelengths, nf)
+    G = params.shape[0]
+    per = n_thetas * nphis
+    if groups_per_batch is None:
+        groups_per_batch = max(1, min(G, 65535))
+        if groups_per_batch >= nw:                                # whole field points per batch (bundle rows)
+            groups_per_batch -= groups_per_batch % nw
+    vec = [np.ascontiguousarray(np.asarray(v, dtype=np.float64).ravel()) for v in (c, enx, eny)]
+    if nf >= len(devs):
+        bounds = [(f0 * nw, f1 * nw) for f0, f1 in shard_bounds(nf, len(devs))]
+    else:
+        bounds = shard_bounds(G, len(devs))
+    work = []
+    for (g0, g1), dev in zip(bounds, devs):
+        image = torch.empty((max(g1 - g0, 1), ny, nx), dtype=torch.int32, device=dev)
+        outside = torch.empty((max(g1 - g0, 1),), dtype=torch.int32, device=dev)
+        ev = (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
+        work.append((dev, g0, g1, image, outside, ev, torch.cuda.current_stream(dev)))
+    for dev in devs:
+        torch.cuda.synchronize(dev)
+    t0 = time.perf_counter()
+    sweep = C.lib().rtpb_image_sweep
+    with E.plan_ref(low) as plan:
+        for dev, g0, g1, image, outside, ev, st in work:
+            ev[0].record(st)
+        nb = max(-(-(g1 - g0) // groups_per_batch) for _, g0, g1, *_ in work)
+        for k in range(nb):                                       # round-robin over the devices, all asynchronous
+            for dev, g0, g1, image, outside, ev, st in work:
+                b0 = g0 + k * groups_per_batch
+                b1 = min(g1, b0 + groups_per_batch)
+                if b0 >= b1:
+                    continue
+                gp = np.ascontiguousarray(params[b0:b1])
+                wn = np.ascontiguousarray(win[b0:b1])
+                C.check(sweep(plan, dev.index or 0, b1 - b0, gp.ctypes.data, int(n_thetas), int(nphis),
+                              vec[0].ctypes.data, vec[1].ctypes.data, vec[2].ctypes.data, tcs.ctypes.data,
+                              pcs.ctypes.data, wn.ctypes.data, nx, ny, image[b0 - g0:b1 - g0].data_ptr(),
+                              outside[b0 - g0:b1 - g0].data_ptr(), st.cuda_stream))
+        for dev, g0, g1, image, outside, ev, st in work:
+            ev[1].record(st)
+        images = np.concatenate([image[:g1 - g0].cpu().numpy() for _, g0, g1, image, *_ in work])
+        outs = np.concatenate([outside[:g1 - g0].cpu().numpy() for _, g0, g1, _, outside, *_ in work])
+    dt = time.perf_counter() - t0
+    per_dev = []
+    for dev, g0, g1, image, outside, ev, st in work:
+        ms = ev[0].elapsed_time(ev[1])
+        # HBM bytes of the fused sweep: the counters, cleared and then added to (the rays never leave the registers)
+        nbytes = (g1 - g0) * (ny * nx + 1) * 4 * 2
+        per_dev.append({"device": dev.index or 0, "groups": g1 - g0, "rays": (g1 - g0) * per, "kernel_ms": ms,
+                        "ray_surface_per_s": (g1 - g0) * per * S / (ms * 1e-3) if ms > 0 else None,
+                        "hbm_bytes": nbytes, "hbm_GBps": nbytes / (ms * 1e-3) / 1e9 if ms > 0 else None})
+    return images, outs, {"seconds": dt, "rays": G * per, "ray_surface_per_s": G * per * S / dt,
+                          "per_device": per_dev}
 
 
 def _fan_into(buf, pt, theta_max, n_thetas, wavelength, nphis, center_ray, code):

@@ -8,8 +8,9 @@
 //   rtpb_trace.hip         the fused trace kernel, rtpb_trace / rtpb_trace_host, tuning and timing
 //   rtpb_generators.hip    device ray fans and collimated bundles (RT:45-161)
 //   rtpb_analysis.hip      intersect_rays, the plane statistics (spot and focus), grid interpolation
-//   rtpb_sweep.hip         the fused spot / focus sweep (rtpb_stats.h: what it shares with the plane statistics;
-//                          rtpb_sweep_host.h: its row planning, media table and upload layout, plain C++)
+//   rtpb_image.hip         the spot image of a plane (binned ray counts per group)
+//   rtpb_sweep.hip         the fused spot / focus / image sweep (rtpb_stats.h: what it shares with the plane
+//                          kernels; rtpb_sweep_host.h: its row planning, media table and upload layout, plain C++)
 //   rtpb_surface_ops.hip   propagate_ray2plane and the user-geometry hook kernels
 #pragma once
 
@@ -449,6 +450,13 @@ struct StreamScratch {
 // The second pass of the plane statistics and of the sweeps (spot_final_kernel, rtpb_analysis.hip): n_stats is 7
 // (spot) or 16 (focus) sums per group, from partials[n_groups][tiles][n_stats].
 int launch_stats_final(int n_stats, double* partials, double* stats, int64_t n_groups, int64_t tiles, hipStream_t st);
+
+// What the two image calls share (rtpb_image.hip): the checks of the image arguments -- `call` names the call in the
+// message ("spot-image", "image-sweep"), group_size is the rays per group -- and the zeroing of a call's n_groups
+// slices of both outputs on its stream.
+int image_check(const char* call, int32_t nx, int32_t ny, int64_t group_size, int64_t n_groups, const void* windows,
+                const void* image_out, const void* outside_out);
+int image_clear(int32_t* image_out, int32_t* outside_out, int64_t n_groups, int32_t nx, int32_t ny, hipStream_t st);
 
 }  // namespace rtpbi
 

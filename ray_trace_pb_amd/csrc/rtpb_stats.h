@@ -1,7 +1,7 @@
-// rtpb_stats.h -- what the plane statistics (rtpb_analysis.hip) and the fused sweep (rtpb_sweep.hip) share: the
-// statistics sets, the one definition of a ray's contribution to the focus statistics, the reduction's argument
-// block and its block-wide tree.  Everything here has internal linkage, as it had inside the one unit: each unit's
-// kernels take its own SpotArgs.
+// rtpb_stats.h -- what the plane kernels (rtpb_analysis.hip, rtpb_image.hip) and the fused sweep (rtpb_sweep.hip)
+// share: the statistics sets, the one definition of a ray's contribution to the focus statistics and to a spot image,
+// the wave's aggregated image adds, the reduction's argument block and its block-wide tree.  Everything here has
+// internal linkage, as it had inside the one unit: each unit's kernels take its own SpotArgs.
 #pragma once
 
 #include "rtpb_internal.h"
@@ -51,6 +51,44 @@ RTPB_HD double focus_term(const FocusRay& f, int k) {
     case 13: return f.y * f.v;
     case 14: return f.x * f.v;
     default: return f.y * f.u;
+    }
+}
+
+// Spot images (rtpb_spot_image / rtpb_image_sweep): a 2-D histogram of the final positions per group, int32 counts,
+// so the result is exact and independent of the order of arrival.  The one definition of a ray's contribution, for
+// the plane kernel and the fused sweep alike: x and y are the ray's final position rounded to the storage type, w the
+// group's window {x_lo, y_lo, x_scale, y_scale}.  A ray counts when the spot statistics count it (x and y finite; the
+// sweep adds its own dead-row rule before calling).  tx = (x - x_lo) * x_scale and ty likewise, each one rounded
+// subtract and one rounded multiply; the ray is inside iff 0 <= tx < nx and 0 <= ty < ny, compared in floating point
+// (a NaN or infinite window, or an overflowing tx, is outside), and only then are tx and ty converted to integers:
+// no index exists for a ray that failed the test.  Returns the bin iy * nx + ix, kImageOutside for a counting ray
+// that is not inside, kImageSkip for a ray that does not count.  nx, ny <= RTPB_MAX_IMAGE_SIDE, so a bin fits an int.
+constexpr int kImageSkip = -1, kImageOutside = -2;
+RTPB_HD int image_bin(double x, double y, const double (&w)[4], int nx, int ny) {
+    if (!(x - x == 0.0 && y - y == 0.0)) return kImageSkip;
+    const double tx = (x - w[0]) * w[2], ty = (y - w[1]) * w[3];
+    if (tx >= 0.0 && tx < double(nx) && ty >= 0.0 && ty < double(ny))
+        return static_cast<int>(ty) * nx + static_cast<int>(tx);
+    return kImageOutside;
+}
+
+// One wave's contributions to one group's image (image: the group's ny * nx counters, outside: its one; both
+// wave-uniform), bin from image_bin.  Every lane of the wave must call it.  Per-ray atomics would serialise on the
+// few hot bins of a tight spot, so the wave aggregates first: while a lane is pending, the first pending lane's bin is
+// broadcast, the lanes that share it are counted with one ballot, that lane issues one no-return atomic add of the
+// count and the matched lanes retire; the outside rays take one add per wave.  Integer adds: any order, same image.
+__device__ __forceinline__ void wave_image_add(int bin, int32_t* __restrict__ image, int32_t* __restrict__ outside) {
+    const int lane = static_cast<int>(__lane_id());
+    const unsigned long long out = __ballot(bin == kImageOutside);
+    if (out != 0 && lane == __ffsll(out) - 1) atomicAdd(outside, __popcll(out));
+    unsigned long long pending = __ballot(bin >= 0);
+    while (pending != 0) {
+        const int leader = __ffsll(pending) - 1;
+        const int b = __builtin_amdgcn_readlane(bin, leader);
+        // (a retired lane's bin differs from b: every lane that shares a bin retires with it)
+        const unsigned long long same = __ballot(bin == b);
+        if (lane == leader) atomicAdd(image + b, __popcll(same));
+        pending &= ~same;
     }
 }
 

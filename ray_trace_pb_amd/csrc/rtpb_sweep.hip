@@ -1,5 +1,6 @@
-// rtpb_sweep.hip -- the fused spot-diagram / through-focus sweep: generate + trace + reduce in one
-// kernel, rtpb_spot_sweep and rtpb_focus_sweep.  The statistics it shares with the plane kernels are rtpb_stats.h,
+// rtpb_sweep.hip -- the fused spot-diagram / through-focus / spot-image sweep: generate + trace +
+// reduce in one kernel, rtpb_spot_sweep, rtpb_focus_sweep and rtpb_image_sweep.  What it shares with the plane
+// kernels (the statistics, the image's contribution rule) is rtpb_stats.h,
 // the host arithmetic of a call (row planning, media table, upload layout) rtpb_sweep_host.h.
 #include "rtpb_stats.h"
 #include "rtpb_sweep_host.h"
@@ -14,6 +15,7 @@ namespace {
 // same 256-ray tile partials as spot_partial_kernel.  spot_final_kernel then produces statistics
 // bit-identical to generating, tracing (planes='final') and reducing separately -- without the
 // 3 x 64 B per ray of HBM traffic and the launches in between.
+struct SweepImage;
 struct SweepArgs {
     const DevSurface<double>* __restrict__ surf;
     const DevMaterial<double>* __restrict__ mats;
@@ -24,7 +26,10 @@ struct SweepArgs {
                                         // per surface n_s / n_s+1, 1 / n_s+1 and host_rcp_ok(n_s+1) (0 / 1)
     const int32_t* __restrict__ gidx;   // single rows: the group of block row y; bundle rows: see rows
     const int32_t* __restrict__ rows;   // bundle rows: (offset into gidx, number of groups) of block row y
-    double* __restrict__ partials;
+    union {
+        double* __restrict__ partials;              // spot and focus statistics
+        const SweepImage* __restrict__ image;       // image mode
+    };
     int64_t n_thetas, nphis, gsize, tiles;
     double c[3], ex[3], ey[3];
     int32_t nsurf;
@@ -32,6 +37,16 @@ struct SweepArgs {
     uint32_t nt_mul;
     int32_t nt_shift;
 };
+
+// The image mode's outputs: they ride in the sweep's one upload, followed by the groups' windows (SweepLayout::img
+// and win), so the kernels' argument block keeps its size and layout and the statistics instantiations stay the
+// code they were.
+struct SweepImage {
+    int32_t* image;      // [n_groups][ny][nx]
+    int32_t* outside;    // [n_groups]
+    int32_t nx, ny;
+};
+static_assert(sizeof(SweepImage) % sizeof(double) == 0, "the windows follow it");
 
 template <typename TS>
 __device__ __forceinline__ double stored(double v) { return static_cast<double>(static_cast<TS>(v)); }
@@ -76,11 +91,14 @@ constexpr int kStateRows = 11;                     // bundle state per lane: x y
 // reflect and lens_step compute dx, dy and dz in full whatever the mode, and a killed row is all NaN (the mode only
 // skips the position fill after a NaN direction and the at-plane) -- so the last surface runs the same step as the
 // others.  Single rows reduce eight of the sixteen statistics at a time (16 KB of LDS), bundle rows two as before.
+// NS = kImageStats (rtpb_image_sweep): no statistics, each counted ray goes into its group's image instead
+// (image_bin, wave_image_add); the rule of which rays count is the spot statistics', and there are no red tiles.
+constexpr int kImageStats = 0;
 template <typename TS, int FEAT, bool BUNDLE, int NS = kStats>
 __global__ __launch_bounds__(kBlock) RTPB_SWEEP_ATTR void sweep_kernel(SweepArgs a) {
     static_assert(!BUNDLE || (FEAT & 16) != 0, "bundles: host-evaluated media");
-    static_assert(NS == kStats || NS == kFocusStats, "spot or focus statistics");
-    constexpr int kRedRows = BUNDLE ? 2 : NS == kStats ? kStats : 8;
+    static_assert(NS == kStats || NS == kFocusStats || NS == kImageStats, "spot or focus statistics, or the image");
+    constexpr int kRedRows = NS == kImageStats ? 1 : BUNDLE ? 2 : NS == kStats ? kStats : 8;
     __shared__ double red[kRedRows][kBlock];
     __shared__ double state[BUNDLE ? kStateRows : 1][kBlock];
     const int tid = threadIdx.x;
@@ -218,6 +236,19 @@ __global__ __launch_bounds__(kBlock) RTPB_SWEEP_ATTR void sweep_kernel(SweepArgs
             }
         }
     };
+    // the image mode's counterpart: one ray's contribution to its group's image, by the same rule of the last
+    // surface; every lane reaches the wave's adds, and g is the same in the whole block
+    auto to_image = [&](const Ray<double>& rr, bool ok, int64_t g) {
+        const cptr<SweepImage> im = (cptr<SweepImage>)(a.image);
+        const cptr<double> win = (cptr<double>)(a.image + 1) + 4 * g;
+        const int nx = im->nx, ny = im->ny;
+        int bin = kImageSkip;
+        if (ok && !is_nan(rr.dx)) {
+            const double w[4] = {win[0], win[1], win[2], win[3]};
+            bin = image_bin(stored<TS>(rr.x), stored<TS>(rr.y), w, nx, ny);
+        }
+        wave_image_add(bin, im->image + g * ny * nx, im->outside + g);
+    };
     if constexpr (!BUNDLE) {
 #pragma unroll
         for (int q = 0; q < kSweepRays; ++q) {
@@ -235,7 +266,10 @@ __global__ __launch_bounds__(kBlock) RTPB_SWEEP_ATTR void sweep_kernel(SweepArgs
         for (int q = 0; q < kSweepRays; ++q) n_cur[q] = q == 0 ? mat_n(0, 0) : n_cur[0];
         trace_from(0);
 #pragma unroll
-        for (int q = 0; q < kSweepRays; ++q) reduce(r[q], tile[q] * kBlock + tid < a.gsize, grp[q], tile[q]);
+        for (int q = 0; q < kSweepRays; ++q) {
+            if constexpr (NS == kImageStats) to_image(r[q], tile[q] * kBlock + tid < a.gsize, grp[q]);
+            else reduce(r[q], tile[q] * kBlock + tid < a.gsize, grp[q], tile[q]);
+        }
     } else {
         const int32_t off = a.rows[2 * blockIdx.y], nb = a.rows[2 * blockIdx.y + 1];
         const int64_t t0 = blockIdx.x;
@@ -326,7 +360,10 @@ __global__ __launch_bounds__(kBlock) RTPB_SWEEP_ATTR void sweep_kernel(SweepArgs
             }
             trace_from(s0);
 #pragma unroll
-            for (int q = 0; q < kSweepRays; ++q) reduce(r[q], t0 * kBlock + tid < a.gsize, grp[q], t0);
+            for (int q = 0; q < kSweepRays; ++q) {
+                if constexpr (NS == kImageStats) to_image(r[q], t0 * kBlock + tid < a.gsize, grp[q]);
+                else reduce(r[q], t0 * kBlock + tid < a.gsize, grp[q], t0);
+            }
         }
     }
 }
@@ -349,13 +386,23 @@ int sweep_check(int64_t n_groups, const double* group_params, int64_t n_thetas, 
     return RTPB_OK;
 }
 
+// rtpb_image_sweep's own arguments (NS = kImageStats: no workspace, no statistics)
+struct ImageCall {
+    const double* windows;      // host, n_groups x 4
+    int32_t nx, ny;
+    int32_t* image_out;
+    int32_t* outside_out;
+};
+
 // ... and the sweep itself (checked arguments): plan the block rows, fill and send the one upload, launch the sweep
-// kernels of the statistics set, then the final reduction
+// kernels of the statistics set, then the final reduction -- or, for the image, clear the outputs and launch the
+// image kernels
 template <int NS>
 int sweep_impl(const rtpb_plan* plan_c, int32_t device, int64_t n_groups, const double* group_params,
                int64_t n_thetas, int64_t nphis, const double center_ray[3], const double ex[3], const double ey[3],
                const double* theta_cos_sin, const double* phi_cos_sin, double* workspace, double* stats_out,
-               void* stream) {
+               void* stream, const ImageCall* im = nullptr) {
+    constexpr bool kImage = NS == kImageStats;
     auto* plan = const_cast<rtpb_plan*>(plan_c);
     const int64_t gsize = n_thetas * nphis;
     const int64_t tiles = (gsize + kBlock - 1) / kBlock;
@@ -369,7 +416,8 @@ int sweep_impl(const rtpb_plan* plan_c, int32_t device, int64_t n_groups, const 
     const size_t M = plan->mats.size();
     const SweepRows pr = plan_sweep_rows(group_params, n_groups, pre_n, kSweepRays, kMaxBundle);
     const SweepLayout lay(n_thetas, nphis, n_groups, pre_n ? M + 3 * (M - 1) : 0,
-                          pr.bundles.size() + pr.singles.size() + pr.rows.size());
+                          pr.bundles.size() + pr.singles.size() + pr.rows.size(),
+                          kImage ? sizeof(SweepImage) / sizeof(double) : 0);
     StreamScratch dbuf;
     rc = dbuf.alloc(lay.bytes, st);
     if (rc) return rc;
@@ -386,6 +434,13 @@ int sweep_impl(const rtpb_plan* plan_c, int32_t device, int64_t n_groups, const 
         fill_group_media(dm.data(), M, plan->table.data(), group_params, n_groups, plan->dtype,
                          reinterpret_cast<double*>(h + lay.gn));
     }
+    if constexpr (kImage) {
+        const SweepImage head{im->image_out, im->outside_out, im->nx, im->ny};
+        std::memcpy(h + lay.img, &head, sizeof(head));
+        std::memcpy(h + lay.win, im->windows, size_t(4 * n_groups) * sizeof(double));
+        rc = image_clear(im->image_out, im->outside_out, n_groups, im->nx, im->ny, st);
+        if (rc) return rc;
+    }
     int32_t* hidx = reinterpret_cast<int32_t*>(h + lay.idx);
     hidx = std::copy(pr.bundles.begin(), pr.bundles.end(), hidx);
     hidx = std::copy(pr.singles.begin(), pr.singles.end(), hidx);
@@ -401,7 +456,8 @@ int sweep_impl(const rtpb_plan* plan_c, int32_t device, int64_t n_groups, const 
     a.grp = reinterpret_cast<const double*>(d + lay.grp);
     a.gn = reinterpret_cast<const double*>(d + lay.gn);
     const int32_t* didx = reinterpret_cast<const int32_t*>(d + lay.idx);
-    a.partials = workspace;
+    if constexpr (kImage) a.image = reinterpret_cast<const SweepImage*>(d + lay.img);
+    else a.partials = workspace;
     a.n_thetas = n_thetas;
     a.nphis = nphis;
     a.gsize = gsize;
@@ -435,8 +491,10 @@ int sweep_impl(const rtpb_plan* plan_c, int32_t device, int64_t n_groups, const 
     if (plan->dtype == RTPB_F64) go(double{});
     else go(float{});
     HIP_TRY(hipGetLastError());
-    rc = launch_stats_final(NS, workspace, stats_out, n_groups, tiles, st);
-    if (rc) return rc;
+    if constexpr (!kImage) {
+        rc = launch_stats_final(NS, workspace, stats_out, n_groups, tiles, st);
+        if (rc) return rc;
+    }
     return dbuf.release();
 }
 
@@ -471,6 +529,28 @@ int rtpb_focus_sweep(const rtpb_plan* plan, int32_t device, int64_t n_groups, co
     if (rc) return rc;
     return sweep_impl<kFocusStats>(plan, device, n_groups, group_params, n_thetas, nphis, center_ray, ex, ey,
                                    theta_cos_sin, phi_cos_sin, workspace, stats_out, stream);
+}
+
+int rtpb_image_sweep(const rtpb_plan* plan, int32_t device, int64_t n_groups, const double* group_params,
+                     int64_t n_thetas, int64_t nphis, const double center_ray[3], const double ex[3],
+                     const double ey[3], const double* theta_cos_sin, const double* phi_cos_sin,
+                     const double* windows, int32_t nx, int32_t ny, int32_t* image_out, int32_t* outside_out,
+                     void* stream) {
+    // (the arguments first: a bad call is RTPB_E_INVALID / RTPB_E_LIMIT with or without a GPU)
+    if (!plan) return fail(RTPB_E_INVALID, "plan is NULL");
+    if (n_groups <= 0 || n_thetas <= 0 || nphis <= 0 || !group_params || !center_ray || !ex || !ey ||
+        !theta_cos_sin || !phi_cos_sin)
+        return fail(RTPB_E_INVALID, "bad image-sweep arguments");
+    // (n_thetas * nphis: a product past int64 is past the limit too)
+    const int64_t gsize = n_thetas > 0x7fffffffll / nphis ? 0x80000000ll : n_thetas * nphis;
+    int rc = image_check("image-sweep", nx, ny, gsize, n_groups, windows, image_out, outside_out);
+    if (rc) return rc;
+    if (n_groups > 65535) return fail(RTPB_E_LIMIT, "image-sweep: too many groups");
+    rc = check_device(device);
+    if (rc) return rc;
+    const ImageCall im{windows, nx, ny, image_out, outside_out};
+    return sweep_impl<kImageStats>(plan, device, n_groups, group_params, n_thetas, nphis, center_ray, ex, ey,
+                                   theta_cos_sin, phi_cos_sin, nullptr, nullptr, stream, &im);
 }
 
 }  // extern "C"

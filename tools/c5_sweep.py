@@ -4,6 +4,12 @@ only, spot statistics reduced on the GPU.  One process per GPU (torchrun): field
 across ranks (no collective besides the final gather of the small statistics table).
 
     python tools/c5_sweep.py [--fields 64] [--n-thetas 3163] [--nphis 3162]
+
+``--sweep focus`` times analysis.focus_sweep instead, ``--sweep image`` analysis.image_sweep (``--bins`` x ``--bins``
+images, explicit windows taken from an untimed spot_sweep of the same workload, so the timed pass is one sweep) next
+to a spot_sweep timed in the same process: the line then carries both per-device kernel times and their ratio.
+``--repeats`` times the sweep that often (every repeat's per-device kernel_ms is in the line); ``--lib`` loads
+another build of the library, e.g. the parent commit's, for alternating A/B processes.
 """
 import argparse
 import json
@@ -26,11 +32,20 @@ def main():
     ap.add_argument("--warmup", type=int, default=1,
                     help="untimed small sweeps first (plan creation, code-object load on first launch)")
     ap.add_argument("--lib", default="", help="library build to load instead of the in-tree librtpb.so (A/B)")
+    ap.add_argument("--sweep", default="spot", choices=("spot", "focus", "image"))
+    ap.add_argument("--bins", type=int, default=64, help="--sweep image: bins per side")
+    ap.add_argument("--repeats", type=int, default=1,
+                    help="timed sweeps (the line reports the last, and every repeat's kernel_ms)")
     args = ap.parse_args()
     import torch
     if args.lib:
+        import ctypes
         from ray_trace_pb_amd import _capi
         _capi.LIB_PATH = os.path.abspath(args.lib)
+        # (an older build of the same ABI version lacks the entry points that joined within it)
+        older = ctypes.CDLL(_capi.LIB_PATH)
+        for name in [n for n in _capi.SIGNATURES if not hasattr(older, n)]:
+            del _capi.SIGNATURES[name]
     import ray_trace_pb_amd.materials as mat
     import ray_trace_pb_amd.raytrace as rt
     from ray_trace_pb_amd import analysis
@@ -57,12 +72,36 @@ def main():
                             dtype=args.dtype, devices=devices)
     if world > 1:
         dist.barrier()
-    t0 = time.perf_counter()
-    summ, timing = analysis.spot_sweep(system, mat.Constant(1), mat.Constant(1), mine, wls, theta, args.n_thetas,
-                                       args.nphis, device=dev, dtype=args.dtype, devices=devices)
-    if world > 1:
-        dist.barrier()
-    wall = time.perf_counter() - t0
+    call = (system, mat.Constant(1), mat.Constant(1), mine, wls, theta, args.n_thetas, args.nphis)
+    kw = dict(device=dev, dtype=args.dtype, devices=devices)
+    extra = {}
+    sweep = {"spot": analysis.spot_sweep, "focus": analysis.focus_sweep}.get(args.sweep)
+    if args.sweep == "image":
+        spot, spot_timing = analysis.spot_sweep(*call, **kw)
+        windows = analysis.auto_image_windows(spot, args.bins)
+
+        def sweep(*a, **k):
+            return analysis.image_sweep(*a, bins=args.bins, windows=windows, **k)
+    kernel_ms = []
+    for _ in range(args.repeats):
+        t0 = time.perf_counter()
+        summ, timing = sweep(*call, **kw)
+        if world > 1:
+            dist.barrier()
+        wall = time.perf_counter() - t0
+        kernel_ms.append([d["kernel_ms"] for d in timing.get("per_device", [])])
+    if args.sweep == "image":
+        # the spot sweep again, after the images: both orders are in the line
+        _, spot_after = analysis.spot_sweep(*call, **kw)
+        ms = [[d["kernel_ms"] for d in t["per_device"]] for t in (spot_timing, spot_after)]
+        img = [float(np.median([r[i] for r in kernel_ms])) for i in range(len(kernel_ms[0]))]
+        extra = {"bins": args.bins, "spot_kernel_ms_before_after": ms,
+                 "image_kernel_ms_median": img,
+                 "image_over_spot_kernel_ms": [2 * m / (a + b) for m, a, b in zip(img, *ms)],
+                 "rank0_inside_fraction_first_fields": (summ["image"].sum(axis=(-2, -1))[:2] /
+                                                        np.maximum(summ["count"][:2], 1)).tolist(),
+                 "rank0_occupied_bins_first_fields": (summ["image"] > 0).sum(axis=(-2, -1))[:2].tolist()}
+        summ = dict(spot, count=summ["count"])
     rays = timing["rays"]
     if world > 1:
         t = torch.tensor([wall, float(rays)], dtype=torch.float64)
@@ -71,7 +110,7 @@ def main():
         wall, rays = float(t[0]), float(t[1])
     if rank == 0:
         S = len(system.surfaces)
-        print(json.dumps({"workload": "C5 spot sweep", "fields": len(fields), "wavelengths": len(wls),
+        print(json.dumps({"workload": "C5 %s sweep" % args.sweep, "repeats_kernel_ms": kernel_ms, **extra, "fields": len(fields), "wavelengths": len(wls),
                           "rays_per_group": args.n_thetas * args.nphis, "total_rays": rays, "surfaces": S,
                           "n_gpus": world, "seconds": wall, "ray_surface_per_s": rays * S / wall,
                           "per_device_rank0": timing.get("per_device"),
