@@ -7,6 +7,7 @@ on the GPU with a deterministic fixed-order reduction (``rtpb_spot_stats``) -- o
 images of integer counts (``rtpb_spot_image``, :func:`image_sweep`).
 """
 import time
+from types import SimpleNamespace
 
 import numpy as np
 
@@ -125,9 +126,35 @@ def focus_stats(plane, group_size):
     return summarize_focus(focus_stats_raw(plane, group_size).cpu().numpy())
 
 
-# the two sweeps: (fused entry point, unfused plane reduction, columns, host summary)
-_SPOT = ("rtpb_spot_sweep", spot_stats_raw, 7, summarize)
-_FOCUS = ("rtpb_focus_sweep", focus_stats_raw, 16, summarize_focus)
+# A sweep mode is what differs between the spot, focus and image sweeps, as the drivers below read it:
+#   entry, ncols    the fused C entry point; its statistics per group (None: no workspace to size a batch by)
+#   shard(dev, per, g0, n, batch) -> (outputs, tail): the device tensors that receive groups [g0, g0 + n), one row per
+#                   group, and tail(b0, b1), entry's arguments between the fan tables and the stream for groups
+#                   [b0, b1) of them; ``per`` rays a group, at most ``batch`` groups a call
+#   hbm_bytes(per, n)   what the fused sweep of n groups moves through HBM
+#   host(G), plane(out, per, b0, nb)   unfused: zeroed host arrays for G groups, and the device reduction of the
+#                   final plane ``out`` of groups [b0, b0 + nb), one tensor per host array
+#   finish(nf, nw, *arrays)   the summary from the host arrays, in outputs' / host's order
+def _stats_mode(entry, plane_raw, ncols, summary):
+    """The mode of a statistics sweep: ``plane_raw`` is the unfused plane reduction, ``summary`` the host summary of
+    the raw sums.  Per device: a batch's workspace (the per-tile partial sums) and the shard's statistics."""
+    def shard(dev, per, g0, n, batch):
+        import torch
+        ws = torch.empty(batch * -(-per // 256) * ncols, dtype=torch.float64, device=dev)
+        stats = torch.empty((n, ncols), dtype=torch.float64, device=dev)
+        return (stats,), lambda b0, b1: (ws.data_ptr(), ws.numel(), stats[b0 - g0:b1 - g0].data_ptr())
+
+    return SimpleNamespace(
+        entry=entry, ncols=ncols, shard=shard,
+        # the per-tile partial sums written and read back, and the statistics (the rays never leave the registers)
+        hbm_bytes=lambda per, n: n * -(-per // 256) * ncols * 8 * 2 + n * ncols * 8,
+        host=lambda G: (np.zeros((G, ncols)),),
+        plane=lambda out, per, b0, nb: (plane_raw(out, per),),
+        finish=lambda nf, nw, raw: summary(raw.reshape(nf, nw, ncols)))
+
+
+_SPOT = _stats_mode("rtpb_spot_sweep", spot_stats_raw, 7, summarize)
+_FOCUS = _stats_mode("rtpb_focus_sweep", focus_stats_raw, 16, summarize_focus)
 
 
 def spot_sweep(system, initial_material, final_material, field_points, wavelengths, theta_max, n_thetas, nphis=1,
@@ -177,123 +204,144 @@ def focus_sweep(system, initial_material, final_material, field_points, waveleng
                   nphis, center_ray, device, dtype, groups_per_batch, fused, devices)
 
 
-def _sweep(kind, system, initial_material, final_material, field_points, wavelengths, theta_max, n_thetas, nphis,
+def _grid(field_points, wavelengths):
+    """(n_fields, 3) field points and (n_wavelengths,) wavelengths, float64 (a no-op on such arrays)."""
+    return np.atleast_2d(np.asarray(field_points, dtype=float)), np.atleast_1d(np.asarray(wavelengths, dtype=float))
+
+
+def _sweep(mode, system, initial_material, final_material, field_points, wavelengths, theta_max, n_thetas, nphis,
            center_ray, device, dtype, groups_per_batch, fused, devices):
-    import torch
-    entry, plane_raw, ncols, summary = kind
-    dev = torch.device(device)
-    tdt = torch.float64 if dtype in ("float64", np.float64) else torch.float32
-    code = C.RTPB_F64 if tdt == torch.float64 else C.RTPB_F32
+    """What the three public sweeps share: the argument checks, the lowered system, one of the two drivers, the
+    timing dict and the mode's host summary."""
     if np.linalg.norm(np.asarray(center_ray, dtype=float)) != 1:
         raise ValueError("center_ray must be a unit vector")
-    field_points = np.atleast_2d(np.asarray(field_points, dtype=float))
-    wavelengths = np.atleast_1d(np.asarray(wavelengths, dtype=float))
-    G = field_points.shape[0] * wavelengths.size
-    per = n_thetas * nphis
+    if devices is not None and not fused:
+        raise ValueError("devices= needs the fused sweep")
+    import torch
+    dev = torch.device(device)
+    tdt = torch.float64 if dtype in ("float64", np.float64) else torch.float32
+    field_points, wavelengths = _grid(field_points, wavelengths)
     mats = [initial_material] + list(system.materials) + [final_material]
     # tabulated materials are lowered at the wavelengths the kernels see: the group's wavelength rounded to the
     # storage type (a float32 sweep's rays carry float32 wavelengths, and the table lookup matches exactly)
     keys = wavelengths if tdt == torch.float64 else wavelengths.astype(np.float32).astype(np.float64)
-    low = E.lower(system.surfaces, mats, lambda: np.unique(keys), code)
+    low = E.lower(system.surfaces, mats, lambda: np.unique(keys), C.RTPB_F64 if tdt == torch.float64 else C.RTPB_F32)
     S = len(system.surfaces)
+    fan = (field_points, wavelengths, theta_max, n_thetas, nphis, center_ray)
     if fused:
         devs = [dev] if devices is None else [torch.device("cuda", int(d)) for d in devices]
-        return _spot_sweep_fused(low, S, field_points, wavelengths, theta_max, n_thetas, nphis, center_ray, devs,
-                                 groups_per_batch, entry, ncols, summary)
-    if devices is not None:
-        raise ValueError("devices= needs the fused sweep")
+        arrays, dt, extra = _sweep_fused(mode, low, S, *fan, devs, groups_per_batch)
+    else:
+        arrays, dt, extra = _sweep_unfused(mode, low, S, *fan, dev, tdt, groups_per_batch)
+    nf, nw = field_points.shape[0], wavelengths.size
+    rays = nf * nw * n_thetas * nphis
+    return mode.finish(nf, nw, *arrays), {"seconds": dt, "rays": rays, "ray_surface_per_s": rays * S / dt, **extra}
+
+
+def _sweep_unfused(mode, low, S, field_points, wavelengths, theta_max, n_thetas, nphis, center_ray, dev, tdt,
+                   groups_per_batch):
+    """Fan generation -> trace planes='final' -> ``mode.plane`` per batch of groups, through HBM buffers."""
+    import torch
+    from .raytrace import fan_into
+    nw = wavelengths.size
+    G, per = field_points.shape[0] * nw, n_thetas * nphis
     if groups_per_batch is None:
         groups_per_batch = max(1, min(G, (1 << 27) // per))     # ~128M rays in flight
-    sel = E.resolve_planes("final", len(system.surfaces))
+    sel = E.resolve_planes("final", S)
     rays = torch.empty((groups_per_batch * per, 8), dtype=tdt, device=dev)
     out = torch.empty((1, groups_per_batch * per, 8), dtype=tdt, device=dev)
-    raw = np.zeros((G, ncols))
-    jobs = [(f, w) for f in range(field_points.shape[0]) for w in range(wavelengths.size)]
+    arrays = mode.host(G)
     torch.cuda.synchronize(dev)
     t0 = time.perf_counter()
     for b0 in range(0, G, groups_per_batch):
-        batch = jobs[b0:b0 + groups_per_batch]
-        for k, (f, w) in enumerate(batch):       # generate each fan in place in the batch buffer
-            _fan_into(rays[k * per:(k + 1) * per], field_points[f], theta_max, n_thetas, wavelengths[w], nphis,
-                      center_ray, code)
-        m = len(batch) * per
+        nb = min(groups_per_batch, G - b0)
+        for k in range(nb):                      # generate each fan in place in the batch buffer
+            fan_into(rays[k * per:(k + 1) * per], field_points[(b0 + k) // nw], theta_max, n_thetas,
+                     wavelengths[(b0 + k) % nw], nphis, center_ray)
+        m = nb * per
         E.trace_device(low, rays[:m], sel, out=out[:, :m])
-        raw[b0:b0 + len(batch)] = plane_raw(out[0, :m], per).cpu().numpy()
+        for a, t in zip(arrays, mode.plane(out[0, :m], per, b0, nb)):
+            a[b0:b0 + nb] = t.cpu().numpy()
     torch.cuda.synchronize(dev)
-    dt = time.perf_counter() - t0
-    summ = summary(raw.reshape(field_points.shape[0], wavelengths.size, ncols))
-    return summ, {"seconds": dt, "rays": G * per, "ray_surface_per_s": G * per * S / dt}
+    return arrays, time.perf_counter() - t0, {}
 
 
-def _spot_sweep_fused(low, S, field_points, wavelengths, theta_max, n_thetas, nphis, center_ray, devs,
-                      groups_per_batch, entry="rtpb_spot_sweep", ncols=7, summary=summarize):
-    """The fused sweep of both statistics sets: ``entry`` is the C entry point (``rtpb_spot_sweep`` /
-    ``rtpb_focus_sweep``), ``ncols`` its statistics per group, ``summary`` the host summary of the raw sums."""
+def _sweep_plan(nf, nw, per, n_devices, groups_per_batch=None, ncols=None):
+    """Which groups each launch of a fused sweep takes (no torch, no device): ``nf`` field points x ``nw``
+    wavelengths, group = field * nw + wavelength, ``per`` rays each, over ``n_devices``; ``ncols`` statistics per
+    group, None for the image mode, which has no workspace.  Returns (groups_per_batch, the devices' contiguous
+    ranges [(g0, g1), ...], the launches [(device slot, b0, b1), ...] in issue order)."""
+    from .raytrace import shard_bounds
+    G = nf * nw
+    if groups_per_batch is None:
+        groups_per_batch = min(G, 65535)
+        if ncols is not None:
+            groups_per_batch = min(groups_per_batch, (1 << 26) // (-(-per // 256) * ncols))   # workspace <= 512 MB
+        groups_per_batch = max(1, groups_per_batch)
+        # whole field points per batch: a field point's groups share each ray's generation and first surface
+        # (the kernel's bundle rows), so batches do not split them
+        if groups_per_batch >= nw:
+            groups_per_batch -= groups_per_batch % nw
+    # one range per device -- whole field points when there are enough of them
+    if nf >= n_devices:
+        bounds = [(f0 * nw, f1 * nw) for f0, f1 in shard_bounds(nf, n_devices)]
+    else:
+        bounds = shard_bounds(G, n_devices)
+    # batches issued round-robin over the devices: every launch is asynchronous, so they run concurrently
+    launches = []
+    for k in range(max(-(-(g1 - g0) // groups_per_batch) for g0, g1 in bounds)):
+        for slot, (g0, g1) in enumerate(bounds):
+            b0 = g0 + k * groups_per_batch
+            if b0 < g1:
+                launches.append((slot, b0, min(g1, b0 + groups_per_batch)))
+    return groups_per_batch, bounds, launches
+
+
+def _sweep_fused(mode, low, S, field_points, wavelengths, theta_max, n_thetas, nphis, center_ray, devs,
+                 groups_per_batch):
+    """One ``mode.entry`` kernel per batch of groups (generation, trace and reduction: no rays touch HBM), the
+    groups split over ``devs`` as :func:`_sweep_plan` says."""
     import torch
-    from .raytrace import _fan_tables, shard_bounds
+    from .raytrace import _fan_tables
     c = np.array(center_ray)
     enx, eny, tcs, pcs = _fan_tables(float(theta_max), int(n_thetas), int(nphis), tuple(c.tolist()), c.dtype.str)
     nf, nw = field_points.shape[0], wavelengths.size
     params = np.empty((nf * nw, 4))
     params[:, 0:3] = np.repeat(field_points, nw, axis=0)          # group = field * nw + wavelength
     params[:, 3] = np.tile(wavelengths, nf)
-    G = params.shape[0]
     per = n_thetas * nphis
-    tiles = -(-per // 256)
-    if groups_per_batch is None:
-        groups_per_batch = max(1, min(G, 65535, (1 << 26) // (tiles * ncols)))   # workspace <= 512 MB
-        # whole field points per batch: a field point's groups share each ray's generation and first surface
-        # (the kernel's bundle rows), so batches do not split them
-        if groups_per_batch >= nw:
-            groups_per_batch -= groups_per_batch % nw
     vec = [np.ascontiguousarray(np.asarray(v, dtype=np.float64).ravel()) for v in (c, enx, eny)]
-    # one contiguous range of groups per device -- whole field points when there are enough of them (see
-    # groups_per_batch); per device: workspace, statistics, its current stream
-    if nf >= len(devs):
-        bounds = [(f0 * nw, f1 * nw) for f0, f1 in shard_bounds(nf, len(devs))]
-    else:
-        bounds = shard_bounds(G, len(devs))
-    work = []
+    groups_per_batch, bounds, launches = _sweep_plan(nf, nw, per, len(devs), groups_per_batch, mode.ncols)
+    work = []          # per device: its groups, the mode's outputs and argument tail, an event pair, its stream
     for (g0, g1), dev in zip(bounds, devs):
-        ws = torch.empty(groups_per_batch * tiles * ncols, dtype=torch.float64, device=dev)
-        stats = torch.empty((max(g1 - g0, 1), ncols), dtype=torch.float64, device=dev)
+        outputs, tail = mode.shard(dev, per, g0, max(g1 - g0, 1), groups_per_batch)
         ev = (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
-        work.append((dev, g0, g1, ws, stats, ev, torch.cuda.current_stream(dev)))
+        work.append((dev, g1 - g0, outputs, tail, ev, torch.cuda.current_stream(dev)))
     for dev in devs:
         torch.cuda.synchronize(dev)
     t0 = time.perf_counter()
-    sweep = getattr(C.lib(), entry)
+    sweep = getattr(C.lib(), mode.entry)
     with E.plan_ref(low) as plan:
-        for dev, g0, g1, ws, stats, ev, st in work:
+        for *_, ev, st in work:
             ev[0].record(st)
-        # batches issued round-robin over the devices: every launch is asynchronous, so they run concurrently
-        nb = max(-(-(g1 - g0) // groups_per_batch) for _, g0, g1, *_ in work)
-        for k in range(nb):
-            for dev, g0, g1, ws, stats, ev, st in work:
-                b0 = g0 + k * groups_per_batch
-                b1 = min(g1, b0 + groups_per_batch)
-                if b0 >= b1:
-                    continue
-                gp = np.ascontiguousarray(params[b0:b1])
-                C.check(sweep(plan, dev.index or 0, b1 - b0, gp.ctypes.data, int(n_thetas), int(nphis),
-                              vec[0].ctypes.data, vec[1].ctypes.data, vec[2].ctypes.data, tcs.ctypes.data,
-                              pcs.ctypes.data, ws.data_ptr(), ws.numel(), stats[b0 - g0:b1 - g0].data_ptr(),
-                              st.cuda_stream))
-        for dev, g0, g1, ws, stats, ev, st in work:
+        for slot, b0, b1 in launches:
+            dev, _, _, tail, _, st = work[slot]
+            gp = np.ascontiguousarray(params[b0:b1])
+            C.check(sweep(plan, dev.index or 0, b1 - b0, gp.ctypes.data, int(n_thetas), int(nphis),
+                          vec[0].ctypes.data, vec[1].ctypes.data, vec[2].ctypes.data, tcs.ctypes.data,
+                          pcs.ctypes.data, *tail(b0, b1), st.cuda_stream))
+        for *_, ev, st in work:
             ev[1].record(st)
-        raw = np.concatenate([stats[:g1 - g0].cpu().numpy() for _, g0, g1, _, stats, _, _ in work])
+        shards = [[t[:n] for t in outputs] for _, n, outputs, *_ in work]
+        arrays = [np.concatenate([t.cpu().numpy() for t in ts]) for ts in zip(*shards)]
     dt = time.perf_counter() - t0
     per_dev = []
-    for dev, g0, g1, ws, stats, ev, st in work:
-        ms = ev[0].elapsed_time(ev[1])
-        # HBM bytes of the fused sweep: the per-tile partial sums written and read back (the rays never
-        # leave the registers)
-        nbytes = (g1 - g0) * tiles * ncols * 8 * 2 + (g1 - g0) * ncols * 8
-        per_dev.append({"device": dev.index or 0, "groups": g1 - g0, "rays": (g1 - g0) * per, "kernel_ms": ms,
-                        "ray_surface_per_s": (g1 - g0) * per * S / (ms * 1e-3) if ms > 0 else None,
+    for dev, n, _, _, ev, _ in work:
+        ms, nbytes = ev[0].elapsed_time(ev[1]), mode.hbm_bytes(per, n)
+        per_dev.append({"device": dev.index or 0, "groups": n, "rays": n * per, "kernel_ms": ms,
+                        "ray_surface_per_s": n * per * S / (ms * 1e-3) if ms > 0 else None,
                         "hbm_bytes": nbytes, "hbm_GBps": nbytes / (ms * 1e-3) / 1e9 if ms > 0 else None})
-    summ = summary(raw.reshape(nf, nw, ncols))
-    return summ, {"seconds": dt, "rays": G * per, "ray_surface_per_s": G * per * S / dt, "per_device": per_dev}
+    return arrays, dt, {"per_device": per_dev}
 
 
 def _bins(bins):
@@ -400,134 +448,46 @@ def image_sweep(system, initial_material, final_material, field_points, waveleng
     count for the spot statistics but fall outside the window -- and ``count`` = image.sum + outside, both
     (n_fields, n_wavelengths) int64, ``windows``, and ``x_edges`` (..., nx + 1) / ``y_edges`` (..., ny + 1), the bin
     edges lo + i / scale; the timing dict has :func:`spot_sweep`'s shape and covers the image pass alone."""
-    import torch
     nx, ny = _bins(bins)
-    fp = np.atleast_2d(np.asarray(field_points, dtype=float))
-    wl = np.atleast_1d(np.asarray(wavelengths, dtype=float))
-    nf, nw = fp.shape[0], wl.size
     if windows is None:
         spot, _ = spot_sweep(system, initial_material, final_material, field_points, wavelengths, theta_max,
                              n_thetas, nphis, center_ray=center_ray, device=device, dtype=dtype,
                              groups_per_batch=groups_per_batch, fused=fused, devices=devices)
         windows = auto_image_windows(spot, (nx, ny), sigmas)
     windows = np.ascontiguousarray(windows, dtype=np.float64)
-    if windows.shape != (nf, nw, 4):
+    field_points, wavelengths = _grid(field_points, wavelengths)
+    if windows.shape != (field_points.shape[0], wavelengths.size, 4):
         raise ValueError("windows must have shape (n_fields, n_wavelengths, 4)")
-    if np.linalg.norm(np.asarray(center_ray, dtype=float)) != 1:
-        raise ValueError("center_ray must be a unit vector")
-    if devices is not None and not fused:
-        raise ValueError("devices= needs the fused sweep")
-    dev = torch.device(device)
-    tdt = torch.float64 if dtype in ("float64", np.float64) else torch.float32
-    code = C.RTPB_F64 if tdt == torch.float64 else C.RTPB_F32
-    mats = [initial_material] + list(system.materials) + [final_material]
-    keys = wl if tdt == torch.float64 else wl.astype(np.float32).astype(np.float64)    # (as _sweep lowers them)
-    low = E.lower(system.surfaces, mats, lambda: np.unique(keys), code)
-    S = len(system.surfaces)
-    G, per = nf * nw, n_thetas * nphis
-    win = windows.reshape(G, 4)
-    if fused:
-        devs = [dev] if devices is None else [torch.device("cuda", int(d)) for d in devices]
-        image, outside, timing = _image_sweep_fused(low, S, fp, wl, theta_max, n_thetas, nphis, center_ray, devs,
-                                                    groups_per_batch, win, nx, ny)
-    else:
-        if groups_per_batch is None:
-            groups_per_batch = max(1, min(G, (1 << 27) // per))     # ~128M rays in flight
-        sel = E.resolve_planes("final", S)
-        rays = torch.empty((groups_per_batch * per, 8), dtype=tdt, device=dev)
-        out = torch.empty((1, groups_per_batch * per, 8), dtype=tdt, device=dev)
-        image = np.zeros((G, ny, nx), dtype=np.int32)
-        outside = np.zeros(G, dtype=np.int32)
-        torch.cuda.synchronize(dev)
-        t0 = time.perf_counter()
-        for b0 in range(0, G, groups_per_batch):
-            nb = min(groups_per_batch, G - b0)
-            for k in range(nb):                      # generate each fan in place in the batch buffer
-                _fan_into(rays[k * per:(k + 1) * per], fp[(b0 + k) // nw], theta_max, n_thetas, wl[(b0 + k) % nw],
-                          nphis, center_ray, code)
-            m = nb * per
-            E.trace_device(low, rays[:m], sel, out=out[:, :m])
-            im, outs = spot_image_raw(out[0, :m], per, win[b0:b0 + nb], (nx, ny))
-            image[b0:b0 + nb], outside[b0:b0 + nb] = im.cpu().numpy(), outs.cpu().numpy()
-        torch.cuda.synchronize(dev)
-        dt = time.perf_counter() - t0
-        timing = {"seconds": dt, "rays": G * per, "ray_surface_per_s": G * per * S / dt}
-    image = image.reshape(nf, nw, ny, nx)
-    outside = outside.reshape(nf, nw).astype(np.int64)
-    xe, ye = image_edges(windows, (nx, ny))
-    return {"image": image, "outside": outside, "count": image.sum(axis=(-2, -1), dtype=np.int64) + outside,
-            "windows": windows, "x_edges": xe, "y_edges": ye}, timing
+    return _sweep(_image_mode(windows, nx, ny), system, initial_material, final_material, field_points, wavelengths,
+                  theta_max, n_thetas, nphis, center_ray, device, dtype, groups_per_batch, fused, devices)
 
 
-def _image_sweep_fused(low, S, field_points, wavelengths, theta_max, n_thetas, nphis, center_ray, devs,
-                       groups_per_batch, win, nx, ny):
-    """The fused image sweep over the devices: :func:`_spot_sweep_fused`'s group order, sharding and batches, with
-    ``rtpb_image_sweep`` and per device the images in place of the workspace and statistics."""
-    import torch
-    from .raytrace import _fan_tables, shard_bounds
-    c = np.array(center_ray)
-    enx, eny, tcs, pcs = _fan_tables(float(theta_max), int(n_thetas), int(nphis), tuple(c.tolist()), c.dtype.str)
-    nf, nw = field_points.shape[0], wavelengths.size
-    params = np.empty((nf * nw, 4))
-    params[:, 0:3] = np.repeat(field_points, nw, axis=0)          # group = field * nw + wavelength
-    params[:, 3] = np.tile(wavelengths, nf)
-    G = params.shape[0]
-    per = n_thetas * nphis
-    if groups_per_batch is None:
-        groups_per_batch = max(1, min(G, 65535))
-        if groups_per_batch >= nw:                                # whole field points per batch (bundle rows)
-            groups_per_batch -= groups_per_batch % nw
-    vec = [np.ascontiguousarray(np.asarray(v, dtype=np.float64).ravel()) for v in (c, enx, eny)]
-    if nf >= len(devs):
-        bounds = [(f0 * nw, f1 * nw) for f0, f1 in shard_bounds(nf, len(devs))]
-    else:
-        bounds = shard_bounds(G, len(devs))
-    work = []
-    for (g0, g1), dev in zip(bounds, devs):
-        image = torch.empty((max(g1 - g0, 1), ny, nx), dtype=torch.int32, device=dev)
-        outside = torch.empty((max(g1 - g0, 1),), dtype=torch.int32, device=dev)
-        ev = (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
-        work.append((dev, g0, g1, image, outside, ev, torch.cuda.current_stream(dev)))
-    for dev in devs:
-        torch.cuda.synchronize(dev)
-    t0 = time.perf_counter()
-    sweep = C.lib().rtpb_image_sweep
-    with E.plan_ref(low) as plan:
-        for dev, g0, g1, image, outside, ev, st in work:
-            ev[0].record(st)
-        nb = max(-(-(g1 - g0) // groups_per_batch) for _, g0, g1, *_ in work)
-        for k in range(nb):                                       # round-robin over the devices, all asynchronous
-            for dev, g0, g1, image, outside, ev, st in work:
-                b0 = g0 + k * groups_per_batch
-                b1 = min(g1, b0 + groups_per_batch)
-                if b0 >= b1:
-                    continue
-                gp = np.ascontiguousarray(params[b0:b1])
-                wn = np.ascontiguousarray(win[b0:b1])
-                C.check(sweep(plan, dev.index or 0, b1 - b0, gp.ctypes.data, int(n_thetas), int(nphis),
-                              vec[0].ctypes.data, vec[1].ctypes.data, vec[2].ctypes.data, tcs.ctypes.data,
-                              pcs.ctypes.data, wn.ctypes.data, nx, ny, image[b0 - g0:b1 - g0].data_ptr(),
-                              outside[b0 - g0:b1 - g0].data_ptr(), st.cuda_stream))
-        for dev, g0, g1, image, outside, ev, st in work:
-            ev[1].record(st)
-        images = np.concatenate([image[:g1 - g0].cpu().numpy() for _, g0, g1, image, *_ in work])
-        outs = np.concatenate([outside[:g1 - g0].cpu().numpy() for _, g0, g1, _, outside, *_ in work])
-    dt = time.perf_counter() - t0
-    per_dev = []
-    for dev, g0, g1, image, outside, ev, st in work:
-        ms = ev[0].elapsed_time(ev[1])
-        # HBM bytes of the fused sweep: the counters, cleared and then added to (the rays never leave the registers)
-        nbytes = (g1 - g0) * (ny * nx + 1) * 4 * 2
-        per_dev.append({"device": dev.index or 0, "groups": g1 - g0, "rays": (g1 - g0) * per, "kernel_ms": ms,
-                        "ray_surface_per_s": (g1 - g0) * per * S / (ms * 1e-3) if ms > 0 else None,
-                        "hbm_bytes": nbytes, "hbm_GBps": nbytes / (ms * 1e-3) / 1e9 if ms > 0 else None})
-    return images, outs, {"seconds": dt, "rays": G * per, "ray_surface_per_s": G * per * S / dt,
-                          "per_device": per_dev}
+def _image_mode(windows, nx, ny):
+    """The image sweep as the drivers see it (:func:`_stats_mode`): ``rtpb_image_sweep`` fused, ``spot_image_raw``
+    per plane, no workspace; per device the shard's images and outside counts.  ``windows`` is C-contiguous
+    (n_fields, n_wavelengths, 4) float64, so the windows of groups [b0, b1) are contiguous in it."""
+    win = windows.reshape(-1, 4)
 
+    def shard(dev, per, g0, n, batch):
+        import torch
+        image = torch.empty((n, ny, nx), dtype=torch.int32, device=dev)
+        outside = torch.empty((n,), dtype=torch.int32, device=dev)
+        return (image, outside), lambda b0, b1: (win[b0:b1].ctypes.data, nx, ny, image[b0 - g0:b1 - g0].data_ptr(),
+                                                 outside[b0 - g0:b1 - g0].data_ptr())
 
-def _fan_into(buf, pt, theta_max, n_thetas, wavelength, nphis, center_ray, code):
-    from .raytrace import fan_into
-    fan_into(buf, pt, theta_max, n_thetas, wavelength, nphis, center_ray)
+    def finish(nf, nw, image, outside):
+        image = image.reshape(nf, nw, ny, nx)
+        outside = outside.reshape(nf, nw).astype(np.int64)
+        xe, ye = image_edges(windows, (nx, ny))
+        return {"image": image, "outside": outside, "count": image.sum(axis=(-2, -1), dtype=np.int64) + outside,
+                "windows": windows, "x_edges": xe, "y_edges": ye}
+
+    return SimpleNamespace(
+        entry="rtpb_image_sweep", ncols=None, shard=shard, finish=finish,
+        # the counters, cleared and then added to (the rays never leave the registers)
+        hbm_bytes=lambda per, n: n * (ny * nx + 1) * 4 * 2,
+        host=lambda G: (np.zeros((G, ny, nx), dtype=np.int32), np.zeros(G, dtype=np.int32)),
+        plane=lambda out, per, b0, nb: spot_image_raw(out, per, win[b0:b0 + nb], (nx, ny)))
 
 
 class GridInterpolator:

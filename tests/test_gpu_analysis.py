@@ -319,6 +319,37 @@ def test_spot_sweep_over_devices_is_bitwise_equal():
         assert all(p["kernel_ms"] > 0 for p in tm["per_device"])
 
 
+def test_sweeps_split_a_field_point_over_devices_and_leave_a_device_empty():
+    """The two sharding paths of the fused sweeps that need fewer field points than devices, for all three modes, with
+    one device's result as the reference: 2 field points x 5 wavelengths on three shards (ranges of 3, 3 and 4
+    groups, so the groups of each field point are split; batches of 2 leave ragged ones), and 1 x 1 on two shards
+    (the first is empty: no launch, no rows).  The per-device records carry the planner's ranges and the seven keys."""
+    import sweep_cases
+    c = sweep_cases.case("astig_relay")
+    keys = {"device", "groups", "rays", "kernel_ms", "ray_surface_per_s", "hbm_bytes", "hbm_GBps"}
+    for fields, wls, devs, gpb in ((c.fields, c.wls, [0, 0, 0], 2), (c.fields[:1], c.wls[:1], [0, 0], None)):
+        args = (c.system, c.m0, c.m1, fields, wls, c.theta, c.nt, c.nph)
+        kw = dict(center_ray=c.center_ray, device=DEV)
+        spot, _ = analysis.spot_sweep(*args, **kw)
+        windows = analysis.auto_image_windows(spot, (16, 12))
+        runs = {"spot": (analysis.spot_sweep, {}), "focus": (analysis.focus_sweep, dict(require_image_plane=False)),
+                "image": (analysis.image_sweep, dict(bins=(16, 12), windows=windows))}
+        _, bounds, _ = analysis._sweep_plan(len(fields), len(wls), c.nt * c.nph, len(devs), gpb, None)
+        assert bounds == ([(0, 3), (3, 6), (6, 10)] if len(devs) == 3 else [(0, 0), (0, 1)])
+        for name, (run, more) in runs.items():
+            one, t1 = run(*args, **kw, **more)
+            many, tm = run(*args, **kw, **more, devices=devs, groups_per_batch=gpb)
+            assert one.keys() == many.keys()
+            for k in one:
+                assert one[k].dtype == many[k].dtype and one[k].shape == many[k].shape, (name, k)
+                assert np.array_equal(one[k], many[k], equal_nan=one[k].dtype.kind == "f"), (name, devs, k)
+            assert [p["groups"] for p in tm["per_device"]] == [g1 - g0 for g0, g1 in bounds], name
+            assert [p["device"] for p in tm["per_device"]] == devs
+            assert sum(p["rays"] for p in tm["per_device"]) == t1["rays"] == tm["rays"]
+            assert all(set(p) == keys for p in tm["per_device"] + t1["per_device"]), name
+        assert spot["count"].sum() > 0
+
+
 def test_spot_sweep_group_order_does_not_matter():
     """rtpb_spot_sweep gathers the groups of one field point into bundle rows whatever their order: fields and
     wavelengths given in another order (groups interleaved differently in one batch) give the same statistics,
