@@ -320,7 +320,10 @@ int rtpb_collimated_rays_tables_wl(int32_t device, int32_t dtype, void* rays_out
 /* propagate_ray2plane(rays, normal, center, material, exclude_backward_propagation) (RT:241-306) on
    device rays (AOS n x 8).  normal / center: DEVICE pointers to 3 doubles (broadcast) or n x 3 doubles
    (*_per_ray = 1).  ts_out (device, n doubles) may be NULL.  workspace: device bytes for the material
-   descriptor (>= 256 + 16 * max(table_len, 1)); the call synchronises `stream` after staging it. */
+   descriptor (>= 256 + 16 * max(table_len, 1)); the call synchronises `stream` after staging it.
+   rays_in and rays_out must be 16-byte aligned (RTPB_E_INVALID otherwise).  A TABLE material's pairs may
+   come in any order (the call sorts its copy); a SELLMEIER material with all-zero coefficients is Vacuum.
+   n_rays == 0 returns RTPB_OK without reading the ray buffers, ts_out or the workspace (all may be NULL). */
 int rtpb_propagate_plane(int32_t device, int32_t dtype, const void* rays_in, int64_t n_rays, const double* normal,
                          int32_t normal_per_ray, const double* center, int32_t center_per_ray,
                          const rtpb_material* material, int32_t exclude_backward, void* rays_out, double* ts_out,
@@ -332,7 +335,9 @@ int rtpb_propagate_plane(int32_t device, int32_t dtype, const void* rays_in, int
    is_pt_on_surface.  The caller evaluates those three hooks; the library does the rest of propagate
    on the device.  `plan` holds ONE surface (only its input_axis is read) and TWO materials (the
    media before / after the surface); buffers are device pointers in the plan's storage type, rays
-   AOS n x 8, normals n x 3.
+   AOS n x 8, normals n x 3.  The n x 8 buffers (rays, hits, hits_out, out) must be 16-byte aligned
+   (RTPB_E_INVALID otherwise); normals and on_surface need only their element alignment.  n == 0 returns
+   RTPB_OK without reading any buffer (all may be NULL).
    rtpb_front_side: hits_out = hits with every row NaN where rays.d . input_axis < 0 (RT:1184-1192);
      hits_out may equal hits.
    rtpb_interact: out = Snell refraction (mode RTPB_REFRACT, n1/n2 from the plan's materials at the
