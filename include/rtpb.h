@@ -55,8 +55,9 @@ extern "C" {
                                    next allocation that maps new memory, or by rtpb_buffer_trim)
                                 9: + rtpb_trace_packed (rtpb_trace_checked's arguments in one struct)
                                 10: + rtpb_focus_stats / rtpb_focus_sweep (through-focus statistics);
-                                    rtpb_spot_image / rtpb_image_sweep (spot images) joined within 10: new
-                                    symbols only, nothing existing changed */
+                                    rtpb_spot_image / rtpb_image_sweep (spot images) and
+                                    rtpb_wavefront_stats / rtpb_wavefront_sweep (wavefront statistics) joined
+                                    within 10: new symbols only, nothing existing changed */
 
 /* ---- error codes ---------------------------------------------------------------------------- */
 #define RTPB_OK 0
@@ -426,6 +427,42 @@ int rtpb_image_sweep(const rtpb_plan* plan, int32_t device, int64_t n_groups, co
                      const double ey[3], const double* theta_cos_sin, const double* phi_cos_sin,
                      const double* windows, int32_t nx, int32_t ny, int32_t* image_out, int32_t* outside_out,
                      void* stream);
+
+/* Wavefront statistics: per group, the moments of the optical path difference (OPD) from which the RMS wavefront
+   error, the diffraction focus and the Marechal Strehl estimate follow on the host.  A group's REFERENCE is eight
+   doubles {C0x, C0y, C0z, d0x, d0y, d0z, p0, kf}: the reference point C0, a pivot direction d0 and a pivot phase p0
+   in radians (the group's chief ray), and kf = n_final(wavelength) / wavelength, evaluated by the caller.  The
+   optical path of a ray to the foot of the perpendicular from C0 is linear in C0, so the variance of the OPD about
+   C0 + delta is an exact quadratic in delta, and its coefficients are the moments summed here.  The pivots are
+   subtracted per ray before anything is squared (un-pivoted sums of a 3e4 rad phase cancel to a few per cent).
+   float64 ONLY: a float32 phase of 1e4 ... 1e7 rad has an ulp of a milliradian to a radian, so a float32 dtype or
+   plan is RTPB_E_INVALID.  For a ray's final state (x, y, z, dx, dy, dz, ph), every operation one rounded IEEE
+   operation in this order, no FMA:
+       ex = dx - d0x;  ey = dy - d0y;  ez = dz - d0z
+       s  = ((C0x - x) * dx + (C0y - y) * dy) + (C0z - z) * dz
+       w  = (ph - p0) * 0.15915494309189535 + s * kf              (the OPD in waves; the constant is 1 / (2 pi))
+   A ray COUNTS when rtpb_spot_stats counts it (x and y finite) and w, ex, ey and ez are all finite; a ray that does
+   not count adds +0 to every sum.  A NaN in a group's reference makes every w NaN: the group counts 0.
+   stats_out (device, n_groups x 15 doubles): count, sum w, w^2, ex, ey, ez, w*ex, w*ey, w*ez, ex^2, ey^2, ez^2,
+   ex*ey, ex*ez, ey*ez, each product one rounded multiply; the fixed-order two-pass reduction of rtpb_spot_stats
+   (a tree per 256-ray tile, then the tiles in a fixed order).  refs: HOST, n_groups x 8, uploaded on `stream`.
+   workspace: device doubles, >= n_groups * ceil(group_size / 256) * 15.  The arguments are checked before the
+   device is.
+   rtpb_wavefront_stats: one (N, 8) AOS float64 plane split into groups as for rtpb_spot_stats. */
+int rtpb_wavefront_stats(int32_t device, int32_t dtype, const void* plane, int64_t group_size, int64_t n_groups,
+                         const double* refs, double* workspace, int64_t workspace_len, double* stats_out,
+                         void* stream);
+
+/* Fused wavefront sweep: rtpb_focus_sweep's arguments with refs (HOST, n_groups x 8; it rides in the sweep's one
+   upload) before the workspace, and its group and tile limits.  The surface steps are rtpb_trace's own (the phase
+   is kept), every group is swept on its own, and the statistics are bit-identical to rtpb_ray_fan_tables +
+   rtpb_trace (final plane) + rtpb_wavefront_stats.  workspace: device doubles,
+   >= n_groups * ceil(n_thetas*nphis / 256) * 15.  stats_out: device, n_groups x 15.  float64 plans only. */
+int rtpb_wavefront_sweep(const rtpb_plan* plan, int32_t device, int64_t n_groups, const double* group_params,
+                         int64_t n_thetas, int64_t nphis, const double center_ray[3], const double ex[3],
+                         const double ey[3], const double* theta_cos_sin, const double* phi_cos_sin,
+                         const double* refs, double* workspace, int64_t workspace_len, double* stats_out,
+                         void* stream);
 
 /* ---- pupil-phase interpolation (scripts/2022_02_06_perfect_imaging_system_psf.py:90-105) */
 /* A 2-D Delaunay triangulation with one value per vertex, in scipy.spatial.Delaunay's representation,

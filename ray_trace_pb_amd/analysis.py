@@ -4,7 +4,8 @@ group and a chunked spot-diagram sweep that never leaves HBM (BASELINE configs[4
 The reference computes spot diagrams in user scripts with NumPy on the full host history; here the
 fans are generated on the GPU (``rtpb_ray_fan_tables``), traced with only the final plane stored, and reduced
 on the GPU with a deterministic fixed-order reduction (``rtpb_spot_stats``) -- or binned into per-group spot
-images of integer counts (``rtpb_spot_image``, :func:`image_sweep`).
+images of integer counts (``rtpb_spot_image``, :func:`image_sweep`), or reduced to the moments of the optical path
+difference (``rtpb_wavefront_stats``, :func:`wavefront_sweep`: RMS wavefront error, diffraction focus, Strehl).
 """
 import time
 from types import SimpleNamespace
@@ -18,6 +19,14 @@ STAT_NAMES = ("count", "sum_x", "sum_y", "sum_z", "sum_xx", "sum_yy", "sum_xy")
 # the spot sums, then the moments of the slopes u = dx/dz, v = dy/dz (rtpb_focus_stats / rtpb_focus_sweep)
 FOCUS_STAT_NAMES = STAT_NAMES + ("sum_u", "sum_v", "sum_uu", "sum_vv", "sum_uv", "sum_xu", "sum_yv", "sum_xv",
                                  "sum_yu")
+# the moments of the OPD w (waves) and of e = d - d0 (rtpb_wavefront_stats / rtpb_wavefront_sweep)
+WAVE_STAT_NAMES = ("count", "sum_w", "sum_ww", "sum_ex", "sum_ey", "sum_ez", "sum_wex", "sum_wey", "sum_wez",
+                   "sum_exex", "sum_eyey", "sum_ezez", "sum_exey", "sum_exez", "sum_eyez")
+# summarize_wavefront: singular values of cov_ee below WAVE_RCOND times the largest are treated as zero.  cov_ee is
+# formed from sums of pivoted directions, |e| <= the bundle's angular size, so its entries carry rounding errors of
+# about 1e-16 of its largest eigenvalue; the smallest eigenvalue of a focused bundle of numerical aperture s is about
+# s^2 of the largest (1e-5 at s = 0.003).  1e-10 lies between the two.
+WAVE_RCOND = 1e-10
 
 
 def _plane_stats_raw(entry, ncols, plane, group_size, stream):
@@ -116,6 +125,110 @@ def rms_radius_at(summary, dz):
         return np.sqrt(np.maximum(cov[..., 0, 0] + cov[..., 1, 1] + 2.0 * dz * A + dz * dz * B, 0.0))
 
 
+def _wave_refs(refs, shape):
+    """``refs`` as a C-contiguous float64 array of the given shape (..., 8)."""
+    refs = np.ascontiguousarray(refs, dtype=np.float64)
+    if refs.shape != tuple(shape):
+        raise ValueError("refs must have shape " + " x ".join(str(k) for k in shape))
+    return refs
+
+
+def wavefront_stats_raw(plane, group_size, refs, stream=None):
+    """Per-group wavefront sums (n_groups, 15; ``WAVE_STAT_NAMES``) of a torch CUDA (N, 8) float64 plane against
+    ``refs`` (n_groups, 8) = (C0, d0, p0, kf) per group, host values (:func:`wavefront_refs`).  Per ray
+    e = d - d0 and the OPD in waves w = (phase - p0) / (2 pi) + kf (C0 - r) . d; a ray counts when x, y, w and e are
+    finite.  float64 only: a float32 phase of 1e4 ... 1e7 rad is noise at the scale of a wave, so a float32 plane
+    raises ``ValueError``."""
+    import torch
+    if plane.dtype != torch.float64:
+        raise ValueError("wavefront statistics need a float64 plane: a float32 phase of 1e4 ... 1e7 rad has an ulp of "
+                         "a milliradian to a radian")
+    n = plane.shape[0]
+    if n % group_size:
+        raise ValueError("plane length must be a multiple of group_size")
+    ngroups = n // group_size
+    refs = _wave_refs(refs, (ngroups, 8))
+    plane = plane.contiguous()
+    tiles = -(-group_size // 256)
+    ws = torch.empty(ngroups * tiles * 15, dtype=torch.float64, device=plane.device)
+    stats = torch.empty((ngroups, 15), dtype=torch.float64, device=plane.device)
+    if stream is None:
+        stream = torch.cuda.current_stream(plane.device).cuda_stream
+    C.check(C.lib().rtpb_wavefront_stats(plane.device.index or 0, C.RTPB_F64, plane.data_ptr(), group_size, ngroups,
+                                         refs.ctypes.data, ws.data_ptr(), ws.numel(), stats.data_ptr(), stream))
+    return stats
+
+
+def _wave_var(var, cov_we, cov_ee, kf, delta):
+    """Var(w + kf delta . e) from the moments: the OPD variance about the reference displaced by ``delta``."""
+    return (var + 2.0 * kf * np.einsum("...i,...i->...", delta, cov_we)
+            + kf * kf * np.einsum("...i,...ij,...j->...", delta, cov_ee, delta))
+
+
+def summarize_wavefront(raw, refs):
+    """Wavefront summary from the 15 raw sums (``WAVE_STAT_NAMES``) and the references they were taken against
+    (..., 8) = (C0, d0, p0, kf); host, NumPy.
+
+    The optical path of a ray to the foot of the perpendicular from a point C is linear in C: moving the reference
+    from C0 to C0 + delta adds kf delta . d to the ray's OPD w (in waves), and delta . d0 is the same for every ray,
+    so with e = d - d0 the OPD variance about C0 + delta is Var(w) + 2 kf delta . cov_we + kf^2 delta' cov_ee delta --
+    exact for the traced bundle, no ray traced twice.  A constant of w is piston; delta across the axis removes
+    tilt, delta along it removes focus.  Returns
+
+    - ``count``, ``raw``, ``reference`` (C0) and ``kf``;
+    - ``mean_opd`` and ``rms_opd``, the mean and standard deviation of w about C0 in waves, and
+      ``strehl`` = exp(-(2 pi rms_opd)^2), the Marechal estimate;
+    - ``mean_e`` (..., 3), ``cov_we`` (..., 3) and ``cov_ee`` (..., 3, 3), each entry S_ab / n - mean_a * mean_b;
+    - ``shift`` (..., 3) = -pinv(cov_ee) cov_we / kf, the displacement of the reference that minimises the variance,
+      the pseudo-inverse dropping singular values below ``WAVE_RCOND`` times the largest: a collimated output has
+      a rank-deficient cov_ee, and the components of the shift it does not constrain are 0;
+    - ``reference_best`` = C0 + shift, the diffraction focus (for a system with spherical aberration it is not
+      the least-squares spot focus of :func:`summarize_focus`);
+    - ``rms_opd_best`` and ``strehl_best``, the figures about it: piston, tilt and focus removed.
+
+    Groups without rays (a NaN reference counts none) give NaN."""
+    raw = np.asarray(raw, dtype=np.float64)
+    refs = _wave_refs(refs, raw.shape[:-1] + (8,))
+    n = raw[..., 0]
+    kf = refs[..., 7]
+    with np.errstate(invalid="ignore", divide="ignore"):
+        mean_w = raw[..., 1] / n
+        var = raw[..., 2] / n - mean_w * mean_w
+        mean_e = raw[..., 3:6] / n[..., None]
+        cov_we = raw[..., 6:9] / n[..., None] - mean_w[..., None] * mean_e
+        cov_ee = np.empty(raw.shape[:-1] + (3, 3))
+        for (i, j), k in zip(((0, 0), (1, 1), (2, 2), (0, 1), (0, 2), (1, 2)), range(9, 15)):
+            cov_ee[..., i, j] = cov_ee[..., j, i] = raw[..., k] / n - mean_e[..., i] * mean_e[..., j]
+        good = (n > 0) & np.isfinite(cov_ee).all(axis=(-2, -1)) & np.isfinite(cov_we).all(axis=-1) & np.isfinite(kf)
+        shift = np.full(raw.shape[:-1] + (3,), np.nan)
+        if good.any():
+            pinv = np.linalg.pinv(cov_ee[good], rcond=WAVE_RCOND, hermitian=True)
+            shift[good] = -np.einsum("...ij,...j->...i", pinv, cov_we[good]) / kf[good][..., None]
+        best = _wave_var(var, cov_we, cov_ee, kf, shift)
+        rms, rms_best = np.sqrt(np.maximum(var, 0.0)), np.sqrt(np.maximum(best, 0.0))
+        two_pi = 2.0 * np.pi
+        return {"count": n, "raw": raw, "reference": refs[..., 0:3], "kf": kf, "mean_opd": mean_w, "rms_opd": rms,
+                "strehl": np.exp(-(two_pi * rms) ** 2), "mean_e": mean_e, "cov_we": cov_we, "cov_ee": cov_ee,
+                "var_opd": var, "shift": shift, "reference_best": refs[..., 0:3] + shift, "rms_opd_best": rms_best,
+                "strehl_best": np.exp(-(two_pi * rms_best) ** 2)}
+
+
+def rms_opd_at(summary, delta):
+    """RMS OPD in waves about the reference displaced by ``delta`` (..., 3) from the point the summary
+    (:func:`summarize_wavefront`) was taken about, from the same moments; ``delta`` broadcasts over the groups.
+    ``rms_opd_at(s, s["shift"])`` is ``s["rms_opd_best"]``."""
+    delta = np.asarray(delta, dtype=np.float64)
+    with np.errstate(invalid="ignore"):
+        return np.sqrt(np.maximum(_wave_var(summary["var_opd"], summary["cov_we"], summary["cov_ee"], summary["kf"],
+                                            delta), 0.0))
+
+
+def wavefront_stats(plane, group_size, refs):
+    """Wavefront summary per contiguous group of ``group_size`` rays of a torch CUDA (N, 8) float64 plane."""
+    return summarize_wavefront(wavefront_stats_raw(plane, group_size, refs).cpu().numpy(),
+                               _wave_refs(refs, (plane.shape[0] // group_size, 8)))
+
+
 def spot_stats(plane, group_size):
     """Spot summary per contiguous group of ``group_size`` rays of a torch CUDA (N, 8) plane."""
     return summarize(spot_stats_raw(plane, group_size).cpu().numpy())
@@ -202,6 +315,82 @@ def focus_sweep(system, initial_material, final_material, field_points, waveleng
                          "require_image_plane=False for the raw moments on the last surface")
     return _sweep(_FOCUS, system, initial_material, final_material, field_points, wavelengths, theta_max, n_thetas,
                   nphis, center_ray, device, dtype, groups_per_batch, fused, devices)
+
+
+def wavefront_refs(system, initial_material, final_material, field_points, wavelengths, center_ray=(0, 0, 1),
+                   spot_summary=None, device="cuda:0", **fan_kw):
+    """The references (n_fields, n_wavelengths, 8) = (C0, d0, p0, kf) of :func:`wavefront_sweep`'s groups.
+
+    C0 is the group's spot centroid, from ``spot_summary`` (a :func:`spot_sweep` or :func:`focus_sweep` summary of
+    the same groups) or from the :func:`spot_sweep` that ``fan_kw`` (``theta_max``, ``n_thetas``, ``nphis``; also
+    ``groups_per_batch``, ``devices``) describes.  d0 and p0 are the final direction and phase of the group's chief
+    ray -- the field point along ``center_ray``, ``get_ray_fan(field, 0, 1, wavelength)`` -- traced through the
+    ordinary ``planes='final'`` path, and kf = final_material.n(wavelength) / wavelength.  A group whose chief ray
+    dies gets a reference of NaN: every ray's OPD is then NaN, the group counts 0 and its summary is NaN."""
+    import torch
+    from .raytrace import get_ray_fan
+    field_points, wavelengths = _grid(field_points, wavelengths)
+    nf, nw = field_points.shape[0], wavelengths.size
+    if spot_summary is None:
+        spot_summary, _ = spot_sweep(system, initial_material, final_material, field_points, wavelengths,
+                                     center_ray=center_ray, device=device, **fan_kw)
+    refs = np.empty((nf, nw, 8))
+    refs[..., 0:3] = np.asarray(spot_summary["centroid"], dtype=np.float64).reshape(nf, nw, 3)
+    chief = np.concatenate([get_ray_fan(f, 0.0, 1, w, center_ray=center_ray) for f in field_points
+                            for w in wavelengths])
+    fin = system.ray_trace(torch.from_numpy(chief).to(torch.device(device)), initial_material, final_material,
+                           planes="final")[-1].cpu().numpy().reshape(nf, nw, 8)
+    refs[..., 3:7] = fin[..., 3:7]
+    refs[..., 7] = [float(final_material.n(w)) / w for w in wavelengths]
+    refs[~np.isfinite(fin[..., :7]).all(axis=-1)] = np.nan
+    return refs
+
+
+def _wave_mode(refs):
+    """The wavefront sweep as the drivers see it (:func:`_stats_mode`, with the groups' references as
+    :func:`_image_mode` carries the windows): ``refs`` is C-contiguous (n_fields, n_wavelengths, 8) float64, so
+    the references of groups [b0, b1) are contiguous in it."""
+    ref = refs.reshape(-1, 8)
+    base = _stats_mode("rtpb_wavefront_sweep", None, 15, None)
+    stats_shard = base.shard
+
+    def shard(dev, per, g0, n, batch):
+        outputs, tail = stats_shard(dev, per, g0, n, batch)
+        return outputs, lambda b0, b1: (ref[b0:b1].ctypes.data,) + tail(b0, b1)
+
+    base.shard = shard
+    base.plane = lambda out, per, b0, nb: (wavefront_stats_raw(out, per, ref[b0:b0 + nb]),)
+    base.finish = lambda nf, nw, raw: summarize_wavefront(raw.reshape(nf, nw, 15), refs)
+    return base
+
+
+def wavefront_sweep(system, initial_material, final_material, field_points, wavelengths, theta_max, n_thetas,
+                    nphis=1, center_ray=(0, 0, 1), device="cuda:0", refs=None, groups_per_batch=None, fused=True,
+                    devices=None, dtype="float64"):
+    """Wavefront analysis for every (field point, wavelength): :func:`spot_sweep`'s fans, with the 15 moments of
+    the optical path difference taken from each ray's final position, direction and phase in the same pass
+    (``rtpb_wavefront_sweep``: the trace kernel's own surface steps, so the phase is the one ``ray_trace`` stores;
+    with ``fused=False`` fan generation -> trace planes='final' -> ``rtpb_wavefront_stats``; bit-identical).
+
+    ``refs`` (n_fields, n_wavelengths, 8) says what each group's OPD is measured against; with ``refs=None``
+    :func:`wavefront_refs` builds them from a :func:`spot_sweep` of the same fans and one chief ray per group, so the
+    rays are traced twice.  Returns (:func:`summarize_wavefront` summary with arrays shaped (n_fields,
+    n_wavelengths, ...), timing dict as :func:`spot_sweep`'s, covering the wavefront pass alone): RMS wavefront
+    error in waves and the Strehl estimate about the reference and about the diffraction focus, which
+    ``reference_best`` locates; :func:`rms_opd_at` gives the figure about any other point.
+
+    float64 only (``dtype`` is there to say so: anything else raises ``ValueError``)."""
+    if dtype not in ("float64", np.float64):
+        raise ValueError("wavefront_sweep is float64 only: a float32 phase of 1e4 ... 1e7 rad has an ulp of a "
+                         "milliradian to a radian")
+    field_points, wavelengths = _grid(field_points, wavelengths)
+    if refs is None:
+        refs = wavefront_refs(system, initial_material, final_material, field_points, wavelengths,
+                              center_ray=center_ray, device=device, theta_max=theta_max, n_thetas=n_thetas,
+                              nphis=nphis, groups_per_batch=groups_per_batch, devices=devices)
+    refs = _wave_refs(refs, (field_points.shape[0], wavelengths.size, 8))
+    return _sweep(_wave_mode(refs), system, initial_material, final_material, field_points, wavelengths, theta_max,
+                  n_thetas, nphis, center_ray, device, "float64", groups_per_batch, fused, devices)
 
 
 def _grid(field_points, wavelengths):

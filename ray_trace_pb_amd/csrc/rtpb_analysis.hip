@@ -1,8 +1,9 @@
 // rtpb_analysis.hip -- device analysis around the trace: intersect_rays
-// (RT:164-238), the per-group spot and focus statistics of a plane, and griddata-style interpolation of pupil phases onto a grid.
+// (RT:164-238), the per-group spot, focus and wavefront statistics of a plane, and griddata-style interpolation of pupil phases onto a grid.
 #include "rtpb_stats.h"
 
 #include <algorithm>
+#include <cstring>
 
 using namespace rtpbi;
 
@@ -96,7 +97,42 @@ __global__ __launch_bounds__(kBlock) void focus_partial_kernel(SpotArgs a) {
     }
 }
 
-// NS statistics per group (kStats or kFocusStats): thread t adds tiles t, t + 256, ... in order, then one tree over
+// The wavefront statistics of an (N, 8) float64 plane (rtpb_wavefront_stats): focus_partial_kernel's structure with
+// wave_ray / wave_term and the group's reference; the fifteen statistics go in two chunks of eight, the last padded
+struct WaveArgs {
+    SpotArgs s;
+    const double* __restrict__ refs;    // per group: C0 (3), d0 (3), p0, kf
+};
+
+__global__ __launch_bounds__(kBlock) void wave_partial_kernel(WaveArgs wa) {
+    constexpr int kRows = 8;
+    __shared__ double red[kRows][kBlock];
+    const SpotArgs& a = wa.s;
+    const int64_t g = blockIdx.y, tile = blockIdx.x;
+    const int64_t j = tile * kBlock + threadIdx.x;
+    WaveRay f{0.0, 0.0, 0.0, 0.0, 0.0};
+    if (j < a.gsize) {
+        const double* r = static_cast<const double*>(a.plane) + (g * a.gsize + j) * 8;
+        const double* q = wa.refs + kWaveRef * g;
+        const double ref[kWaveRef] = {q[0], q[1], q[2], q[3], q[4], q[5], q[6], q[7]};
+        f = wave_ray(r[0], r[1], r[2], r[3], r[4], r[5], r[6], ref);
+    }
+#pragma unroll
+    for (int k0 = 0; k0 < kWaveStats; k0 += kRows) {
+        double u[kRows];
+#pragma unroll
+        for (int k = 0; k < kRows; ++k) u[k] = wave_term(f, k0 + k);
+        // (no barrier between chunks, as in focus_partial_kernel)
+        block_tree_sum<kRows>(u, red);
+        if (threadIdx.x == 0) {
+#pragma unroll
+            for (int k = 0; k < kRows; ++k)
+                if (k0 + k < kWaveStats) a.partials[(g * a.tiles + tile) * kWaveStats + k0 + k] = u[k];
+        }
+    }
+}
+
+// NS statistics per group (kStats, kFocusStats or kWaveStats): thread t adds tiles t, t + 256, ... in order, then one tree over
 // the 256 threads
 template <int NS>
 __global__ __launch_bounds__(kBlock) void spot_final_kernel(SpotArgs a) {
@@ -205,6 +241,7 @@ int rtpbi::launch_stats_final(int n_stats, double* partials, double* stats, int6
     SpotArgs a{nullptr, partials, stats, 0, n_groups, tiles};
     const dim3 grid(static_cast<unsigned>(n_groups));
     if (n_stats == kStats) hipLaunchKernelGGL(spot_final_kernel<kStats>, grid, dim3(kBlock), 0, st, a);
+    else if (n_stats == kWaveStats) hipLaunchKernelGGL(spot_final_kernel<kWaveStats>, grid, dim3(kBlock), 0, st, a);
     else hipLaunchKernelGGL(spot_final_kernel<kFocusStats>, grid, dim3(kBlock), 0, st, a);
     HIP_TRY(hipGetLastError());
     return RTPB_OK;
@@ -250,6 +287,46 @@ int rtpb_focus_stats(int32_t device, int32_t dtype, const void* plane, int64_t g
     rc = check_device(device);
     if (rc) return rc;
     return plane_stats_launch<kFocusStats>(device, dtype, plane, group_size, n_groups, workspace, stats_out, stream);
+}
+
+int rtpb_wavefront_stats(int32_t device, int32_t dtype, const void* plane, int64_t group_size, int64_t n_groups,
+                         const double* refs, double* workspace, int64_t workspace_len, double* stats_out,
+                         void* stream) {
+    // (the arguments first: a bad call is RTPB_E_INVALID / RTPB_E_LIMIT with or without a GPU)
+    if (dtype == RTPB_F32)
+        return fail(RTPB_E_INVALID, "wavefront-stats: float64 planes only (a float32 phase of 1e4 ... 1e7 rad has an "
+                                    "ulp of a milliradian to a radian: its wavefront is noise)");
+    if (dtype != RTPB_F64) return fail(RTPB_E_INVALID, "bad wavefront-stats arguments: dtype");
+    if (group_size <= 0 || n_groups <= 0 || !plane || !refs || !stats_out || !workspace)
+        return fail(RTPB_E_INVALID, "bad wavefront-stats arguments");
+    const int64_t tiles = (group_size + kBlock - 1) / kBlock;
+    if (tiles > 65535 * 16384ll || n_groups > 65535) return fail(RTPB_E_LIMIT, "wavefront-stats: too many groups");
+    if (workspace_len < n_groups * tiles * kWaveStats)
+        return fail(RTPB_E_INVALID,
+                    "wavefront-stats: workspace too small: need n_groups * ceil(group_size/256) * 15 doubles");
+    int rc = check_device(device);
+    if (rc) return rc;
+    DeviceGuard g(device);
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    // the references: one small stream-ordered upload, as the sweeps' per-group tables
+    const size_t bytes = size_t(n_groups) * kWaveRef * sizeof(double);
+    StreamScratch dref;
+    rc = dref.alloc(bytes, st);
+    if (rc) return rc;
+    PinnedStaging& pin = pinned_staging();
+    rc = pin.reserve(bytes);
+    if (rc) return rc;
+    std::memcpy(pin.buf, refs, bytes);
+    rc = pin.upload(dref.p, bytes, st);
+    if (rc) return rc;
+    const WaveArgs a{SpotArgs{plane, workspace, stats_out, group_size, n_groups, tiles},
+                     static_cast<const double*>(dref.p)};
+    hipLaunchKernelGGL(wave_partial_kernel, dim3(static_cast<unsigned>(tiles), static_cast<unsigned>(n_groups)),
+                       dim3(kBlock), 0, st, a);
+    HIP_TRY(hipGetLastError());
+    rc = launch_stats_final(kWaveStats, workspace, stats_out, n_groups, tiles, st);
+    if (rc) return rc;
+    return dref.release();
 }
 
 int rtpb_grid_interpolate(int32_t device, const rtpb_triangulation* tri, const double* xs, int64_t nx,

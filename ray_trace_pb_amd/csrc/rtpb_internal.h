@@ -448,7 +448,7 @@ struct StreamScratch {
 };
 
 // The second pass of the plane statistics and of the sweeps (spot_final_kernel, rtpb_analysis.hip): n_stats is 7
-// (spot) or 16 (focus) sums per group, from partials[n_groups][tiles][n_stats].
+// (spot), 16 (focus) or 15 (wavefront) sums per group, from partials[n_groups][tiles][n_stats].
 int launch_stats_final(int n_stats, double* partials, double* stats, int64_t n_groups, int64_t tiles, hipStream_t st);
 
 // What the two image calls share (rtpb_image.hip): the checks of the image arguments -- `call` names the call in the

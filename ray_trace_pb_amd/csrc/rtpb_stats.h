@@ -1,5 +1,6 @@
 // rtpb_stats.h -- what the plane kernels (rtpb_analysis.hip, rtpb_image.hip) and the fused sweep (rtpb_sweep.hip)
-// share: the statistics sets, the one definition of a ray's contribution to the focus statistics and to a spot image,
+// share: the statistics sets, the one definition of a ray's contribution to the focus statistics, to the wavefront
+// statistics and to a spot image,
 // the wave's aggregated image adds, the reduction's argument block and its block-wide tree.  Everything here has
 // internal linkage, as it had inside the one unit: each unit's kernels take its own SpotArgs.
 #pragma once
@@ -51,6 +52,58 @@ RTPB_HD double focus_term(const FocusRay& f, int k) {
     case 13: return f.y * f.v;
     case 14: return f.x * f.v;
     default: return f.y * f.u;
+    }
+}
+
+// Wavefront statistics (rtpb_wavefront_stats / rtpb_wavefront_sweep): the moments of the optical path difference.
+// A group's reference is kWaveRef doubles (C0x, C0y, C0z, d0x, d0y, d0z, p0, kf): the reference point, the pivot
+// direction and the pivot phase (radians) of the group's chief ray, and kf = n_final / wavelength.  The optical path
+// of a ray to the foot of the perpendicular from C0 is linear in C0, so the variance of the OPD about a displaced
+// reference C0 + delta is an exact quadratic in delta whose coefficients are the first and second moments of
+// (w, e) below (analysis.summarize_wavefront).  The pivots are subtracted per ray before anything is squared: the
+// phase is 1e4 ... 1e7 rad and the OPD a fraction of a wave, and un-pivoted sums cancel to a few per cent.
+// The one definition of a ray's contribution, for the plane kernel and the fused sweep alike, float64 only, every
+// operation one rounded IEEE operation in this order (no FMA):
+//   ex = dx - d0x, ey = dy - d0y, ez = dz - d0z
+//   s  = ((C0x - x) * dx + (C0y - y) * dy) + (C0z - z) * dz
+//   w  = (ph - p0) * kInv2Pi + s * kf                              (the OPD in waves)
+// A ray counts when x and y are finite (the spot statistics' rule) and w, ex, ey and ez are all finite.  wave_ray
+// gives the counted ray as (n, w, ex, ey, ez) with n = 1, or all +0 for a ray that does not count, and wave_term
+// its k-th statistic, each product one rounded multiply: n, w, w w, ex, ey, ez, w ex, w ey, w ez, ex ex, ey ey,
+// ez ez, ex ey, ex ez, ey ez (k past the set: +0, the padding of the last chunk of eight).
+constexpr int kWaveStats = 15;
+constexpr int kWaveRef = 8;
+constexpr double kInv2Pi = 0.15915494309189535;
+struct WaveRay {
+    double n, w, ex, ey, ez;
+};
+RTPB_HD WaveRay wave_ray(double x, double y, double z, double dx, double dy, double dz, double ph,
+                         const double (&ref)[kWaveRef]) {
+    const double ex = dx - ref[3], ey = dy - ref[4], ez = dz - ref[5];
+    const double s = ((ref[0] - x) * dx + (ref[1] - y) * dy) + (ref[2] - z) * dz;
+    const double w = (ph - ref[6]) * kInv2Pi + s * ref[7];
+    if (x - x == 0.0 && y - y == 0.0 && w - w == 0.0 && ex - ex == 0.0 && ey - ey == 0.0 && ez - ez == 0.0)
+        return WaveRay{1.0, w, ex, ey, ez};
+    return WaveRay{0.0, 0.0, 0.0, 0.0, 0.0};
+}
+RTPB_HD double wave_term(const WaveRay& f, int k) {
+    switch (k) {
+    case 0: return f.n;
+    case 1: return f.w;
+    case 2: return f.w * f.w;
+    case 3: return f.ex;
+    case 4: return f.ey;
+    case 5: return f.ez;
+    case 6: return f.w * f.ex;
+    case 7: return f.w * f.ey;
+    case 8: return f.w * f.ez;
+    case 9: return f.ex * f.ex;
+    case 10: return f.ey * f.ey;
+    case 11: return f.ez * f.ez;
+    case 12: return f.ex * f.ey;
+    case 13: return f.ex * f.ez;
+    case 14: return f.ey * f.ez;
+    default: return 0.0;
     }
 }
 

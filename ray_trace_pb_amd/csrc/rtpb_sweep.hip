@@ -1,5 +1,5 @@
-// rtpb_sweep.hip -- the fused spot-diagram / through-focus / spot-image sweep: generate + trace +
-// reduce in one kernel, rtpb_spot_sweep, rtpb_focus_sweep and rtpb_image_sweep.  What it shares with the plane
+// rtpb_sweep.hip -- the fused spot-diagram / through-focus / spot-image / wavefront sweep: generate +
+// trace + reduce in one kernel, rtpb_spot_sweep, rtpb_focus_sweep, rtpb_image_sweep and rtpb_wavefront_sweep.  What it shares with the plane
 // kernels (the statistics, the image's contribution rule) is rtpb_stats.h,
 // the host arithmetic of a call (row planning, media table, upload layout) rtpb_sweep_host.h.
 #include "rtpb_stats.h"
@@ -16,6 +16,7 @@ namespace {
 // bit-identical to generating, tracing (planes='final') and reducing separately -- without the
 // 3 x 64 B per ray of HBM traffic and the launches in between.
 struct SweepImage;
+struct SweepWave;
 struct SweepArgs {
     const DevSurface<double>* __restrict__ surf;
     const DevMaterial<double>* __restrict__ mats;
@@ -29,6 +30,7 @@ struct SweepArgs {
     union {
         double* __restrict__ partials;              // spot and focus statistics
         const SweepImage* __restrict__ image;       // image mode
+        const SweepWave* __restrict__ wave;         // wavefront mode
     };
     int64_t n_thetas, nphis, gsize, tiles;
     double c[3], ex[3], ey[3];
@@ -47,6 +49,13 @@ struct SweepImage {
     int32_t nx, ny;
 };
 static_assert(sizeof(SweepImage) % sizeof(double) == 0, "the windows follow it");
+
+// The wavefront mode's block of the upload, in the same place: where the tile partials go, followed by the groups'
+// references (kWaveRef doubles each, rtpb_stats.h)
+struct SweepWave {
+    double* partials;
+};
+static_assert(sizeof(SweepWave) == sizeof(double), "the references follow it");
 
 template <typename TS>
 __device__ __forceinline__ double stored(double v) { return static_cast<double>(static_cast<TS>(v)); }
@@ -79,7 +88,13 @@ constexpr int kStateRows = 11;                     // bundle state per lane: x y
 #ifndef RTPB_SWEEP_WPE
 #define RTPB_SWEEP_WPE 6
 #endif
-#define RTPB_SWEEP_ATTR __attribute__((amdgpu_waves_per_eu(RTPB_SWEEP_WPE, 8)))
+// The wavefront instantiations run the trace kernel's full step with the phase and the whole direction alive to the
+// end: RTPB_WAVE_WPE waves per SIMD for them (the registers, scratch and LDS at each setting)
+#ifndef RTPB_WAVE_WPE
+#define RTPB_WAVE_WPE 4
+#endif
+#define RTPB_SWEEP_ATTR(NS) \
+    __attribute__((amdgpu_waves_per_eu((NS) == kWaveStats ? RTPB_WAVE_WPE : RTPB_SWEEP_WPE, 8)))
 // An optimisation fence on three per-lane values: the compiler moves no computation on them across it
 #if defined(__HIP_DEVICE_COMPILE__)
 #define RTPB_PIN3(a, b, c) asm volatile("" : "+v"(a), "+v"(b), "+v"(c))
@@ -93,11 +108,18 @@ constexpr int kStateRows = 11;                     // bundle state per lane: x y
 // others.  Single rows reduce eight of the sixteen statistics at a time (16 KB of LDS), bundle rows two as before.
 // NS = kImageStats (rtpb_image_sweep): no statistics, each counted ray goes into its group's image instead
 // (image_bin, wave_image_add); the rule of which rays count is the spot statistics', and there are no red tiles.
+// NS = kWaveStats (rtpb_wavefront_sweep; float64, single rows only): wave_ray of the final state against the group's
+// reference.  The phase is wanted, so the steps are the final-plane trace kernel's (kNoAt: the full semantics of
+// every surface, its roots and square roots included, and no carried x x + y y) and the final state is the one
+// rtpb_trace stores, phase and all; eight of the fifteen statistics at a time.
 constexpr int kImageStats = 0;
 template <typename TS, int FEAT, bool BUNDLE, int NS = kStats>
-__global__ __launch_bounds__(kBlock) RTPB_SWEEP_ATTR void sweep_kernel(SweepArgs a) {
+__global__ __launch_bounds__(kBlock) RTPB_SWEEP_ATTR(NS) void sweep_kernel(SweepArgs a) {
     static_assert(!BUNDLE || (FEAT & 16) != 0, "bundles: host-evaluated media");
-    static_assert(NS == kStats || NS == kFocusStats || NS == kImageStats, "spot or focus statistics, or the image");
+    static_assert(NS == kStats || NS == kFocusStats || NS == kImageStats || NS == kWaveStats,
+                  "spot, focus or wavefront statistics, or the image");
+    constexpr bool kWave = NS == kWaveStats;
+    static_assert(!kWave || (!BUNDLE && sizeof(TS) == 8), "wavefront: float64, single rows");
     constexpr int kRedRows = NS == kImageStats ? 1 : BUNDLE ? 2 : NS == kStats ? kStats : 8;
     __shared__ double red[kRedRows][kBlock];
     __shared__ double state[BUNDLE ? kStateRows : 1][kBlock];
@@ -155,7 +177,7 @@ __global__ __launch_bounds__(kBlock) RTPB_SWEEP_ATTR void sweep_kernel(SweepArgs
         return sd;
     };
     auto code_of = [&](int k) { return surface_code<double>((surf + k)->kind, (surf + k)->rcp_ok); };
-    constexpr int kMode = kPosOnly | ((FEAT & 16) != 0 ? kUniMedia : 0);
+    constexpr int kMode = (kWave ? kNoAt : kPosOnly) | ((FEAT & 16) != 0 ? kUniMedia : 0);
     // the statistics read only the final positions: the steps run with kPosOnly semantics (no TIR fill of the
     // position -- the next surface's intersection makes it NaN, and the final plane gets the rule in reduce), and a
     // run of axial spheres carries x x + y y of each intersection point into the next sphere's quadratic.
@@ -169,7 +191,7 @@ __global__ __launch_bounds__(kBlock) RTPB_SWEEP_ATTR void sweep_kernel(SweepArgs
             dispatch_code<(FEAT & 1) != 0>(code, [&](auto kind, auto geo) {
                 constexpr int K = decltype(kind)::value;
                 constexpr int A = decltype(geo)::value;
-                constexpr bool kCarry = K == SPHERE && A == kGeoAxial;
+                constexpr bool kCarry = K == SPHERE && A == kGeoAxial && !kWave;
                 if constexpr (kCarry) {
 #pragma unroll
                     for (int q = 0; q < kSweepRays; ++q) rxy[q] = r[q].x * r[q].x + r[q].y * r[q].y;
@@ -204,6 +226,10 @@ __global__ __launch_bounds__(kBlock) RTPB_SWEEP_ATTR void sweep_kernel(SweepArgs
     auto reduce = [&](const Ray<double>& rr, bool ok, int64_t g, int64_t t) {
         double v[kStats] = {};
         FocusRay f{0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+        WaveRay wv{0.0, 0.0, 0.0, 0.0, 0.0};
+        double* out;
+        if constexpr (kWave) out = ((cptr<SweepWave>)(a.wave))->partials;
+        else out = a.partials;
         // the reference's position rule of the last surface (RT:1221 / RT:1289; a PerfectLens's after-plane
         // propagation gives a NaN position for a NaN direction by itself): NaN direction -> no spot point
         if (ok && !is_nan(rr.dx)) {
@@ -212,6 +238,10 @@ __global__ __launch_bounds__(kBlock) RTPB_SWEEP_ATTR void sweep_kernel(SweepArgs
                 if (x - x == 0.0 && y - y == 0.0) {
                     v[0] = 1.0; v[1] = x; v[2] = y; v[3] = z; v[4] = x * x; v[5] = y * y; v[6] = x * y;
                 }
+            } else if constexpr (kWave) {
+                const cptr<double> q = (cptr<double>)(a.wave + 1) + kWaveRef * g;
+                const double ref[kWaveRef] = {q[0], q[1], q[2], q[3], q[4], q[5], q[6], q[7]};
+                wv = wave_ray(x, y, z, rr.dx, rr.dy, rr.dz, rr.ph, ref);
             } else {
                 double dx = stored<TS>(rr.dx), dy = stored<TS>(rr.dy), dz = stored<TS>(rr.dz);
                 // the slopes' divisions stay behind the trace: without the fence the float64 instantiations spill
@@ -226,13 +256,14 @@ __global__ __launch_bounds__(kBlock) RTPB_SWEEP_ATTR void sweep_kernel(SweepArgs
 #pragma unroll
             for (int j = 0; j < kRedRows; ++j) {
                 if constexpr (NS == kStats) u[j] = k0 + j < NS ? v[k0 + j] : 0.0;
+                else if constexpr (kWave) u[j] = wave_term(wv, k0 + j);
                 else u[j] = focus_term(f, k0 + j);
             }
             block_tree_sum<kRedRows>(u, red);
             if (tid == 0 && t < a.tiles) {
 #pragma unroll
                 for (int j = 0; j < kRedRows; ++j)
-                    if (k0 + j < NS) a.partials[(g * a.tiles + t) * NS + k0 + j] = u[j];
+                    if (k0 + j < NS) out[(g * a.tiles + t) * NS + k0 + j] = u[j];
             }
         }
     };
@@ -368,20 +399,24 @@ __global__ __launch_bounds__(kBlock) RTPB_SWEEP_ATTR void sweep_kernel(SweepArgs
     }
 }
 
-// rtpb_spot_sweep (NS = kStats) and rtpb_focus_sweep (NS = kFocusStats): the argument checks ...
+// rtpb_spot_sweep (NS = kStats), rtpb_focus_sweep (NS = kFocusStats) and rtpb_wavefront_sweep (NS = kWaveStats): the
+// argument checks ...
 template <int NS>
 int sweep_check(int64_t n_groups, const double* group_params, int64_t n_thetas, int64_t nphis,
                 const double center_ray[3], const double ex[3], const double ey[3], const double* theta_cos_sin,
                 const double* phi_cos_sin, double* workspace, int64_t workspace_len, double* stats_out) {
-    constexpr bool kFocus = NS == kFocusStats;
+    constexpr bool kFocus = NS == kFocusStats, kWave = NS == kWaveStats;
     if (n_groups <= 0 || n_thetas <= 0 || nphis <= 0 || !group_params || !center_ray || !ex || !ey ||
         !theta_cos_sin || !phi_cos_sin || !workspace || !stats_out)
-        return fail(RTPB_E_INVALID, kFocus ? "bad focus-sweep arguments" : "bad spot-sweep arguments");
+        return fail(RTPB_E_INVALID, kWave    ? "bad wavefront-sweep arguments"
+                                    : kFocus ? "bad focus-sweep arguments"
+                                             : "bad spot-sweep arguments");
     const int64_t tiles = (n_thetas * nphis + kBlock - 1) / kBlock;
     if (workspace_len < n_groups * tiles * NS)
         return fail(RTPB_E_INVALID,
-                    kFocus ? "workspace too small: need n_groups * ceil(n_thetas*nphis/256) * 16 doubles"
-                           : "workspace too small: need n_groups * ceil(n_thetas*nphis/256) * 7 doubles");
+                    kWave    ? "workspace too small: need n_groups * ceil(n_thetas*nphis/256) * 15 doubles"
+                    : kFocus ? "workspace too small: need n_groups * ceil(n_thetas*nphis/256) * 16 doubles"
+                             : "workspace too small: need n_groups * ceil(n_thetas*nphis/256) * 7 doubles");
     if (tiles > 0x7fffffffll || n_groups > 65535) return fail(RTPB_E_LIMIT, "too many groups or rays per group");
     return RTPB_OK;
 }
@@ -396,13 +431,14 @@ struct ImageCall {
 
 // ... and the sweep itself (checked arguments): plan the block rows, fill and send the one upload, launch the sweep
 // kernels of the statistics set, then the final reduction -- or, for the image, clear the outputs and launch the
-// image kernels
+// image kernels.  refs: the wavefront mode's references (host, n_groups x kWaveRef); every group of that mode is a
+// single row (the bundle rows' shared first surface keeps no phase) and its storage type is float64.
 template <int NS>
 int sweep_impl(const rtpb_plan* plan_c, int32_t device, int64_t n_groups, const double* group_params,
                int64_t n_thetas, int64_t nphis, const double center_ray[3], const double ex[3], const double ey[3],
                const double* theta_cos_sin, const double* phi_cos_sin, double* workspace, double* stats_out,
-               void* stream, const ImageCall* im = nullptr) {
-    constexpr bool kImage = NS == kImageStats;
+               void* stream, const ImageCall* im = nullptr, const double* refs = nullptr) {
+    constexpr bool kImage = NS == kImageStats, kWave = NS == kWaveStats;
     auto* plan = const_cast<rtpb_plan*>(plan_c);
     const int64_t gsize = n_thetas * nphis;
     const int64_t tiles = (gsize + kBlock - 1) / kBlock;
@@ -414,10 +450,13 @@ int sweep_impl(const rtpb_plan* plan_c, int32_t device, int64_t n_groups, const 
     // bundle rows need the host-evaluated media, which a POLY6 material rules out
     const bool pre_n = (plan->feat & 2) == 0;
     const size_t M = plan->mats.size();
-    const SweepRows pr = plan_sweep_rows(group_params, n_groups, pre_n, kSweepRays, kMaxBundle);
+    const SweepRows pr = plan_sweep_rows(group_params, n_groups, pre_n && !kWave, kSweepRays, kMaxBundle);
     const SweepLayout lay(n_thetas, nphis, n_groups, pre_n ? M + 3 * (M - 1) : 0,
                           pr.bundles.size() + pr.singles.size() + pr.rows.size(),
-                          kImage ? sizeof(SweepImage) / sizeof(double) : 0);
+                          kImage  ? sizeof(SweepImage) / sizeof(double)
+                          : kWave ? sizeof(SweepWave) / sizeof(double)
+                                  : 0,
+                          kWave ? kWaveRef : 4);
     StreamScratch dbuf;
     rc = dbuf.alloc(lay.bytes, st);
     if (rc) return rc;
@@ -441,6 +480,11 @@ int sweep_impl(const rtpb_plan* plan_c, int32_t device, int64_t n_groups, const 
         rc = image_clear(im->image_out, im->outside_out, n_groups, im->nx, im->ny, st);
         if (rc) return rc;
     }
+    if constexpr (kWave) {
+        const SweepWave head{workspace};
+        std::memcpy(h + lay.img, &head, sizeof(head));
+        std::memcpy(h + lay.win, refs, size_t(kWaveRef * n_groups) * sizeof(double));
+    }
     int32_t* hidx = reinterpret_cast<int32_t*>(h + lay.idx);
     hidx = std::copy(pr.bundles.begin(), pr.bundles.end(), hidx);
     hidx = std::copy(pr.singles.begin(), pr.singles.end(), hidx);
@@ -457,6 +501,7 @@ int sweep_impl(const rtpb_plan* plan_c, int32_t device, int64_t n_groups, const 
     a.gn = reinterpret_cast<const double*>(d + lay.gn);
     const int32_t* didx = reinterpret_cast<const int32_t*>(d + lay.idx);
     if constexpr (kImage) a.image = reinterpret_cast<const SweepImage*>(d + lay.img);
+    else if constexpr (kWave) a.wave = reinterpret_cast<const SweepWave*>(d + lay.img);
     else a.partials = workspace;
     a.n_thetas = n_thetas;
     a.nphis = nphis;
@@ -470,13 +515,15 @@ int sweep_impl(const rtpb_plan* plan_c, int32_t device, int64_t n_groups, const 
     auto go = [&](auto tag) {
         using TS = decltype(tag);
         const int f = plan->feat & 3;                 // lens / POLY6 code (no pre_n: POLY6); tables always compiled in
-        if (!pr.rows.empty()) {
-            SweepArgs ap = a;
-            ap.gidx = didx;
-            ap.rows = didx + pr.bundles.size() + pr.singles.size();
-            const dim3 grid(static_cast<unsigned>(tiles), static_cast<unsigned>(pr.rows.size() / 2));
-            if (f == 0) hipLaunchKernelGGL((sweep_kernel<TS, 16, true, NS>), grid, dim3(kBlock), 0, st, ap);
-            else hipLaunchKernelGGL((sweep_kernel<TS, 17, true, NS>), grid, dim3(kBlock), 0, st, ap);
+        if constexpr (!kWave) {                       // (the wavefront mode plans no bundle rows)
+            if (!pr.rows.empty()) {
+                SweepArgs ap = a;
+                ap.gidx = didx;
+                ap.rows = didx + pr.bundles.size() + pr.singles.size();
+                const dim3 grid(static_cast<unsigned>(tiles), static_cast<unsigned>(pr.rows.size() / 2));
+                if (f == 0) hipLaunchKernelGGL((sweep_kernel<TS, 16, true, NS>), grid, dim3(kBlock), 0, st, ap);
+                else hipLaunchKernelGGL((sweep_kernel<TS, 17, true, NS>), grid, dim3(kBlock), 0, st, ap);
+            }
         }
         if (!pr.singles.empty()) {
             SweepArgs as = a;
@@ -488,8 +535,12 @@ int sweep_impl(const rtpb_plan* plan_c, int32_t device, int64_t n_groups, const 
             else hipLaunchKernelGGL((sweep_kernel<TS, 3, false, NS>), grid, dim3(kBlock), 0, st, as);   // POLY6 media
         }
     };
-    if (plan->dtype == RTPB_F64) go(double{});
-    else go(float{});
+    if constexpr (kWave) {
+        go(double{});
+    } else {
+        if (plan->dtype == RTPB_F64) go(double{});
+        else go(float{});
+    }
     HIP_TRY(hipGetLastError());
     if constexpr (!kImage) {
         rc = launch_stats_final(NS, workspace, stats_out, n_groups, tiles, st);
@@ -529,6 +580,26 @@ int rtpb_focus_sweep(const rtpb_plan* plan, int32_t device, int64_t n_groups, co
     if (rc) return rc;
     return sweep_impl<kFocusStats>(plan, device, n_groups, group_params, n_thetas, nphis, center_ray, ex, ey,
                                    theta_cos_sin, phi_cos_sin, workspace, stats_out, stream);
+}
+
+int rtpb_wavefront_sweep(const rtpb_plan* plan, int32_t device, int64_t n_groups, const double* group_params,
+                         int64_t n_thetas, int64_t nphis, const double center_ray[3], const double ex[3],
+                         const double ey[3], const double* theta_cos_sin, const double* phi_cos_sin,
+                         const double* refs, double* workspace, int64_t workspace_len, double* stats_out,
+                         void* stream) {
+    // (the arguments first: a bad call is RTPB_E_INVALID / RTPB_E_LIMIT with or without a GPU)
+    if (!plan) return fail(RTPB_E_INVALID, "plan is NULL");
+    if (plan->dtype != RTPB_F64)
+        return fail(RTPB_E_INVALID, "wavefront-sweep: float64 plans only (a float32 phase of 1e4 ... 1e7 rad has an "
+                                    "ulp of a milliradian to a radian: its wavefront is noise)");
+    if (!refs) return fail(RTPB_E_INVALID, "bad wavefront-sweep arguments");
+    int rc = sweep_check<kWaveStats>(n_groups, group_params, n_thetas, nphis, center_ray, ex, ey, theta_cos_sin,
+                                     phi_cos_sin, workspace, workspace_len, stats_out);
+    if (rc) return rc;
+    rc = check_device(device);
+    if (rc) return rc;
+    return sweep_impl<kWaveStats>(plan, device, n_groups, group_params, n_thetas, nphis, center_ray, ex, ey,
+                                  theta_cos_sin, phi_cos_sin, workspace, stats_out, stream, nullptr, refs);
 }
 
 int rtpb_image_sweep(const rtpb_plan* plan, int32_t device, int64_t n_groups, const double* group_params,

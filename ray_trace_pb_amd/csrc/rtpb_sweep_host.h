@@ -72,17 +72,18 @@ inline void fill_group_media(const rtpb::DevMaterial<double>* mats, size_t n_mat
 
 // The one upload of a sweep, as byte offsets (for the pinned host copy and the device block alike): the trig tables
 // ((cos, sin) pairs: thetas, then phis) at 0, the group parameters, the media table (media_doubles per group, or 0),
-// the image sweep's block (image_head_doubles for its output header, then the windows, 4 doubles per group; nothing
-// for the other sweeps), then the int32 index block (bundles, singles, rows).
+// the image or wavefront sweep's block (head_doubles for its header, then per_group doubles per group: the image's
+// windows, 4, or the wavefront references, 8; nothing for the other sweeps), then the int32 index block (bundles,
+// singles, rows).
 struct SweepLayout {
     size_t grp, gn, img, win, idx, bytes;
     SweepLayout(int64_t n_thetas, int64_t nphis, int64_t n_groups, size_t media_doubles, size_t n_idx,
-                size_t image_head_doubles = 0) {
+                size_t head_doubles = 0, size_t per_group = 4) {
         grp = size_t(n_thetas + nphis) * 2 * sizeof(double);
         gn = grp + size_t(4 * n_groups) * sizeof(double);
         img = gn + size_t(n_groups) * media_doubles * sizeof(double);
-        win = img + image_head_doubles * sizeof(double);
-        idx = win + (image_head_doubles ? size_t(4 * n_groups) * sizeof(double) : 0);
+        win = img + head_doubles * sizeof(double);
+        idx = win + (head_doubles ? per_group * size_t(n_groups) * sizeof(double) : 0);
         bytes = idx + n_idx * sizeof(int32_t);
     }
 };

@@ -1,0 +1,79 @@
+"""The wavefront statistics restated in NumPy, and references built from the oracle alone (not a test module).
+
+``wave_terms`` is the one definition of a ray's contribution (include/rtpb.h, csrc/rtpb_stats.h wave_ray /
+wave_term), operation for operation; ``fixed_order_wave_sums`` adds the kernels' two-stage reduction (a pairwise
+tree per 256-ray tile, then the tiles in the final kernel's order), as tests/test_gpu_focus.py does for the focus
+sums.  ``oracle_refs`` gives the references (C0, d0, p0, kf) of a sweep's groups from oracle-traced fans and chief
+rays; tests/test_wavefront_host.py checks on the CPU what tests/test_gpu_wavefront.py assumes about them."""
+import numpy as np
+
+import ray_trace_pb_amd.raytrace as rt
+from oracle import rt_numpy as O
+
+INV_2PI = 0.15915494309189535
+NS = 15
+
+
+def wave_terms(plane, group_size, refs):
+    """(G, group_size, 15) terms of an (N, 8) float64 plane against refs (G, 8): +0 rows for rays that do not count."""
+    p = np.asarray(plane, dtype=np.float64).reshape(-1, group_size, 8)
+    r = np.asarray(refs, dtype=np.float64).reshape(-1, 1, 8)
+    assert r.shape[0] == p.shape[0]
+    x, y, z, dx, dy, dz, ph = (p[..., k] for k in range(7))
+    with np.errstate(invalid="ignore", over="ignore"):
+        ex, ey, ez = dx - r[..., 3], dy - r[..., 4], dz - r[..., 5]
+        s = ((r[..., 0] - x) * dx + (r[..., 1] - y) * dy) + (r[..., 2] - z) * dz
+        w = (ph - r[..., 6]) * INV_2PI + s * r[..., 7]
+        ok = (x - x == 0.0) & (y - y == 0.0) & (w - w == 0.0) & (ex - ex == 0.0) & (ey - ey == 0.0) & (ez - ez == 0.0)
+        terms = np.stack((np.ones_like(x), w, w * w, ex, ey, ez, w * ex, w * ey, w * ez, ex * ex, ey * ey, ez * ez,
+                          ex * ey, ex * ez, ey * ez), -1)
+    return np.where(ok[..., None], terms, 0.0)
+
+
+def fixed_order_wave_sums(plane, group_size, refs, tile=256):
+    """(G, 15): wave_terms reduced in the kernels' order -- per 256-ray tile a pairwise tree (red[t] += red[t + w],
+    w = 128 ... 1); per group, thread t adds tiles t, t + 256, ... in order, then the same tree over the threads."""
+    terms = wave_terms(plane, group_size, refs)
+    G = terms.shape[0]
+    tiles = -(-group_size // tile)
+    acc = np.zeros((G, tiles * tile, NS))
+    acc[:, :group_size] = terms
+    acc = acc.reshape(G, tiles, tile, NS)
+    w = tile // 2
+    while w:
+        acc[:, :, :w] = acc[:, :, :w] + acc[:, :, w:2 * w]
+        w //= 2
+    part = acc[:, :, 0]
+    fin = np.zeros((G, tile, NS))
+    for c in range(0, tiles, tile):
+        blk = part[:, c:c + tile]
+        fin[:, :blk.shape[1]] = fin[:, :blk.shape[1]] + blk
+    w = tile // 2
+    while w:
+        fin[:, :w] = fin[:, :w] + fin[:, w:2 * w]
+        w //= 2
+    return fin[:, 0]
+
+
+def oracle_chief(S, M, field, wl, center_ray=(0.0, 0.0, 1.0)):
+    """The final state (8,) of the chief ray of a group: the field point along center_ray, traced by the oracle."""
+    return O.ray_trace(S, M, rt.get_ray_fan(field, 0.0, 1, wl, center_ray=center_ray))[-1][0]
+
+
+def oracle_refs(S, M, final_material, fields, wls, finals, center_ray=(0.0, 0.0, 1.0)):
+    """(n_fields, n_wavelengths, 8) references from the oracle: C0 the mean position of the rays with finite x and y
+    of the group's final plane (``finals``: (groups * rays, 8), field-major), d0 and p0 the oracle's chief ray,
+    kf = n_final / wavelength.  A group whose chief ray is not finite gets NaN."""
+    fields = np.atleast_2d(np.asarray(fields, dtype=float))
+    nf, nw = len(fields), len(wls)
+    fin = np.asarray(finals).reshape(nf, nw, -1, 8)
+    refs = np.full((nf, nw, 8), np.nan)
+    for i, f in enumerate(fields):
+        for j, wl in enumerate(wls):
+            chief = oracle_chief(S, M, f, wl, center_ray)
+            ok = np.isfinite(fin[i, j, :, 0]) & np.isfinite(fin[i, j, :, 1])
+            if np.isfinite(chief[:7]).all() and ok.any():
+                refs[i, j, 0:3] = fin[i, j, ok, :3].mean(axis=0)
+                refs[i, j, 3:7] = chief[3:7]
+                refs[i, j, 7] = float(final_material.n(wl)) / wl
+    return refs

@@ -7,7 +7,9 @@ across ranks (no collective besides the final gather of the small statistics tab
 
 ``--sweep focus`` times analysis.focus_sweep instead, ``--sweep image`` analysis.image_sweep (``--bins`` x ``--bins``
 images, explicit windows taken from an untimed spot_sweep of the same workload, so the timed pass is one sweep) next
-to a spot_sweep timed in the same process: the line then carries both per-device kernel times and their ratio.
+to a spot_sweep timed in the same process: the line then carries both per-device kernel times and their ratio;
+``--sweep wave`` does the same for analysis.wavefront_sweep (float64; the references from the untimed spot_sweep and
+one chief ray per group).
 ``--repeats`` times the sweep that often (every repeat's per-device kernel_ms is in the line); ``--lib`` loads
 another build of the library, e.g. the parent commit's, for alternating A/B processes.
 """
@@ -32,7 +34,7 @@ def main():
     ap.add_argument("--warmup", type=int, default=1,
                     help="untimed small sweeps first (plan creation, code-object load on first launch)")
     ap.add_argument("--lib", default="", help="library build to load instead of the in-tree librtpb.so (A/B)")
-    ap.add_argument("--sweep", default="spot", choices=("spot", "focus", "image"))
+    ap.add_argument("--sweep", default="spot", choices=("spot", "focus", "image", "wave"))
     ap.add_argument("--bins", type=int, default=64, help="--sweep image: bins per side")
     ap.add_argument("--repeats", type=int, default=1,
                     help="timed sweeps (the line reports the last, and every repeat's kernel_ms)")
@@ -82,6 +84,13 @@ def main():
 
         def sweep(*a, **k):
             return analysis.image_sweep(*a, bins=args.bins, windows=windows, **k)
+    if args.sweep == "wave":
+        spot, spot_timing = analysis.spot_sweep(*call, **kw)
+        refs = analysis.wavefront_refs(*call[:5], spot_summary=spot, device=dev)
+        kw.pop("dtype")
+
+        def sweep(*a, **k):
+            return analysis.wavefront_sweep(*a, refs=refs, **k)
     kernel_ms = []
     for _ in range(args.repeats):
         t0 = time.perf_counter()
@@ -101,6 +110,15 @@ def main():
                  "rank0_inside_fraction_first_fields": (summ["image"].sum(axis=(-2, -1))[:2] /
                                                         np.maximum(summ["count"][:2], 1)).tolist(),
                  "rank0_occupied_bins_first_fields": (summ["image"] > 0).sum(axis=(-2, -1))[:2].tolist()}
+        summ = dict(spot, count=summ["count"])
+    if args.sweep == "wave":
+        _, spot_after = analysis.spot_sweep(*call, dtype=args.dtype, **kw)
+        ms = [[d["kernel_ms"] for d in t["per_device"]] for t in (spot_timing, spot_after)]
+        wav = [float(np.median([r[i] for r in kernel_ms])) for i in range(len(kernel_ms[0]))]
+        extra = {"spot_kernel_ms_before_after": ms, "wave_kernel_ms_median": wav,
+                 "wave_over_spot_kernel_ms": [2 * m / (a + b) for m, a, b in zip(wav, *ms)],
+                 "rank0_rms_opd_waves_first_fields": summ["rms_opd"][:2].tolist(),
+                 "rank0_rms_opd_best_waves_first_fields": summ["rms_opd_best"][:2].tolist()}
         summ = dict(spot, count=summ["count"])
     rays = timing["rays"]
     if world > 1:
