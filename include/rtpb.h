@@ -56,8 +56,9 @@ extern "C" {
                                 9: + rtpb_trace_packed (rtpb_trace_checked's arguments in one struct)
                                 10: + rtpb_focus_stats / rtpb_focus_sweep (through-focus statistics);
                                     rtpb_spot_image / rtpb_image_sweep (spot images) and
-                                    rtpb_wavefront_stats / rtpb_wavefront_sweep (wavefront statistics) joined
-                                    within 10: new symbols only, nothing existing changed */
+                                    rtpb_wavefront_stats / rtpb_wavefront_sweep (wavefront statistics) and the
+                                    four rtpb_*_sweep_collimated (collimated-beam sweeps) joined within 10: new
+                                    symbols only, nothing existing changed */
 
 /* ---- error codes ---------------------------------------------------------------------------- */
 #define RTPB_OK 0
@@ -463,6 +464,42 @@ int rtpb_wavefront_sweep(const rtpb_plan* plan, int32_t device, int64_t n_groups
                          const double ey[3], const double* theta_cos_sin, const double* phi_cos_sin,
                          const double* refs, double* workspace, int64_t workspace_len, double* stats_out,
                          void* stream);
+
+/* Fused sweeps of COLLIMATED BEAMS (objects at infinity): the four sweeps above with another source of rays.  For
+   every group g the beam get_collimated_rays(pt_g, displacement_max, n_disps, wavelength_g, nphis, phi_start,
+   normal_g) (RT:99-161) is generated, traced through `plan` (final state only) and reduced -- the same kernel with
+   another generator, the same row planning, statistics, images and references, nothing but the results reaching HBM.
+   group_params: HOST, n_groups x {x, y, z, wavelength}, the beam's point pt and its wavelength.
+   group_frames: HOST, n_groups x 9 {normal, n1, n2}: the beam's direction (a unit vector) and the basis of its
+   cross-section, n1 = (0,1,0) x normal (normal x (1,0,0) where that vanishes) and n2 = normal x n1, both normalised,
+   evaluated by the caller as for rtpb_collimated_rays_tables.  offsets: HOST, n_disps doubles, the caller's
+   linspace(-displacement_max, displacement_max, n_disps); phi_cos_sin: HOST, nphis (cos, sin) pairs of
+   phi_start + 2 pi i / nphis.  Ray k = idisp * nphis + iphi of a group starts at
+       pt + n1 * (off * cos phi) + n2 * (off * sin phi)        (each product and sum one rounded operation, no FMA)
+   along normal with phase 0, every value rounded through the plan's storage type: the results are bit-identical to
+   rtpb_collimated_rays_tables + rtpb_trace (final plane) + rtpb_spot_stats / rtpb_focus_stats / rtpb_spot_image /
+   rtpb_wavefront_stats.  Groups with the same point AND the same frame (bit for bit) are swept together, as the
+   fans of one field point are, so a call should hold all the wavelengths of its beams; beams that share a point and
+   differ in direction are swept apart.  Workspace sizes (with n_disps*nphis rays per group), the 65535-group and
+   tile limits, the float64-only rule of the wavefront call and the error codes are those of the fan calls; the
+   arguments are checked before the device is. */
+int rtpb_spot_sweep_collimated(const rtpb_plan* plan, int32_t device, int64_t n_groups, const double* group_params,
+                               const double* group_frames, int64_t n_disps, int64_t nphis, const double* offsets,
+                               const double* phi_cos_sin, double* workspace, int64_t workspace_len,
+                               double* stats_out, void* stream);
+int rtpb_focus_sweep_collimated(const rtpb_plan* plan, int32_t device, int64_t n_groups, const double* group_params,
+                                const double* group_frames, int64_t n_disps, int64_t nphis, const double* offsets,
+                                const double* phi_cos_sin, double* workspace, int64_t workspace_len,
+                                double* stats_out, void* stream);
+int rtpb_wavefront_sweep_collimated(const rtpb_plan* plan, int32_t device, int64_t n_groups,
+                                    const double* group_params, const double* group_frames, int64_t n_disps,
+                                    int64_t nphis, const double* offsets, const double* phi_cos_sin,
+                                    const double* refs, double* workspace, int64_t workspace_len, double* stats_out,
+                                    void* stream);
+int rtpb_image_sweep_collimated(const rtpb_plan* plan, int32_t device, int64_t n_groups, const double* group_params,
+                                const double* group_frames, int64_t n_disps, int64_t nphis, const double* offsets,
+                                const double* phi_cos_sin, const double* windows, int32_t nx, int32_t ny,
+                                int32_t* image_out, int32_t* outside_out, void* stream);
 
 /* ---- pupil-phase interpolation (scripts/2022_02_06_perfect_imaging_system_psf.py:90-105) */
 /* A 2-D Delaunay triangulation with one value per vertex, in scipy.spatial.Delaunay's representation,

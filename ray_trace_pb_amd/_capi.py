@@ -116,6 +116,12 @@ SIGNATURES = {
     "rtpb_wavefront_stats": (ctypes.c_int, [_i32, _i32, _P, _i64, _i64, _P, _P, _i64, _P, _P]),
     "rtpb_wavefront_sweep": (ctypes.c_int, [_P, _i32, _i64, _P, _i64, _i64, _P, _P, _P, _P, _P, _P, _P, _i64, _P,
                                             _P]),
+    "rtpb_spot_sweep_collimated": (ctypes.c_int, [_P, _i32, _i64, _P, _P, _i64, _i64, _P, _P, _P, _i64, _P, _P]),
+    "rtpb_focus_sweep_collimated": (ctypes.c_int, [_P, _i32, _i64, _P, _P, _i64, _i64, _P, _P, _P, _i64, _P, _P]),
+    "rtpb_wavefront_sweep_collimated": (ctypes.c_int, [_P, _i32, _i64, _P, _P, _i64, _i64, _P, _P, _P, _P, _i64, _P,
+                                                       _P]),
+    "rtpb_image_sweep_collimated": (ctypes.c_int, [_P, _i32, _i64, _P, _P, _i64, _i64, _P, _P, _P, _i32, _i32, _P, _P,
+                                                   _P]),
     "rtpb_set_tuning": (ctypes.c_int, [ctypes.c_char_p, _i64]),
     "rtpb_timing_enable": (ctypes.c_int, [_i32]),
     "rtpb_timing_collect": (ctypes.c_int, [ctypes.POINTER(_dbl), ctypes.POINTER(_i64)]),

@@ -6,6 +6,8 @@ fans are generated on the GPU (``rtpb_ray_fan_tables``), traced with only the fi
 on the GPU with a deterministic fixed-order reduction (``rtpb_spot_stats``) -- or binned into per-group spot
 images of integer counts (``rtpb_spot_image``, :func:`image_sweep`), or reduced to the moments of the optical path
 difference (``rtpb_wavefront_stats``, :func:`wavefront_sweep`: RMS wavefront error, diffraction focus, Strehl).
+The ``collimated_*`` sweeps run the same four analyses on ``get_collimated_rays`` beams, one per (field direction,
+wavelength): objects at infinity (``rtpb_*_sweep_collimated``).
 """
 import time
 from types import SimpleNamespace
@@ -282,8 +284,9 @@ def spot_sweep(system, initial_material, final_material, field_points, wavelengt
     give bit-identical statistics.  ``devices`` (fused only): the (field, wavelength) groups are split into
     contiguous ranges, one per GPU, swept concurrently from this thread (per-device kernel times in the
     timing dict).  Returns (summary dict with arrays shaped (n_fields, n_wavelengths, ...), timing dict)."""
-    return _sweep(_SPOT, system, initial_material, final_material, field_points, wavelengths, theta_max, n_thetas,
-                  nphis, center_ray, device, dtype, groups_per_batch, fused, devices)
+    return _sweep(_SPOT, system, initial_material, final_material,
+                  _fan_source(field_points, wavelengths, theta_max, n_thetas, nphis, center_ray), device, dtype,
+                  groups_per_batch, fused, devices)
 
 
 def _image_plane_normal_to_z(system):
@@ -309,12 +312,17 @@ def focus_sweep(system, initial_material, final_material, field_points, waveleng
     ``ValueError`` unless that surface is a ``FlatSurface`` or ``PlaneMirror`` with normal exactly (0, 0, +-1);
     with ``False`` the raw moments are returned for any system, and the focus quantities describe the bundle only
     as far as the last surface is a z-plane."""
+    _require_image_plane(system, require_image_plane)
+    return _sweep(_FOCUS, system, initial_material, final_material,
+                  _fan_source(field_points, wavelengths, theta_max, n_thetas, nphis, center_ray), device, dtype,
+                  groups_per_batch, fused, devices)
+
+
+def _require_image_plane(system, require_image_plane):
     if require_image_plane and not _image_plane_normal_to_z(system):
         raise ValueError("focus_sweep: the last surface must be an image plane normal to z (a FlatSurface or "
                          "PlaneMirror with normal (0, 0, +-1)); append an image plane to the system, or pass "
                          "require_image_plane=False for the raw moments on the last surface")
-    return _sweep(_FOCUS, system, initial_material, final_material, field_points, wavelengths, theta_max, n_thetas,
-                  nphis, center_ray, device, dtype, groups_per_batch, fused, devices)
 
 
 def wavefront_refs(system, initial_material, final_material, field_points, wavelengths, center_ray=(0, 0, 1),
@@ -327,17 +335,24 @@ def wavefront_refs(system, initial_material, final_material, field_points, wavel
     ray -- the field point along ``center_ray``, ``get_ray_fan(field, 0, 1, wavelength)`` -- traced through the
     ordinary ``planes='final'`` path, and kf = final_material.n(wavelength) / wavelength.  A group whose chief ray
     dies gets a reference of NaN: every ray's OPD is then NaN, the group counts 0 and its summary is NaN."""
-    import torch
     from .raytrace import get_ray_fan
     field_points, wavelengths = _grid(field_points, wavelengths)
-    nf, nw = field_points.shape[0], wavelengths.size
+    nf = field_points.shape[0]
     if spot_summary is None:
         spot_summary, _ = spot_sweep(system, initial_material, final_material, field_points, wavelengths,
                                      center_ray=center_ray, device=device, **fan_kw)
-    refs = np.empty((nf, nw, 8))
-    refs[..., 0:3] = np.asarray(spot_summary["centroid"], dtype=np.float64).reshape(nf, nw, 3)
     chief = np.concatenate([get_ray_fan(f, 0.0, 1, w, center_ray=center_ray) for f in field_points
                             for w in wavelengths])
+    return _refs_from(system, initial_material, final_material, nf, wavelengths, spot_summary, chief, device)
+
+
+def _refs_from(system, initial_material, final_material, nf, wavelengths, spot_summary, chief, device):
+    """(nf, n_wavelengths, 8) references: the summary's centroids, the chief rays (host, one per group, field-major)
+    traced through the ordinary planes='final' path, and kf."""
+    import torch
+    nw = wavelengths.size
+    refs = np.empty((nf, nw, 8))
+    refs[..., 0:3] = np.asarray(spot_summary["centroid"], dtype=np.float64).reshape(nf, nw, 3)
     fin = system.ray_trace(torch.from_numpy(chief).to(torch.device(device)), initial_material, final_material,
                            planes="final")[-1].cpu().numpy().reshape(nf, nw, 8)
     refs[..., 3:7] = fin[..., 3:7]
@@ -389,8 +404,9 @@ def wavefront_sweep(system, initial_material, final_material, field_points, wave
                               center_ray=center_ray, device=device, theta_max=theta_max, n_thetas=n_thetas,
                               nphis=nphis, groups_per_batch=groups_per_batch, devices=devices)
     refs = _wave_refs(refs, (field_points.shape[0], wavelengths.size, 8))
-    return _sweep(_wave_mode(refs), system, initial_material, final_material, field_points, wavelengths, theta_max,
-                  n_thetas, nphis, center_ray, device, "float64", groups_per_batch, fused, devices)
+    return _sweep(_wave_mode(refs), system, initial_material, final_material,
+                  _fan_source(field_points, wavelengths, theta_max, n_thetas, nphis, center_ray), device, "float64",
+                  groups_per_batch, fused, devices)
 
 
 def _grid(field_points, wavelengths):
@@ -398,42 +414,123 @@ def _grid(field_points, wavelengths):
     return np.atleast_2d(np.asarray(field_points, dtype=float)), np.atleast_1d(np.asarray(wavelengths, dtype=float))
 
 
-def _sweep(mode, system, initial_material, final_material, field_points, wavelengths, theta_max, n_thetas, nphis,
-           center_ray, device, dtype, groups_per_batch, fused, devices):
-    """What the three public sweeps share: the argument checks, the lowered system, one of the two drivers, the
-    timing dict and the mode's host summary."""
+# A sweep source is what differs between the fans and the collimated beams, as the drivers read it:
+#   nf, nw, per     fields (field points, or beams), wavelengths and rays per group; group = field * nw + wavelength
+#   wavelengths     (nw,) float64
+#   suffix          of the fused C entry point's name after the mode's
+#   head()          -> head(b0, b1): the entry's arguments from group_params up to the mode's tail, for groups
+#                   [b0, b1), and the host arrays they point into (to be kept until the call returns)
+#   into(buf, g)    unfused: group g's rays written into the device buffer ``buf``
+def _fan_source(field_points, wavelengths, theta_max, n_thetas, nphis, center_ray):
+    """The point-source fans of the four sweeps: ``get_ray_fan(field, theta_max, n_thetas, wavelength, nphis,
+    center_ray)`` per (field point, wavelength)."""
     if np.linalg.norm(np.asarray(center_ray, dtype=float)) != 1:
         raise ValueError("center_ray must be a unit vector")
+    field_points, wavelengths = _grid(field_points, wavelengths)
+    nf, nw = field_points.shape[0], wavelengths.size
+
+    def head():
+        from .raytrace import _fan_tables
+        c = np.array(center_ray)
+        enx, eny, tcs, pcs = _fan_tables(float(theta_max), int(n_thetas), int(nphis), tuple(c.tolist()), c.dtype.str)
+        params = np.empty((nf * nw, 4))
+        params[:, 0:3] = np.repeat(field_points, nw, axis=0)          # group = field * nw + wavelength
+        params[:, 3] = np.tile(wavelengths, nf)
+        vec = [np.ascontiguousarray(np.asarray(v, dtype=np.float64).ravel()) for v in (c, enx, eny)]
+
+        def args(b0, b1):
+            gp = np.ascontiguousarray(params[b0:b1])
+            return (gp.ctypes.data, int(n_thetas), int(nphis), vec[0].ctypes.data, vec[1].ctypes.data,
+                    vec[2].ctypes.data, tcs.ctypes.data, pcs.ctypes.data), (gp, vec, tcs, pcs)
+        return args
+
+    def into(buf, g):
+        from .raytrace import fan_into
+        fan_into(buf, field_points[g // nw], theta_max, n_thetas, wavelengths[g % nw], nphis, center_ray)
+
+    return SimpleNamespace(nf=nf, nw=nw, per=n_thetas * nphis, wavelengths=wavelengths, suffix="", head=head,
+                           into=into)
+
+
+def _beams(normals, pt):
+    """(n_fields, 3) float64 unit normals and one point per field from ``normals`` and ``pt`` (one point, or one per
+    field); the reference's ``ValueError`` for a normal that is not unit to 1e-12."""
+    normals = np.atleast_2d(np.asarray(normals, dtype=float))
+    if normals.ndim != 2 or normals.shape[1] != 3:
+        raise ValueError("normals must have shape (n_fields, 3)")
+    if (np.abs(np.linalg.norm(normals, axis=1) - 1) > 1e-12).any():
+        raise ValueError("normal must be a normalized vector")
+    pt = np.asarray(pt, dtype=float)
+    if pt.shape == (3,):
+        pt = np.broadcast_to(pt, normals.shape)
+    if pt.shape != normals.shape:
+        raise ValueError("pt must be one point (3,) or one per field (n_fields, 3)")
+    return normals, np.ascontiguousarray(pt)
+
+
+def _beam_source(normals, wavelengths, displacement_max, n_disps, nphis, phi_start, pt):
+    """The collimated beams of the four collimated sweeps: ``get_collimated_rays(pt, displacement_max, n_disps,
+    wavelength, nphis, phi_start, normal)`` per (beam, wavelength), a beam being a field direction ``normal`` and
+    its point ``pt``.  n1 / n2 per beam come from the lines ``get_collimated_rays`` itself runs."""
+    normals, pts = _beams(normals, pt)
+    wavelengths = np.atleast_1d(np.asarray(wavelengths, dtype=float))
+    nf, nw = normals.shape[0], wavelengths.size
+
+    def head():
+        from .raytrace import _collimated_frame, _collimated_tables
+        offs, pcs = _collimated_tables(displacement_max, int(n_disps), int(nphis), phi_start)
+        frames = np.array([np.concatenate([np.asarray(v, dtype=np.float64) for v in _collimated_frame(n)])
+                           for n in normals])
+        frames = np.ascontiguousarray(np.repeat(frames, nw, axis=0))
+        params = np.empty((nf * nw, 4))
+        params[:, 0:3] = np.repeat(pts, nw, axis=0)
+        params[:, 3] = np.tile(wavelengths, nf)
+
+        def args(b0, b1):
+            gp, fr = np.ascontiguousarray(params[b0:b1]), np.ascontiguousarray(frames[b0:b1])
+            return (gp.ctypes.data, fr.ctypes.data, int(n_disps), int(nphis), offs.ctypes.data,
+                    pcs.ctypes.data), (gp, fr, offs, pcs)
+        return args
+
+    def into(buf, g):
+        from .raytrace import collimated_into
+        collimated_into(buf, pts[g // nw], displacement_max, n_disps, wavelengths[g % nw], nphis, phi_start,
+                        normals[g // nw])
+
+    return SimpleNamespace(nf=nf, nw=nw, per=n_disps * nphis, wavelengths=wavelengths, suffix="_collimated",
+                           head=head, into=into, normals=normals, pts=pts)
+
+
+def _sweep(mode, system, initial_material, final_material, source, device, dtype, groups_per_batch, fused, devices):
+    """What the public sweeps share: the argument checks, the lowered system, one of the two drivers, the timing
+    dict and the mode's host summary.  ``source`` says what a group's rays are (:func:`_fan_source`,
+    :func:`_beam_source`)."""
     if devices is not None and not fused:
         raise ValueError("devices= needs the fused sweep")
     import torch
     dev = torch.device(device)
     tdt = torch.float64 if dtype in ("float64", np.float64) else torch.float32
-    field_points, wavelengths = _grid(field_points, wavelengths)
+    wavelengths = source.wavelengths
     mats = [initial_material] + list(system.materials) + [final_material]
     # tabulated materials are lowered at the wavelengths the kernels see: the group's wavelength rounded to the
     # storage type (a float32 sweep's rays carry float32 wavelengths, and the table lookup matches exactly)
     keys = wavelengths if tdt == torch.float64 else wavelengths.astype(np.float32).astype(np.float64)
     low = E.lower(system.surfaces, mats, lambda: np.unique(keys), C.RTPB_F64 if tdt == torch.float64 else C.RTPB_F32)
     S = len(system.surfaces)
-    fan = (field_points, wavelengths, theta_max, n_thetas, nphis, center_ray)
     if fused:
         devs = [dev] if devices is None else [torch.device("cuda", int(d)) for d in devices]
-        arrays, dt, extra = _sweep_fused(mode, low, S, *fan, devs, groups_per_batch)
+        arrays, dt, extra = _sweep_fused(mode, low, S, source, devs, groups_per_batch)
     else:
-        arrays, dt, extra = _sweep_unfused(mode, low, S, *fan, dev, tdt, groups_per_batch)
-    nf, nw = field_points.shape[0], wavelengths.size
-    rays = nf * nw * n_thetas * nphis
+        arrays, dt, extra = _sweep_unfused(mode, low, S, source, dev, tdt, groups_per_batch)
+    nf, nw = source.nf, source.nw
+    rays = nf * nw * source.per
     return mode.finish(nf, nw, *arrays), {"seconds": dt, "rays": rays, "ray_surface_per_s": rays * S / dt, **extra}
 
 
-def _sweep_unfused(mode, low, S, field_points, wavelengths, theta_max, n_thetas, nphis, center_ray, dev, tdt,
-                   groups_per_batch):
-    """Fan generation -> trace planes='final' -> ``mode.plane`` per batch of groups, through HBM buffers."""
+def _sweep_unfused(mode, low, S, source, dev, tdt, groups_per_batch):
+    """Ray generation -> trace planes='final' -> ``mode.plane`` per batch of groups, through HBM buffers."""
     import torch
-    from .raytrace import fan_into
-    nw = wavelengths.size
-    G, per = field_points.shape[0] * nw, n_thetas * nphis
+    G, per = source.nf * source.nw, source.per
     if groups_per_batch is None:
         groups_per_batch = max(1, min(G, (1 << 27) // per))     # ~128M rays in flight
     sel = E.resolve_planes("final", S)
@@ -444,9 +541,8 @@ def _sweep_unfused(mode, low, S, field_points, wavelengths, theta_max, n_thetas,
     t0 = time.perf_counter()
     for b0 in range(0, G, groups_per_batch):
         nb = min(groups_per_batch, G - b0)
-        for k in range(nb):                      # generate each fan in place in the batch buffer
-            fan_into(rays[k * per:(k + 1) * per], field_points[(b0 + k) // nw], theta_max, n_thetas,
-                     wavelengths[(b0 + k) % nw], nphis, center_ray)
+        for k in range(nb):                      # generate each group in place in the batch buffer
+            source.into(rays[k * per:(k + 1) * per], b0 + k)
         m = nb * per
         E.trace_device(low, rays[:m], sel, out=out[:, :m])
         for a, t in zip(arrays, mode.plane(out[0, :m], per, b0, nb)):
@@ -486,20 +582,12 @@ def _sweep_plan(nf, nw, per, n_devices, groups_per_batch=None, ncols=None):
     return groups_per_batch, bounds, launches
 
 
-def _sweep_fused(mode, low, S, field_points, wavelengths, theta_max, n_thetas, nphis, center_ray, devs,
-                 groups_per_batch):
-    """One ``mode.entry`` kernel per batch of groups (generation, trace and reduction: no rays touch HBM), the
-    groups split over ``devs`` as :func:`_sweep_plan` says."""
+def _sweep_fused(mode, low, S, source, devs, groups_per_batch):
+    """One ``mode.entry`` kernel (the source's variant of it) per batch of groups (generation, trace and reduction:
+    no rays touch HBM), the groups split over ``devs`` as :func:`_sweep_plan` says."""
     import torch
-    from .raytrace import _fan_tables
-    c = np.array(center_ray)
-    enx, eny, tcs, pcs = _fan_tables(float(theta_max), int(n_thetas), int(nphis), tuple(c.tolist()), c.dtype.str)
-    nf, nw = field_points.shape[0], wavelengths.size
-    params = np.empty((nf * nw, 4))
-    params[:, 0:3] = np.repeat(field_points, nw, axis=0)          # group = field * nw + wavelength
-    params[:, 3] = np.tile(wavelengths, nf)
-    per = n_thetas * nphis
-    vec = [np.ascontiguousarray(np.asarray(v, dtype=np.float64).ravel()) for v in (c, enx, eny)]
+    head = source.head()
+    nf, nw, per = source.nf, source.nw, source.per
     groups_per_batch, bounds, launches = _sweep_plan(nf, nw, per, len(devs), groups_per_batch, mode.ncols)
     work = []          # per device: its groups, the mode's outputs and argument tail, an event pair, its stream
     for (g0, g1), dev in zip(bounds, devs):
@@ -509,16 +597,15 @@ def _sweep_fused(mode, low, S, field_points, wavelengths, theta_max, n_thetas, n
     for dev in devs:
         torch.cuda.synchronize(dev)
     t0 = time.perf_counter()
-    sweep = getattr(C.lib(), mode.entry)
+    sweep = getattr(C.lib(), mode.entry + source.suffix)
     with E.plan_ref(low) as plan:
         for *_, ev, st in work:
             ev[0].record(st)
         for slot, b0, b1 in launches:
             dev, _, _, tail, _, st = work[slot]
-            gp = np.ascontiguousarray(params[b0:b1])
-            C.check(sweep(plan, dev.index or 0, b1 - b0, gp.ctypes.data, int(n_thetas), int(nphis),
-                          vec[0].ctypes.data, vec[1].ctypes.data, vec[2].ctypes.data, tcs.ctypes.data,
-                          pcs.ctypes.data, *tail(b0, b1), st.cuda_stream))
+            args, keep = head(b0, b1)
+            C.check(sweep(plan, dev.index or 0, b1 - b0, *args, *tail(b0, b1), st.cuda_stream))
+            del keep
         for *_, ev, st in work:
             ev[1].record(st)
         shards = [[t[:n] for t in outputs] for _, n, outputs, *_ in work]
@@ -647,8 +734,9 @@ def image_sweep(system, initial_material, final_material, field_points, waveleng
     field_points, wavelengths = _grid(field_points, wavelengths)
     if windows.shape != (field_points.shape[0], wavelengths.size, 4):
         raise ValueError("windows must have shape (n_fields, n_wavelengths, 4)")
-    return _sweep(_image_mode(windows, nx, ny), system, initial_material, final_material, field_points, wavelengths,
-                  theta_max, n_thetas, nphis, center_ray, device, dtype, groups_per_batch, fused, devices)
+    return _sweep(_image_mode(windows, nx, ny), system, initial_material, final_material,
+                  _fan_source(field_points, wavelengths, theta_max, n_thetas, nphis, center_ray), device, dtype,
+                  groups_per_batch, fused, devices)
 
 
 def _image_mode(windows, nx, ny):
@@ -677,6 +765,96 @@ def _image_mode(windows, nx, ny):
         hbm_bytes=lambda per, n: n * (ny * nx + 1) * 4 * 2,
         host=lambda G: (np.zeros((G, ny, nx), dtype=np.int32), np.zeros(G, dtype=np.int32)),
         plane=lambda out, per, b0, nb: spot_image_raw(out, per, win[b0:b0 + nb], (nx, ny)))
+
+
+def collimated_spot_sweep(system, initial_material, final_material, normals, wavelengths, displacement_max, n_disps,
+                          nphis=1, phi_start=0., pt=(0, 0, 0), device="cuda:0", dtype="float64",
+                          groups_per_batch=None, fused=True, devices=None):
+    """Spot diagrams of an object at infinity, for every (field direction, wavelength): a
+    ``get_collimated_rays(pt, displacement_max, n_disps, wavelength, nphis, phi_start, normal)`` beam per group,
+    generated, traced (final plane only) and reduced on the GPU as :func:`spot_sweep` does for fans.
+
+    ``normals`` (n_fields, 3) are the beams' directions, unit to 1e-12 (else the reference's ``ValueError``);
+    ``pt`` is one point for all of them or one per field.  ``fused=True`` runs ``rtpb_spot_sweep_collimated``, one
+    kernel per batch of groups; ``fused=False`` runs ``rtpb_collimated_rays_tables`` -> ``rtpb_trace``
+    planes='final' -> ``rtpb_spot_stats`` through HBM buffers; both give bit-identical statistics.  The other
+    keywords, the summary (arrays shaped (n_fields, n_wavelengths, ...)) and the timing dict are
+    :func:`spot_sweep`'s.  The statistics are those of the reference's bundle, centre-heavy as it is: ``nphis`` rays
+    on each of ``n_disps`` rings, the rings' radii evenly spaced."""
+    return _sweep(_SPOT, system, initial_material, final_material,
+                  _beam_source(normals, wavelengths, displacement_max, n_disps, nphis, phi_start, pt), device, dtype,
+                  groups_per_batch, fused, devices)
+
+
+def collimated_focus_sweep(system, initial_material, final_material, normals, wavelengths, displacement_max, n_disps,
+                           nphis=1, phi_start=0., pt=(0, 0, 0), device="cuda:0", dtype="float64",
+                           groups_per_batch=None, fused=True, devices=None, require_image_plane=True):
+    """Through-focus analysis of :func:`collimated_spot_sweep`'s beams: :func:`focus_sweep` with that source
+    (``rtpb_focus_sweep_collimated``, or unfused through ``rtpb_focus_stats``; bit-identical)."""
+    _require_image_plane(system, require_image_plane)
+    return _sweep(_FOCUS, system, initial_material, final_material,
+                  _beam_source(normals, wavelengths, displacement_max, n_disps, nphis, phi_start, pt), device, dtype,
+                  groups_per_batch, fused, devices)
+
+
+def collimated_image_sweep(system, initial_material, final_material, normals, wavelengths, displacement_max, n_disps,
+                           nphis=1, phi_start=0., pt=(0, 0, 0), device="cuda:0", dtype="float64", bins=64,
+                           windows=None, sigmas=4.0, groups_per_batch=None, fused=True, devices=None):
+    """Spot-diagram images of :func:`collimated_spot_sweep`'s beams: :func:`image_sweep` with that source
+    (``rtpb_image_sweep_collimated``, or unfused through ``rtpb_spot_image``; identical counts).  With
+    ``windows=None`` a :func:`collimated_spot_sweep` of the same beams chooses them."""
+    nx, ny = _bins(bins)
+    beam = (normals, wavelengths, displacement_max, n_disps, nphis, phi_start, pt)
+    if windows is None:
+        spot, _ = collimated_spot_sweep(system, initial_material, final_material, *beam, device=device, dtype=dtype,
+                                        groups_per_batch=groups_per_batch, fused=fused, devices=devices)
+        windows = auto_image_windows(spot, (nx, ny), sigmas)
+    windows = np.ascontiguousarray(windows, dtype=np.float64)
+    source = _beam_source(*beam)
+    if windows.shape != (source.nf, source.nw, 4):
+        raise ValueError("windows must have shape (n_fields, n_wavelengths, 4)")
+    return _sweep(_image_mode(windows, nx, ny), system, initial_material, final_material, source, device, dtype,
+                  groups_per_batch, fused, devices)
+
+
+def collimated_wavefront_refs(system, initial_material, final_material, normals, wavelengths, pt=(0, 0, 0),
+                              spot_summary=None, device="cuda:0", **beam_kw):
+    """The references (n_fields, n_wavelengths, 8) = (C0, d0, p0, kf) of :func:`collimated_wavefront_sweep`'s groups,
+    as :func:`wavefront_refs` builds the fans': C0 the group's spot centroid, from ``spot_summary`` or from the
+    :func:`collimated_spot_sweep` that ``beam_kw`` (``displacement_max``, ``n_disps``, ``nphis``, ``phi_start``;
+    also ``groups_per_batch``, ``devices``) describes; d0 and p0 the final direction and phase of the beam's chief
+    ray, ``get_collimated_rays(pt, 0, 1, wavelength, normal=normal)``, traced through the ordinary
+    ``planes='final'`` path; kf = final_material.n(wavelength) / wavelength."""
+    from .raytrace import get_collimated_rays
+    normals, pts = _beams(normals, pt)
+    wavelengths = np.atleast_1d(np.asarray(wavelengths, dtype=float))
+    if spot_summary is None:
+        spot_summary, _ = collimated_spot_sweep(system, initial_material, final_material, normals, wavelengths,
+                                                pt=pts, device=device, **beam_kw)
+    chief = np.concatenate([get_collimated_rays(p, 0, 1, w, normal=n) for p, n in zip(pts, normals)
+                            for w in wavelengths])
+    return _refs_from(system, initial_material, final_material, normals.shape[0], wavelengths, spot_summary, chief,
+                      device)
+
+
+def collimated_wavefront_sweep(system, initial_material, final_material, normals, wavelengths, displacement_max,
+                               n_disps, nphis=1, phi_start=0., pt=(0, 0, 0), device="cuda:0", refs=None,
+                               groups_per_batch=None, fused=True, devices=None, dtype="float64"):
+    """Wavefront analysis of :func:`collimated_spot_sweep`'s beams: :func:`wavefront_sweep` with that source
+    (``rtpb_wavefront_sweep_collimated``, or unfused through ``rtpb_wavefront_stats``; bit-identical).  With
+    ``refs=None`` :func:`collimated_wavefront_refs` builds the references.  float64 only."""
+    if dtype not in ("float64", np.float64):
+        raise ValueError("wavefront_sweep is float64 only: a float32 phase of 1e4 ... 1e7 rad has an ulp of a "
+                         "milliradian to a radian")
+    source = _beam_source(normals, wavelengths, displacement_max, n_disps, nphis, phi_start, pt)
+    if refs is None:
+        refs = collimated_wavefront_refs(system, initial_material, final_material, source.normals,
+                                         source.wavelengths, pt=source.pts, device=device,
+                                         displacement_max=displacement_max, n_disps=n_disps, nphis=nphis,
+                                         phi_start=phi_start, groups_per_batch=groups_per_batch, devices=devices)
+    refs = _wave_refs(refs, (source.nf, source.nw, 8))
+    return _sweep(_wave_mode(refs), system, initial_material, final_material, source, device, "float64",
+                  groups_per_batch, fused, devices)
 
 
 class GridInterpolator:

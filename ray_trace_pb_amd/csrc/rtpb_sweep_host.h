@@ -23,13 +23,18 @@ struct SweepRows {
 // Groups of one field point (the bit patterns of x, y, z; group_params holds x, y, z, wavelength per group) go into
 // bundle rows of rays_per_lane ... max_bundle groups, multiples of rays_per_lane (see sweep_kernel); a point's
 // leftover groups are single rows.  Without bundles (they need the host-evaluated media) every group is single.
+// A collimated-beam sweep passes its groups' frames (normal, n1, n2: 9 doubles per group): a row's groups then share
+// the whole beam, the bit patterns of the point and of the frame together -- fields at one point that differ in
+// their normal, the ordinary case, never share a row.  Without frames the key's other words are 0, and the rows and
+// their order are those of the point alone.
 inline SweepRows plan_sweep_rows(const double* group_params, int64_t n_groups, bool bundles_allowed,
-                                 int rays_per_lane, int max_bundle) {
+                                 int rays_per_lane, int max_bundle, const double* frames = nullptr) {
     SweepRows r;
-    std::map<std::array<uint64_t, 3>, std::vector<int32_t>> by_point;   // field point (bit patterns) -> groups
+    std::map<std::array<uint64_t, 12>, std::vector<int32_t>> by_point;   // source (bit patterns) -> groups
     for (int64_t gi = 0; gi < n_groups; ++gi) {
-        std::array<uint64_t, 3> key;
+        std::array<uint64_t, 12> key{};
         std::memcpy(key.data(), group_params + 4 * gi, 3 * sizeof(double));
+        if (frames) std::memcpy(key.data() + 3, frames + 9 * gi, 9 * sizeof(double));
         if (bundles_allowed) by_point[key].push_back(static_cast<int32_t>(gi));
         else r.singles.push_back(static_cast<int32_t>(gi));
     }
@@ -73,17 +78,19 @@ inline void fill_group_media(const rtpb::DevMaterial<double>* mats, size_t n_mat
 // The one upload of a sweep, as byte offsets (for the pinned host copy and the device block alike): the trig tables
 // ((cos, sin) pairs: thetas, then phis) at 0, the group parameters, the media table (media_doubles per group, or 0),
 // the image or wavefront sweep's block (head_doubles for its header, then per_group doubles per group: the image's
-// windows, 4, or the wavefront references, 8; nothing for the other sweeps), then the int32 index block (bundles,
-// singles, rows).
+// windows, 4, or the wavefront references, 8; nothing for the other sweeps), the beams' frames (frame_doubles per
+// group: normal, n1, n2; 0 for fans), then the int32 index block (bundles, singles, rows).  A beam sweep's tables
+// are the phis' pairs and then its offsets as plain doubles: it passes ceil(n_disps / 2) pair slots for them.
 struct SweepLayout {
-    size_t grp, gn, img, win, idx, bytes;
+    size_t grp, gn, img, win, frm, idx, bytes;
     SweepLayout(int64_t n_thetas, int64_t nphis, int64_t n_groups, size_t media_doubles, size_t n_idx,
-                size_t head_doubles = 0, size_t per_group = 4) {
+                size_t head_doubles = 0, size_t per_group = 4, size_t frame_doubles = 0) {
         grp = size_t(n_thetas + nphis) * 2 * sizeof(double);
         gn = grp + size_t(4 * n_groups) * sizeof(double);
         img = gn + size_t(n_groups) * media_doubles * sizeof(double);
         win = img + head_doubles * sizeof(double);
-        idx = win + (head_doubles ? per_group * size_t(n_groups) * sizeof(double) : 0);
+        frm = win + (head_doubles ? per_group * size_t(n_groups) * sizeof(double) : 0);
+        idx = frm + frame_doubles * size_t(n_groups) * sizeof(double);
         bytes = idx + n_idx * sizeof(int32_t);
     }
 };

@@ -1,0 +1,647 @@
+// rtpb_sweep_kernel.h -- the fused spot-diagram / through-focus / spot-image / wavefront sweep:
+// generate + trace + reduce in one kernel.  The kernel and its host driver are templates on the SOURCE of a group's
+// rays; each source's entry points instantiate them in a translation unit of their own, so the units compile side by
+// side: rtpb_sweep.hip (point-source fans: rtpb_spot_sweep, rtpb_focus_sweep, rtpb_image_sweep, rtpb_wavefront_sweep)
+// and rtpb_sweep_beam.hip (collimated beams: the same four with _collimated).  What the sweep shares with the plane
+// kernels (the statistics, the image's contribution rule) is rtpb_stats.h, the host arithmetic of a call (row
+// planning, media table, upload layout) rtpb_sweep_host.h.
+#pragma once
+
+#include "rtpb_stats.h"
+#include "rtpb_sweep_host.h"
+
+using namespace rtpbi;
+
+namespace {
+
+// Spot-diagram sweep, fused (C5).  Group g is the fan get_ray_fan(pt_g, ..., wl_g)
+// (RT:45-96, same per-ray arithmetic as ray_fan_kernel, angles from the caller's tables); each ray is
+// generated in registers, traced through the plan keeping only its final state, and reduced into the
+// same 256-ray tile partials as spot_partial_kernel.  spot_final_kernel then produces statistics
+// bit-identical to generating, tracing (planes='final') and reducing separately -- without the
+// 3 x 64 B per ray of HBM traffic and the launches in between.
+//
+// Collimated-beam sweep (kSrcBeam).  Group g is the beam get_collimated_rays(pt_g, ..., wl_g, normal_g) (RT:99-161,
+// the per-ray arithmetic of collimated_kernel, offsets and angles from the caller's tables): ray k = idisp * nphis +
+// iphi, position pt + n1 (off cos phi) + n2 (off sin phi), direction normal, phase 0.  Only the generator differs:
+// the index split, the trace and the reductions are the fan's, with the two tables in each other's place -- the
+// table indexed by the remainder (the fan's thetas, the beam's phis) first, the one indexed by the quotient second.
+constexpr int kSrcFan = 0, kSrcBeam = 1;
+constexpr int kFrame = 9;               // a beam's frame: normal, n1, n2
+struct SweepImage;
+struct SweepWave;
+struct SweepArgs {
+    const DevSurface<double>* __restrict__ surf;
+    const DevMaterial<double>* __restrict__ mats;
+    const double* __restrict__ table;
+    // fan: (cos, sin) of the thetas [n_thetas], then of the phis [nphis].  Beam: (cos, sin) of the phis [n_thetas],
+    // then the offsets as plain doubles [nphis]
+    const double2* __restrict__ tab;
+    const double* __restrict__ grp;     // per group: x, y, z, wavelength
+    const double* __restrict__ gn;      // FEAT bit 4: per group, n of the S+1 materials at its wavelength, then
+                                        // per surface n_s / n_s+1, 1 / n_s+1 and host_rcp_ok(n_s+1) (0 / 1)
+    const int32_t* __restrict__ gidx;   // single rows: the group of block row y; bundle rows: see rows
+    const int32_t* __restrict__ rows;   // bundle rows: (offset into gidx, number of groups) of block row y
+    union {
+        double* __restrict__ partials;              // spot and focus statistics
+        const SweepImage* __restrict__ image;       // image mode
+        const SweepWave* __restrict__ wave;         // wavefront mode
+    };
+    // ray j of a group: j % n_thetas indexes the first table, j / n_thetas the second (the beam's n_thetas is its
+    // nphis, its nphis its n_disps)
+    int64_t n_thetas, nphis, gsize, tiles;
+    union {
+        struct {
+            double c[3], ex[3], ey[3];                  // fan: the axis and its basis, one for the call
+        };
+        const double* __restrict__ frm;                 // beam: per group normal, n1, n2 (kFrame doubles)
+    };
+    int32_t nsurf;
+    // j / n_thetas as (j * nt_mul) >> nt_shift for j < 2^31 (nt_mul != 0, see sweep_divisor), else int64 division
+    uint32_t nt_mul;
+    int32_t nt_shift;
+};
+
+// The image mode's outputs: they ride in the sweep's one upload, followed by the groups' windows (SweepLayout::img
+// and win), so the kernels' argument block keeps its size and layout and the statistics instantiations stay the
+// code they were.
+struct SweepImage {
+    int32_t* image;      // [n_groups][ny][nx]
+    int32_t* outside;    // [n_groups]
+    int32_t nx, ny;
+};
+static_assert(sizeof(SweepImage) % sizeof(double) == 0, "the windows follow it");
+
+// The wavefront mode's block of the upload, in the same place: where the tile partials go, followed by the groups'
+// references (kWaveRef doubles each, rtpb_stats.h)
+struct SweepWave {
+    double* partials;
+};
+static_assert(sizeof(SweepWave) == sizeof(double), "the references follow it");
+
+template <typename TS>
+__device__ __forceinline__ double stored(double v) { return static_cast<double>(static_cast<TS>(v)); }
+
+// kSweepRays rays per lane, traced side by side: each surface runs one surface_step instantiation per ray in one
+// straight-line region (inside one run of equal surface codes), so independent dependency chains interleave (two:
+// -6 % vs one ray per lane); each ray's 256-ray tile is reduced separately, with the same tree as
+// spot_partial_kernel.  Single rows: block b covers tiles kSweepRays*b ... of one group.
+// BUNDLE rows (round 5): up to kMaxBundle groups of one field point (a multiple of kSweepRays: 2, 4, 6 or 8) -- the same
+// fan at several wavelengths.  Block b covers tile b of every group of the bundle: each lane generates its ray once
+// and, when the first surface refracts (Flat / Sphere), runs the part of that surface that does not depend on the
+// wavelength once (intersection, normal, front-side and on-surface tests, tangent basis: surface_step_pair's split)
+// into LDS; then, kSweepRays groups at a time, it refracts the shared state with each group's Snell ratio
+// (snell_apply) and traces those rays side by side through the other surfaces.  A field point's leftover groups run
+// in single rows.
+#ifndef RTPB_SWEEP_RPL
+#define RTPB_SWEEP_RPL 2
+#endif
+constexpr int kSweepRays = RTPB_SWEEP_RPL;         // rays per lane (tiles per block)
+// groups per bundle row: a multiple of kSweepRays (each pass of a row traces kSweepRays of its groups)
+constexpr int kMaxBundle = 8 - 8 % kSweepRays;
+constexpr int kStateRows = 11;                     // bundle state per lane: x y z, N, c, c . d, N . d
+
+// Occupancy: held to >= 6 waves per SIMD (<= 80 VGPRs).  Round 3 measured 7 best (2.4 % faster than the natural
+// 83 VGPRs / 5 waves, experiments/ab_sweep_wpe*.log); with round 4's lens instantiation, fixup-free quotients and
+// x x + y y carry the sweep runs 0.379 s at 6, 0.384 s at 7, 0.401 s at 8 (profiles/r04/e/, one process,
+// bit-identical); round 5's pair rows: 0.345 s at 6, 0.348 s at 5, 0.353 s at 7 (profiles/r05/g).  Bundle rows hold
+// 26 KB of LDS per block (the state, and the reduction two statistics at a time), so 6 blocks fit a CU's 160 KB.
+// RTPB_SWEEP_WPE overrides it (A/B builds).
+#ifndef RTPB_SWEEP_WPE
+#define RTPB_SWEEP_WPE 6
+#endif
+// The wavefront instantiations run the trace kernel's full step with the phase and the whole direction alive to the
+// end: RTPB_WAVE_WPE waves per SIMD for them (the registers, scratch and LDS at each setting)
+#ifndef RTPB_WAVE_WPE
+#define RTPB_WAVE_WPE 4
+#endif
+#define RTPB_SWEEP_ATTR(NS) \
+    __attribute__((amdgpu_waves_per_eu((NS) == kWaveStats ? RTPB_WAVE_WPE : RTPB_SWEEP_WPE, 8)))
+// An optimisation fence on three per-lane values: the compiler moves no computation on them across it
+#if defined(__HIP_DEVICE_COMPILE__)
+#define RTPB_PIN3(a, b, c) asm volatile("" : "+v"(a), "+v"(b), "+v"(c))
+#else
+#define RTPB_PIN3(a, b, c) ((void)0)
+#endif
+// NS = kStats: the spot statistics.  NS = kFocusStats (rtpb_focus_sweep): focus_ray of the final state, so the whole
+// final direction stays alive to the end.  kPosOnly leaves no part of it unfinished on any surface kind -- snell_apply,
+// reflect and lens_step compute dx, dy and dz in full whatever the mode, and a killed row is all NaN (the mode only
+// skips the position fill after a NaN direction and the at-plane) -- so the last surface runs the same step as the
+// others.  Single rows reduce eight of the sixteen statistics at a time (16 KB of LDS), bundle rows two as before.
+// NS = kImageStats (rtpb_image_sweep): no statistics, each counted ray goes into its group's image instead
+// (image_bin, wave_image_add); the rule of which rays count is the spot statistics', and there are no red tiles.
+// NS = kWaveStats (rtpb_wavefront_sweep; float64, single rows only): wave_ray of the final state against the group's
+// reference.  The phase is wanted, so the steps are the final-plane trace kernel's (kNoAt: the full semantics of
+// every surface, its roots and square roots included, and no carried x x + y y) and the final state is the one
+// rtpb_trace stores, phase and all; eight of the fifteen statistics at a time.
+constexpr int kImageStats = 0;
+// SRC = kSrcBeam: the generator of a collimated beam; a bundle row's groups share the beam (pt and frame) as the
+// fan's share the field point, and everything after the generator is the same code.
+template <typename TS, int FEAT, bool BUNDLE, int NS = kStats, int SRC = kSrcFan>
+__global__ __launch_bounds__(kBlock) RTPB_SWEEP_ATTR(NS) void sweep_kernel(SweepArgs a) {
+    static_assert(SRC == kSrcFan || SRC == kSrcBeam, "a fan or a beam");
+    static_assert(!BUNDLE || (FEAT & 16) != 0, "bundles: host-evaluated media");
+    static_assert(NS == kStats || NS == kFocusStats || NS == kImageStats || NS == kWaveStats,
+                  "spot, focus or wavefront statistics, or the image");
+    constexpr bool kWave = NS == kWaveStats;
+    static_assert(!kWave || (!BUNDLE && sizeof(TS) == 8), "wavefront: float64, single rows");
+    constexpr int kRedRows = NS == kImageStats ? 1 : BUNDLE ? 2 : NS == kStats ? kStats : 8;
+    __shared__ double red[kRedRows][kBlock];
+    __shared__ double state[BUNDLE ? kStateRows : 1][kBlock];
+    const int tid = threadIdx.x;
+    auto gen = [&](int64_t j, int64_t g) {
+        const double* gp = a.grp + 4 * g;
+        const int64_t jj = j < a.gsize ? j : 0;
+        int64_t it, ip;
+        if (a.nt_mul != 0) {
+            const uint32_t x = static_cast<uint32_t>(jj);
+            const uint32_t qt = static_cast<uint32_t>((uint64_t(x) * a.nt_mul) >> a.nt_shift);
+            ip = qt;
+            it = x - qt * static_cast<uint32_t>(a.n_thetas);
+        } else {
+            it = jj % a.n_thetas;
+            ip = jj / a.n_thetas;
+        }
+        Ray<double> r;
+        if constexpr (SRC == kSrcBeam) {
+            // collimated_kernel's products in its association; the frame is the block's, so scalar loads
+            const double* fr = a.frm + kFrame * g;
+            const double2 ph = a.tab[it];
+            const double oo = reinterpret_cast<const double*>(a.tab + a.n_thetas)[ip];
+            const double oc = oo * ph.x, os = oo * ph.y;
+            r.x = stored<TS>(gp[0] + fr[3] * oc + fr[6] * os);
+            r.y = stored<TS>(gp[1] + fr[4] * oc + fr[7] * os);
+            r.z = stored<TS>(gp[2] + fr[5] * oc + fr[8] * os);
+            r.dx = stored<TS>(fr[0]); r.dy = stored<TS>(fr[1]); r.dz = stored<TS>(fr[2]);
+        } else {
+            const double2 t = a.tab[it], ph = a.tab[a.n_thetas + ip];
+            const double ct = t.x, st = t.y, cp = ph.x, sp = ph.y;
+            r.x = stored<TS>(gp[0]); r.y = stored<TS>(gp[1]); r.z = stored<TS>(gp[2]);
+            r.dx = stored<TS>(a.c[0] * ct + a.ex[0] * cp * st + a.ey[0] * sp * st);
+            r.dy = stored<TS>(a.c[1] * ct + a.ex[1] * cp * st + a.ey[1] * sp * st);
+            r.dz = stored<TS>(a.c[2] * ct + a.ex[2] * cp * st + a.ey[2] * sp * st);
+        }
+        r.ph = 0.0;
+        r.wl = stored<TS>(gp[3]);
+        return r;
+    };
+    const cptr<DevSurface<double>> surf = (cptr<DevSurface<double>>)(a.surf);
+    const cptr<DevMaterial<double>> mats = (cptr<DevMaterial<double>>)(a.mats);
+    const cptr<double> table = (cptr<double>)(a.table);
+    int64_t grp[kSweepRays], tile[kSweepRays];
+    Ray<double> r[kSweepRays];
+    // one wavelength per group: with FEAT bit 4 the host has evaluated every material at it (the kernel's own
+    // material_n, see rtpb_spot_sweep) and the values arrive as scalar loads; without it (single rows only) every ray
+    // of the block has the group's wavelength, so the per-wavelength values of ray 0 serve both
+    Rcp<double> iwl[kSweepRays];
+    cptr<double> gn[kSweepRays];
+    double n_cur[kSweepRays];
+    // the group's wavelength (not r[0].wl: a row kill fills the ray's wavelength with NaN too, and the single rows'
+    // second ray takes ray 0's n)
+    double wl0 = 0.0;
+    auto mat_n = [&](int q, int k) -> double {
+        if constexpr ((FEAT & 16) != 0) return gn[q][k];
+        else return material_n<double, (FEAT & 2) != 0>(load_material<double>(mats + k), wl0, table);
+    };
+    // the surface's descriptor for ray q: with host-evaluated media, the Snell ratio and 1 / n2 of q's group (IEEE
+    // division on the host)
+    auto surface_for = [&](int q, int k, const DevSurface<double>& base) {
+        DevSurface<double> sd = base;
+        if constexpr ((FEAT & 16) != 0) {
+            sd.nr = gn[q][a.nsurf + 1 + k];
+            sd.rn2 = gn[q][2 * a.nsurf + 1 + k];
+            sd.rcp_ok = (sd.rcp_ok & ~(4 | 8)) | 4 | (gn[q][3 * a.nsurf + 1 + k] != 0.0 ? 8 : 0);
+        }
+        return sd;
+    };
+    auto code_of = [&](int k) { return surface_code<double>((surf + k)->kind, (surf + k)->rcp_ok); };
+    constexpr int kMode = (kWave ? kNoAt : kPosOnly) | ((FEAT & 16) != 0 ? kUniMedia : 0);
+    // the statistics read only the final positions: the steps run with kPosOnly semantics (no TIR fill of the
+    // position -- the next surface's intersection makes it NaN, and the final plane gets the rule in reduce), and a
+    // run of axial spheres carries x x + y y of each intersection point into the next sphere's quadratic.
+    // Runs of consecutive surfaces of one (kind, axial) code: each run loops inside one instantiation of the surface
+    // step, so the rays' registers carry from surface to surface without the copies a per-surface join of the kind
+    // branches needs (the ODT path of C5: 12 axial spheres, a lens, a flat = 3 runs).
+    double rxy[kSweepRays];
+    auto trace_from = [&](int s) {
+        while (s < a.nsurf) {
+            const int code = code_of(s);
+            dispatch_code<(FEAT & 1) != 0>(code, [&](auto kind, auto geo) {
+                constexpr int K = decltype(kind)::value;
+                constexpr int A = decltype(geo)::value;
+                constexpr bool kCarry = K == SPHERE && A == kGeoAxial && !kWave;
+                if constexpr (kCarry) {
+#pragma unroll
+                    for (int q = 0; q < kSweepRays; ++q) rxy[q] = r[q].x * r[q].x + r[q].y * r[q].y;
+                }
+                do {
+                    const DevSurface<double> base = load_surface<double>(surf + s);
+                    double n_next[kSweepRays];
+#pragma unroll
+                    for (int q = 0; q < kSweepRays; ++q) n_next[q] = (BUNDLE || q == 0) ? mat_n(q, s + 1) : n_next[0];
+                    auto none = [](const Ray<double>&) {};
+                    Ray<double> o[kSweepRays];
+#pragma unroll
+                    for (int q = 0; q < kSweepRays; ++q) {
+                        const DevSurface<double> sd = (BUNDLE || q == 0) ? surface_for(q, s, base)
+                                                                         : surface_for(0, s, base);
+                        surface_step<double, K, A, kMode>(sd, r[q], n_cur[q], n_next[q], iwl[q], none, o[q],
+                                                          static_cast<GuardBranch*>(nullptr),
+                                                          kCarry ? &rxy[q] : nullptr);
+                    }
+#pragma unroll
+                    for (int q = 0; q < kSweepRays; ++q) {
+                        r[q] = o[q];
+                        n_cur[q] = n_next[q];
+                    }
+                    ++s;
+                } while (s < a.nsurf && code_of(s) == code);
+            });
+        }
+    };
+    // one ray's contribution to its group's tile partial: spot_partial_kernel's tree (block_tree_sum), kRedRows
+    // statistics at a time
+    auto reduce = [&](const Ray<double>& rr, bool ok, int64_t g, int64_t t) {
+        double v[kStats] = {};
+        FocusRay f{0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+        WaveRay wv{0.0, 0.0, 0.0, 0.0, 0.0};
+        double* out;
+        if constexpr (kWave) out = ((cptr<SweepWave>)(a.wave))->partials;
+        else out = a.partials;
+        // the reference's position rule of the last surface (RT:1221 / RT:1289; a PerfectLens's after-plane
+        // propagation gives a NaN position for a NaN direction by itself): NaN direction -> no spot point
+        if (ok && !is_nan(rr.dx)) {
+            const double x = stored<TS>(rr.x), y = stored<TS>(rr.y), z = stored<TS>(rr.z);
+            if constexpr (NS == kStats) {
+                if (x - x == 0.0 && y - y == 0.0) {
+                    v[0] = 1.0; v[1] = x; v[2] = y; v[3] = z; v[4] = x * x; v[5] = y * y; v[6] = x * y;
+                }
+            } else if constexpr (kWave) {
+                const cptr<double> q = (cptr<double>)(a.wave + 1) + kWaveRef * g;
+                const double ref[kWaveRef] = {q[0], q[1], q[2], q[3], q[4], q[5], q[6], q[7]};
+                wv = wave_ray(x, y, z, rr.dx, rr.dy, rr.dz, rr.ph, ref);
+            } else {
+                double dx = stored<TS>(rr.dx), dy = stored<TS>(rr.dy), dz = stored<TS>(rr.dz);
+                // the slopes' divisions stay behind the trace: without the fence the float64 instantiations spill
+                // inside the surface loops (FEAT 17 single rows: 20 spilled VGPRs instead of the spot kernel's 1)
+                RTPB_PIN3(dx, dy, dz);
+                f = focus_ray(x, y, z, dx, dy, dz);
+            }
+        }
+#pragma unroll
+        for (int k0 = 0; k0 < NS; k0 += kRedRows) {
+            double u[kRedRows];
+#pragma unroll
+            for (int j = 0; j < kRedRows; ++j) {
+                if constexpr (NS == kStats) u[j] = k0 + j < NS ? v[k0 + j] : 0.0;
+                else if constexpr (kWave) u[j] = wave_term(wv, k0 + j);
+                else u[j] = focus_term(f, k0 + j);
+            }
+            block_tree_sum<kRedRows>(u, red);
+            if (tid == 0 && t < a.tiles) {
+#pragma unroll
+                for (int j = 0; j < kRedRows; ++j)
+                    if (k0 + j < NS) out[(g * a.tiles + t) * NS + k0 + j] = u[j];
+            }
+        }
+    };
+    // the image mode's counterpart: one ray's contribution to its group's image, by the same rule of the last
+    // surface; every lane reaches the wave's adds, and g is the same in the whole block
+    auto to_image = [&](const Ray<double>& rr, bool ok, int64_t g) {
+        const cptr<SweepImage> im = (cptr<SweepImage>)(a.image);
+        const cptr<double> win = (cptr<double>)(a.image + 1) + 4 * g;
+        const int nx = im->nx, ny = im->ny;
+        int bin = kImageSkip;
+        if (ok && !is_nan(rr.dx)) {
+            const double w[4] = {win[0], win[1], win[2], win[3]};
+            bin = image_bin(stored<TS>(rr.x), stored<TS>(rr.y), w, nx, ny);
+        }
+        wave_image_add(bin, im->image + g * ny * nx, im->outside + g);
+    };
+    if constexpr (!BUNDLE) {
+#pragma unroll
+        for (int q = 0; q < kSweepRays; ++q) {
+            grp[q] = a.gidx[blockIdx.y];
+            tile[q] = kSweepRays * int64_t(blockIdx.x) + q;
+            r[q] = gen(tile[q] * kBlock + tid, grp[q]);
+            // a beam's positions are complete before the trace begins: without the fence the PerfectLens single rows
+            // spill 12 VGPRs instead of the fan's 1
+            if constexpr (SRC == kSrcBeam) RTPB_PIN3(r[q].x, r[q].y, r[q].z);
+        }
+        wl0 = r[0].wl;
+#pragma unroll
+        for (int q = 0; q < kSweepRays; ++q) {
+            iwl[q] = q == 0 ? make_wl_rcp(r[0].wl) : iwl[0];   // every phase update's divisor, 2 pi / wl
+            gn[q] = (cptr<double>)(a.gn) + grp[q] * (4 * a.nsurf + 1);
+        }
+#pragma unroll
+        for (int q = 0; q < kSweepRays; ++q) n_cur[q] = q == 0 ? mat_n(0, 0) : n_cur[0];
+        trace_from(0);
+#pragma unroll
+        for (int q = 0; q < kSweepRays; ++q) {
+            if constexpr (NS == kImageStats) to_image(r[q], tile[q] * kBlock + tid < a.gsize, grp[q]);
+            else reduce(r[q], tile[q] * kBlock + tid < a.gsize, grp[q], tile[q]);
+        }
+    } else {
+        const int32_t off = a.rows[2 * blockIdx.y], nb = a.rows[2 * blockIdx.y + 1];
+        const int64_t t0 = blockIdx.x;
+        const Ray<double> rg = gen(t0 * kBlock + tid, int64_t(a.gidx[off]));
+        wl0 = rg.wl;
+        const int code0 = a.nsurf > 0 ? code_of(0) : -1;
+        using std::integral_constant;
+        // fn(kind, geo) on the first surface's code when it is a refracting Flat / Sphere; false otherwise
+        auto on_first = [&](auto&& fn) {
+            if (code0 == 3 * SPHERE + kGeoAxial) fn(integral_constant<int, SPHERE>(), integral_constant<int, kGeoAxial>());
+            else if (code0 == 3 * SPHERE) fn(integral_constant<int, SPHERE>(), integral_constant<int, kGeoGeneral>());
+            else if (code0 == 3 * FLAT + kGeoAxial) fn(integral_constant<int, FLAT>(), integral_constant<int, kGeoAxial>());
+            else if (code0 == 3 * FLAT + kGeoXZ) fn(integral_constant<int, FLAT>(), integral_constant<int, kGeoXZ>());
+            else if (code0 == 3 * FLAT) fn(integral_constant<int, FLAT>(), integral_constant<int, kGeoGeneral>());
+            else return false;
+            return true;
+        };
+        // the shared part of the first surface (surface_step_pair): a row that fails the front-side or on-surface
+        // test stores a NaN position and c . d, so each refraction of it is all NaN (as the step's kill)
+        const bool shared = on_first([&](auto kind, auto geo) {
+            constexpr int K = decltype(kind)::value;
+            constexpr int A = decltype(geo)::value;
+            const DevSurface<double> base = load_surface<double>(surf);
+            const Rcp<double> iwl0 = make_wl_rcp(rg.wl);     // (the phase, and with it n1 and iwl0, is not kept)
+            double rxy0 = rg.x * rg.x + rg.y * rg.y;
+            double Nx, Ny, Nz;
+            Ray<double> ri;
+            bool fwd = true;
+            hit_and_normal<double, K, A>(base, rg, 1.0, iwl0, static_cast<GuardBranch*>(nullptr),
+                                         K == SPHERE && A == kGeoAxial ? &rxy0 : nullptr, ri, Nx, Ny, Nz, &fwd);
+            const bool front_ok = !front_side_fails<A, true>(rg, base) && fwd;
+            constexpr int kBasis = K == FLAT ? A : kGeoGeneral;
+            const SnellBasis<double> b = snell_basis<kBasis>(ri, Nx, Ny, Nz, static_cast<GuardBranch*>(nullptr));
+            bool ok;
+            if constexpr (K == SPHERE) ok = on_sphere<A == kGeoAxial>(ri, base, A == kGeoAxial ? &rxy0 : nullptr) && front_ok;
+            else ok = on_flat<A>(ri, base) && front_ok;
+            double px = ri.x, py = ri.y, pz = ri.z, cd = b.cd;
+            if (!ok) px = py = pz = cd = qnan<double>();
+            state[0][tid] = px; state[1][tid] = py; state[2][tid] = pz;
+            state[3][tid] = Nx; state[4][tid] = Ny; state[5][tid] = Nz;
+            state[6][tid] = b.cx; state[7][tid] = b.cy; state[8][tid] = b.cz;
+            state[9][tid] = cd; state[10][tid] = b.nd;
+        });
+        if (!shared) {
+            state[0][tid] = rg.x; state[1][tid] = rg.y; state[2][tid] = rg.z;
+            state[3][tid] = rg.dx; state[4][tid] = rg.dy; state[5][tid] = rg.dz;
+        }
+        for (int p = 0; p < nb; p += kSweepRays) {
+#pragma unroll
+            for (int q = 0; q < kSweepRays; ++q) {
+                grp[q] = a.gidx[off + p + q];
+                tile[q] = t0;
+                gn[q] = (cptr<double>)(a.gn) + grp[q] * (4 * a.nsurf + 1);
+                r[q].ph = 0.0;
+                r[q].wl = stored<TS>(a.grp[4 * grp[q] + 3]);
+            }
+            int s0 = 0;
+            const bool first = on_first([&](auto kind, auto geo) {
+                constexpr int kBasis = decltype(kind)::value == FLAT ? decltype(geo)::value : kGeoGeneral;
+                Ray<double> ri;
+                ri.x = state[0][tid]; ri.y = state[1][tid]; ri.z = state[2][tid];
+                ri.dx = ri.dy = ri.dz = 0.0;
+                ri.ph = 0.0;
+                const double Nx = state[3][tid], Ny = state[4][tid], Nz = state[5][tid];
+                SnellBasis<double> b;
+                b.cx = state[6][tid]; b.cy = state[7][tid]; b.cz = state[8][tid];
+                b.cd = state[9][tid]; b.nd = state[10][tid];
+#pragma unroll
+                for (int q = 0; q < kSweepRays; ++q) {
+                    ri.wl = r[q].wl;
+                    r[q] = snell_apply<kBasis, false>(ri, Nx, Ny, Nz, b, gn[q][a.nsurf + 1],
+                                                        static_cast<GuardBranch*>(nullptr));
+                }
+            });
+            if (first) {
+                s0 = 1;
+            } else {
+#pragma unroll
+                for (int q = 0; q < kSweepRays; ++q) {
+                    r[q].x = state[0][tid]; r[q].y = state[1][tid]; r[q].z = state[2][tid];
+                    r[q].dx = state[3][tid]; r[q].dy = state[4][tid]; r[q].dz = state[5][tid];
+                }
+            }
+#pragma unroll
+            for (int q = 0; q < kSweepRays; ++q) {
+                iwl[q] = make_wl_rcp(r[q].wl);
+                n_cur[q] = mat_n(q, s0);
+            }
+            trace_from(s0);
+#pragma unroll
+            for (int q = 0; q < kSweepRays; ++q) {
+                if constexpr (NS == kImageStats) to_image(r[q], t0 * kBlock + tid < a.gsize, grp[q]);
+                else reduce(r[q], t0 * kBlock + tid < a.gsize, grp[q], t0);
+            }
+        }
+    }
+}
+
+// What a call says about its groups' rays besides group_params, as the entry points received it (host pointers).
+// Ray j of a group takes entry j % n_a of tab_a and entry j / n_a of tab_b.
+//   fan (rtpb_*_sweep):             n_a = n_thetas, tab_a the thetas' (cos, sin); n_b = nphis, tab_b the phis'
+//                                   (cos, sin); c, ex, ey the axis and its basis
+//   beam (rtpb_*_sweep_collimated): n_a = nphis, tab_a the phis' (cos, sin); n_b = n_disps, tab_b the offsets;
+//                                   frames n_groups x kFrame
+struct SweepSource {
+    int64_t n_a, n_b;
+    const double* tab_a;
+    const double* tab_b;
+    const double* c;
+    const double* ex;
+    const double* ey;
+    const double* frames;
+    bool complete(int src) const {
+        return n_a > 0 && n_b > 0 && tab_a && tab_b && (src == kSrcBeam ? frames != nullptr : c && ex && ey);
+    }
+};
+
+inline SweepSource fan_source(int64_t n_thetas, int64_t nphis, const double* center_ray, const double* ex,
+                              const double* ey, const double* theta_cos_sin, const double* phi_cos_sin) {
+    return SweepSource{n_thetas, nphis, theta_cos_sin, phi_cos_sin, center_ray, ex, ey, nullptr};
+}
+
+inline SweepSource beam_source(const double* group_frames, int64_t n_disps, int64_t nphis, const double* offsets,
+                               const double* phi_cos_sin) {
+    return SweepSource{nphis, n_disps, phi_cos_sin, offsets, nullptr, nullptr, nullptr, group_frames};
+}
+
+// rtpb_spot_sweep (NS = kStats), rtpb_focus_sweep (NS = kFocusStats) and rtpb_wavefront_sweep (NS = kWaveStats), and
+// their _collimated counterparts (SRC = kSrcBeam): the argument checks ...
+template <int NS, int SRC = kSrcFan>
+int sweep_check(int64_t n_groups, const double* group_params, const SweepSource& s, double* workspace,
+                int64_t workspace_len, double* stats_out) {
+    constexpr bool kFocus = NS == kFocusStats, kWave = NS == kWaveStats;
+    if (n_groups <= 0 || !s.complete(SRC) || !group_params || !workspace || !stats_out)
+        return fail(RTPB_E_INVALID, kWave    ? "bad wavefront-sweep arguments"
+                                    : kFocus ? "bad focus-sweep arguments"
+                                             : "bad spot-sweep arguments");
+    const int64_t tiles = (s.n_a * s.n_b + kBlock - 1) / kBlock;
+    if (workspace_len < n_groups * tiles * NS)
+        return fail(RTPB_E_INVALID,
+                    SRC == kSrcBeam
+                        ? (kWave    ? "workspace too small: need n_groups * ceil(n_disps*nphis/256) * 15 doubles"
+                           : kFocus ? "workspace too small: need n_groups * ceil(n_disps*nphis/256) * 16 doubles"
+                                    : "workspace too small: need n_groups * ceil(n_disps*nphis/256) * 7 doubles")
+                    : kWave  ? "workspace too small: need n_groups * ceil(n_thetas*nphis/256) * 15 doubles"
+                    : kFocus ? "workspace too small: need n_groups * ceil(n_thetas*nphis/256) * 16 doubles"
+                             : "workspace too small: need n_groups * ceil(n_thetas*nphis/256) * 7 doubles");
+    if (tiles > 0x7fffffffll || n_groups > 65535) return fail(RTPB_E_LIMIT, "too many groups or rays per group");
+    return RTPB_OK;
+}
+
+// ... those of the image sweeps (no workspace, no statistics; `what` names the call in the messages) ...
+template <int SRC = kSrcFan>
+int image_sweep_check(const char* what, const char* too_many, int64_t n_groups, const double* group_params,
+                      const SweepSource& s, const double* windows, int32_t nx, int32_t ny, int32_t* image_out,
+                      int32_t* outside_out) {
+    if (n_groups <= 0 || !s.complete(SRC) || !group_params)
+        return fail(RTPB_E_INVALID, SRC == kSrcBeam ? "bad image-sweep-collimated arguments"
+                                                    : "bad image-sweep arguments");
+    // (n_a * n_b: a product past int64 is past the limit too)
+    const int64_t gsize = s.n_a > 0x7fffffffll / s.n_b ? 0x80000000ll : s.n_a * s.n_b;
+    int rc = image_check(what, nx, ny, gsize, n_groups, windows, image_out, outside_out);
+    if (rc) return rc;
+    if (n_groups > 65535) return fail(RTPB_E_LIMIT, too_many);
+    return RTPB_OK;
+}
+
+// rtpb_image_sweep's own arguments (NS = kImageStats: no workspace, no statistics)
+struct ImageCall {
+    const double* windows;      // host, n_groups x 4
+    int32_t nx, ny;
+    int32_t* image_out;
+    int32_t* outside_out;
+};
+
+// ... and the sweep itself (checked arguments): plan the block rows, fill and send the one upload, launch the sweep
+// kernels of the statistics set, then the final reduction -- or, for the image, clear the outputs and launch the
+// image kernels.  refs: the wavefront mode's references (host, n_groups x kWaveRef); every group of that mode is a
+// single row (the bundle rows' shared first surface keeps no phase) and its storage type is float64.
+template <int NS, int SRC = kSrcFan>
+int sweep_impl(const rtpb_plan* plan_c, int32_t device, int64_t n_groups, const double* group_params,
+               const SweepSource& src, double* workspace, double* stats_out, void* stream,
+               const ImageCall* im = nullptr, const double* refs = nullptr) {
+    constexpr bool kImage = NS == kImageStats, kWave = NS == kWaveStats, kBeam = SRC == kSrcBeam;
+    auto* plan = const_cast<rtpb_plan*>(plan_c);
+    const int64_t gsize = src.n_a * src.n_b;
+    const int64_t tiles = (gsize + kBlock - 1) / kBlock;
+    DeviceGuard g(device);
+    void* blob = nullptr;
+    int rc = plan_device_blob(plan, device, &blob);
+    if (rc) return rc;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    // bundle rows need the host-evaluated media, which a POLY6 material rules out
+    const bool pre_n = (plan->feat & 2) == 0;
+    const size_t M = plan->mats.size();
+    const SweepRows pr = plan_sweep_rows(group_params, n_groups, pre_n && !kWave, kSweepRays, kMaxBundle,
+                                         kBeam ? src.frames : nullptr);
+    // (a beam's second table is its offsets, plain doubles: half as many pair slots)
+    const SweepLayout lay(src.n_a, kBeam ? (src.n_b + 1) / 2 : src.n_b, n_groups, pre_n ? M + 3 * (M - 1) : 0,
+                          pr.bundles.size() + pr.singles.size() + pr.rows.size(),
+                          kImage  ? sizeof(SweepImage) / sizeof(double)
+                          : kWave ? sizeof(SweepWave) / sizeof(double)
+                                  : 0,
+                          kWave ? kWaveRef : 4, kBeam ? kFrame : 0);
+    StreamScratch dbuf;
+    rc = dbuf.alloc(lay.bytes, st);
+    if (rc) return rc;
+    PinnedStaging& g_pinned = pinned_staging();
+    rc = g_pinned.reserve(lay.bytes);
+    if (rc) return rc;
+    char* const h = reinterpret_cast<char*>(g_pinned.buf);
+    std::memcpy(h, src.tab_a, size_t(2 * src.n_a) * sizeof(double));
+    std::memcpy(h + size_t(2 * src.n_a) * sizeof(double), src.tab_b, size_t((kBeam ? 1 : 2) * src.n_b) * sizeof(double));
+    std::memcpy(h + lay.grp, group_params, size_t(4 * n_groups) * sizeof(double));
+    if constexpr (kBeam) std::memcpy(h + lay.frm, src.frames, size_t(kFrame * n_groups) * sizeof(double));
+    if (pre_n) {
+        std::vector<DevMaterial<double>> dm(M);
+        for (size_t k = 0; k < M; ++k) dm[k] = device_material(*plan, k);
+        fill_group_media(dm.data(), M, plan->table.data(), group_params, n_groups, plan->dtype,
+                         reinterpret_cast<double*>(h + lay.gn));
+    }
+    if constexpr (kImage) {
+        const SweepImage head{im->image_out, im->outside_out, im->nx, im->ny};
+        std::memcpy(h + lay.img, &head, sizeof(head));
+        std::memcpy(h + lay.win, im->windows, size_t(4 * n_groups) * sizeof(double));
+        rc = image_clear(im->image_out, im->outside_out, n_groups, im->nx, im->ny, st);
+        if (rc) return rc;
+    }
+    if constexpr (kWave) {
+        const SweepWave head{workspace};
+        std::memcpy(h + lay.img, &head, sizeof(head));
+        std::memcpy(h + lay.win, refs, size_t(kWaveRef * n_groups) * sizeof(double));
+    }
+    int32_t* hidx = reinterpret_cast<int32_t*>(h + lay.idx);
+    hidx = std::copy(pr.bundles.begin(), pr.bundles.end(), hidx);
+    hidx = std::copy(pr.singles.begin(), pr.singles.end(), hidx);
+    std::copy(pr.rows.begin(), pr.rows.end(), hidx);
+    rc = g_pinned.upload(dbuf.p, lay.bytes, st);
+    if (rc) return rc;
+    const char* const d = static_cast<const char*>(dbuf.p);
+    SweepArgs a{};
+    a.surf = static_cast<const DevSurface<double>*>(blob);
+    a.mats = reinterpret_cast<const DevMaterial<double>*>(static_cast<char*>(blob) + plan->off_mats);
+    a.table = reinterpret_cast<const double*>(static_cast<char*>(blob) + plan->off_table);
+    a.tab = reinterpret_cast<const double2*>(d);
+    a.grp = reinterpret_cast<const double*>(d + lay.grp);
+    a.gn = reinterpret_cast<const double*>(d + lay.gn);
+    const int32_t* didx = reinterpret_cast<const int32_t*>(d + lay.idx);
+    if constexpr (kImage) a.image = reinterpret_cast<const SweepImage*>(d + lay.img);
+    else if constexpr (kWave) a.wave = reinterpret_cast<const SweepWave*>(d + lay.img);
+    else a.partials = workspace;
+    a.n_thetas = src.n_a;
+    a.nphis = src.n_b;
+    a.gsize = gsize;
+    a.tiles = tiles;
+    if constexpr (kBeam) {
+        a.frm = reinterpret_cast<const double*>(d + lay.frm);
+    } else {
+        for (int j = 0; j < 3; ++j) {
+            a.c[j] = src.c[j]; a.ex[j] = src.ex[j]; a.ey[j] = src.ey[j];
+        }
+    }
+    a.nsurf = plan->nsurf;
+    sweep_divisor(src.n_a, gsize, a.nt_mul, a.nt_shift);
+    auto go = [&](auto tag) {
+        using TS = decltype(tag);
+        const int f = plan->feat & 3;                 // lens / POLY6 code (no pre_n: POLY6); tables always compiled in
+        if constexpr (!kWave) {                       // (the wavefront mode plans no bundle rows)
+            if (!pr.rows.empty()) {
+                SweepArgs ap = a;
+                ap.gidx = didx;
+                ap.rows = didx + pr.bundles.size() + pr.singles.size();
+                const dim3 grid(static_cast<unsigned>(tiles), static_cast<unsigned>(pr.rows.size() / 2));
+                if (f == 0) hipLaunchKernelGGL((sweep_kernel<TS, 16, true, NS, SRC>), grid, dim3(kBlock), 0, st, ap);
+                else hipLaunchKernelGGL((sweep_kernel<TS, 17, true, NS, SRC>), grid, dim3(kBlock), 0, st, ap);
+            }
+        }
+        if (!pr.singles.empty()) {
+            SweepArgs as = a;
+            as.gidx = didx + pr.bundles.size();
+            const dim3 grid(static_cast<unsigned>((tiles + kSweepRays - 1) / kSweepRays),
+                            static_cast<unsigned>(pr.singles.size()));
+            if (pre_n && f == 0) hipLaunchKernelGGL((sweep_kernel<TS, 16, false, NS, SRC>), grid, dim3(kBlock), 0, st, as);
+            else if (pre_n) hipLaunchKernelGGL((sweep_kernel<TS, 17, false, NS, SRC>), grid, dim3(kBlock), 0, st, as);
+            else hipLaunchKernelGGL((sweep_kernel<TS, 3, false, NS, SRC>), grid, dim3(kBlock), 0, st, as);   // POLY6 media
+        }
+    };
+    if constexpr (kWave) {
+        go(double{});
+    } else {
+        if (plan->dtype == RTPB_F64) go(double{});
+        else go(float{});
+    }
+    HIP_TRY(hipGetLastError());
+    if constexpr (!kImage) {
+        rc = launch_stats_final(NS, workspace, stats_out, n_groups, tiles, st);
+        if (rc) return rc;
+    }
+    return dbuf.release();
+}
+
+}  // namespace
+

@@ -212,13 +212,7 @@ def get_collimated_rays(pt, displacement_max, n_disps: int, wavelengths, nphis: 
     pp, oo = np.meshgrid(phis, offs)
     pp, oo = pp.ravel(), oo.ravel()
     pt = np.array(pt).squeeze()
-    normal = np.array(normal).squeeze()
-    n1 = np.cross(np.array([0, 1, 0]), normal)
-    if np.linalg.norm(n1) == 0:
-        n1 = np.cross(normal, np.array([1, 0, 0]))
-    n1 = n1 / np.linalg.norm(n1)
-    n2 = np.cross(normal, n1)
-    n2 = n2 / np.linalg.norm(n2)
+    normal, n1, n2 = _collimated_frame(normal)
     rays = np.zeros((n_disps * nphis, 8))
     rays[:, 0:3] = pt[None, :] + n1[None, :] * (oo * np.cos(pp))[:, None] + n2[None, :] * (oo * np.sin(pp))[:, None]
     rays[:, 3:6] = normal
@@ -226,16 +220,8 @@ def get_collimated_rays(pt, displacement_max, n_disps: int, wavelengths, nphis: 
     return rays
 
 
-def _collimated_device(pt, displacement_max, n_disps, wavelength, nphis, phi_start, normal, device, dtype):
-    """get_collimated_rays in HBM: the host-side values of RT:128-144 (phis, offsets, their cos/sin,
-    the n1/n2 basis) come from NumPy exactly as in the reference, the per-ray products from
-    ``rtpb_collimated_rays_tables`` -- bit-identical to the reference's rays."""
-    import torch
-    dev = torch.device(device)
-    tdt = torch.float32 if dtype in ("float32", np.float32, torch.float32) else torch.float64
-    out = torch.empty((n_disps * nphis, 8), dtype=tdt, device=dev)
-    phis = np.arange(nphis) * 2 * np.pi / nphis + phi_start
-    offs = np.ascontiguousarray(np.linspace(-displacement_max, displacement_max, n_disps), dtype=np.float64)
+def _collimated_frame(normal):
+    """(normal, n1, n2) of RT:133-144: n1 = y x normal, or normal x x when normal is along y; n2 = normal x n1."""
     normal = np.array(normal).squeeze()
     n1 = np.cross(np.array([0, 1, 0]), normal)
     if np.linalg.norm(n1) == 0:
@@ -243,22 +229,52 @@ def _collimated_device(pt, displacement_max, n_disps, wavelength, nphis, phi_sta
     n1 = n1 / np.linalg.norm(n1)
     n2 = np.cross(normal, n1)
     n2 = n2 / np.linalg.norm(n2)
+    return normal, n1, n2
+
+
+def _collimated_tables(displacement_max, n_disps, nphis, phi_start):
+    """Host-side values of RT:128-131: the linspace offsets (n_disps,) and (cos, sin) of the phis (nphis, 2)."""
+    phis = np.arange(nphis) * 2 * np.pi / nphis + phi_start
+    offs = np.ascontiguousarray(np.linspace(-displacement_max, displacement_max, n_disps), dtype=np.float64)
     pcs = np.ascontiguousarray(np.stack((np.cos(phis), np.sin(phis)), axis=1), dtype=np.float64)
-    vec = [np.ascontiguousarray(np.asarray(v, dtype=np.float64).ravel()) for v in (pt, normal, n1, n2)]
+    return offs, pcs
+
+
+def _collimated_device(pt, displacement_max, n_disps, wavelength, nphis, phi_start, normal, device, dtype):
+    import torch
+    dev = torch.device(device)
+    tdt = torch.float32 if dtype in ("float32", np.float32, torch.float32) else torch.float64
+    out = torch.empty((n_disps * nphis, 8), dtype=tdt, device=dev)
+    return collimated_into(out, pt, displacement_max, n_disps, wavelength, nphis, phi_start, normal)
+
+
+def collimated_into(buf, pt, displacement_max, n_disps, wavelength, nphis=1, phi_start=0., normal=(0, 0, 1)):
+    """Write get_collimated_rays(pt, displacement_max, n_disps, wavelength, nphis, phi_start, normal) into the torch
+    CUDA buffer ``buf`` ((n_disps*nphis, 8), float64 or float32) on its current stream.
+
+    The host-side values of RT:128-144 (phis, offsets, their cos/sin, the n1/n2 basis) come from NumPy exactly as
+    in the reference, the per-ray products from ``rtpb_collimated_rays_tables`` (``_wl`` for per-ray
+    wavelengths) -- bit-identical to the reference's rays."""
+    import torch
+    dev = buf.device
     n = int(n_disps) * int(nphis)
+    if buf.shape != (n, 8) or not buf.is_contiguous():
+        raise ValueError("collimated_into: buffer shape does not match the bundle")
+    offs, pcs = _collimated_tables(displacement_max, n_disps, nphis, phi_start)
+    vec = [np.ascontiguousarray(np.asarray(v, dtype=np.float64).ravel()) for v in (pt,) + _collimated_frame(normal)]
     wl, col = _wavelength_args(wavelength, n, 0, n, dev)
-    code = C.RTPB_F64 if tdt == torch.float64 else C.RTPB_F32
+    code = C.RTPB_F64 if buf.dtype == torch.float64 else C.RTPB_F32
     stream = torch.cuda.current_stream(dev).cuda_stream
     if col is None:
-        C.check(C.lib().rtpb_collimated_rays_tables(dev.index or 0, code, out.data_ptr(), vec[0].ctypes.data,
+        C.check(C.lib().rtpb_collimated_rays_tables(dev.index or 0, code, buf.data_ptr(), vec[0].ctypes.data,
                                                     int(n_disps), int(nphis), vec[1].ctypes.data, vec[2].ctypes.data,
                                                     vec[3].ctypes.data, offs.ctypes.data, pcs.ctypes.data, wl, stream))
     else:
-        C.check(C.lib().rtpb_collimated_rays_tables_wl(dev.index or 0, code, out.data_ptr(), vec[0].ctypes.data,
+        C.check(C.lib().rtpb_collimated_rays_tables_wl(dev.index or 0, code, buf.data_ptr(), vec[0].ctypes.data,
                                                        int(n_disps), int(nphis), vec[1].ctypes.data,
                                                        vec[2].ctypes.data, vec[3].ctypes.data, offs.ctypes.data,
                                                        pcs.ctypes.data, col.data_ptr(), stream))
-    return out
+    return buf
 
 
 # =============================================================================== ray utilities

@@ -1,0 +1,324 @@
+"""GPU: the collimated-beam sweeps (analysis.collimated_spot_sweep / _focus_sweep / _image_sweep / _wavefront_sweep;
+rtpb_*_sweep_collimated) on the cases of tests/beam_cases.py against the NumPy oracle, bit for bit.
+
+The oracle traces each group's beam from the reference generator (rt.get_collimated_rays) and its final planes are
+reduced in the kernels' order: the raw sums must be the same bits, hence every summary entry; images and outside
+counts are equal integers; the wavefront sums are wave_oracle's restatement against references built from the
+oracle's own centroids and chief rays.  The same comparison runs for the unfused pipeline (rtpb_collimated_rays_tables
++ trace(planes='final') + the plane reductions), so a failure says which path left the reference.  No case is exempt
+from the count comparison.  The POLY6 case evaluates its media with the device's pow, which is not NumPy's: there
+the counts are the oracle's, the sums agree to 1e-11 as tests/test_gpu_poly6.py asks of the fan sweep, and fused and
+unfused agree bit for bit."""
+import functools
+
+import numpy as np
+import pytest
+
+torch = pytest.importorskip("torch")
+
+import ray_trace_pb_amd.materials as mat  # noqa: E402
+import ray_trace_pb_amd.raytrace as rt  # noqa: E402
+from ray_trace_pb_amd import analysis  # noqa: E402
+from oracle import rt_numpy as O  # noqa: E402
+from parity import same_bits  # noqa: E402
+from serialize import material_to_dict, surface_to_dict  # noqa: E402
+import beam_cases as bc  # noqa: E402
+import sweep_cases as sc  # noqa: E402
+import wave_oracle as W  # noqa: E402
+from test_gpu_analysis import fixed_order_sums  # noqa: E402
+from test_gpu_focus import fixed_order_focus_sums  # noqa: E402
+from test_image_host import image_of_plane  # noqa: E402
+
+pytestmark = pytest.mark.gpu
+DEV = "cuda:0"
+BINS = (16, 12)
+EPS = 2.0 ** -52
+
+
+@functools.lru_cache(maxsize=None)
+def oracle_sums(name, dtype, nd=None, nph=None):
+    """(spot sums (fields, wavelengths, 7), focus sums (..., 16)) of the oracle's final planes, computed once per
+    (case, dtype, shape) and shared by the fused and unfused tests; read-only."""
+    c = bc.case(name)
+    fin = bc.oracle_finals(name, dtype, nd, nph)
+    per = (nd or c.nd) * (nph or c.nph)
+    shape = (len(c.normals), len(c.wls))
+    spot = fixed_order_sums(fin, per).reshape(shape + (7,))
+    focus = fixed_order_focus_sums(fin, per).reshape(shape + (16,))
+    spot.setflags(write=False)
+    focus.setflags(write=False)
+    return spot, focus
+
+
+def same_int64(got, ref):
+    got, ref = np.ascontiguousarray(got, dtype=np.float64), np.ascontiguousarray(ref, dtype=np.float64)
+    return got.shape == ref.shape and np.array_equal(got.view(np.int64), ref.view(np.int64))
+
+
+def assert_same_summary(got, exp):
+    assert got.keys() == exp.keys()
+    for k in exp:
+        assert same_bits(got[k], exp[k]), k
+
+
+def assert_spot_and_focus(c, spot, focus, ref_spot, ref_focus):
+    """Counts exactly in every case; then the bits, or for POLY6 media 1e-11."""
+    assert np.array_equal(spot["count"], ref_spot[..., 0])
+    assert np.array_equal(focus["count"], ref_focus[..., 0])
+    if not c.bitwise:
+        np.testing.assert_allclose(spot["raw"], ref_spot, rtol=1e-11, atol=1e-14)
+        np.testing.assert_allclose(focus["raw"], ref_focus, rtol=1e-11, atol=1e-14)
+        return
+    assert same_int64(spot["raw"], ref_spot)
+    assert same_int64(focus["raw"], ref_focus)
+    exp = analysis.summarize(ref_spot)
+    assert spot.keys() == exp.keys()
+    for k in ("count", "centroid", "rms_radius"):
+        assert same_bits(spot[k], exp[k]), k
+    assert_same_summary(focus, analysis.summarize_focus(ref_focus))
+
+
+@pytest.mark.parametrize("fused", [True, False], ids=["fused", "unfused"])
+@pytest.mark.parametrize("dtype", ["float64", "float32"])
+@pytest.mark.parametrize("name", bc.NAMES)
+def test_spot_and_focus_sweeps_bitwise_vs_oracle(name, dtype, fused):
+    """raw == the oracle's sums as int64 views (7 and 16 columns), and every summary entry the same bits as the
+    summary of the oracle's sums."""
+    c = bc.case(name)
+    ref_spot, ref_focus = oracle_sums(name, dtype)
+    kw = dict(pt=c.pts, device=DEV, dtype=dtype, fused=fused, groups_per_batch=c.gpb if fused else c.gpb + 1)
+    spot, timing = analysis.collimated_spot_sweep(*bc.sweep_args(c), **kw)
+    focus, _ = analysis.collimated_focus_sweep(*bc.sweep_args(c), require_image_plane=False, **kw)
+    print(name, dtype, "fused" if fused else "unfused", "oracle count", ref_spot[..., 0].astype(int).tolist(),
+          "spot", spot["count"].astype(int).tolist(), "focus", focus["count"].astype(int).tolist())
+    assert spot["raw"].shape == (len(c.normals), len(c.wls), 7)
+    assert timing["rays"] == len(c.normals) * len(c.wls) * c.nd * c.nph
+    assert_spot_and_focus(c, spot, focus, ref_spot, ref_focus)
+
+
+@pytest.mark.parametrize("fused", [True, False], ids=["fused", "unfused"])
+@pytest.mark.parametrize("dtype", ["float64", "float32"])
+@pytest.mark.parametrize("name", bc.NAMES)
+def test_images_equal_the_oracles(name, dtype, fused):
+    """Image counts and `outside` exactly, the windows from the oracle's own spot summary (a dead group's window is
+    the unit one around NaN and holds nothing)."""
+    c = bc.case(name)
+    ref_spot, _ = oracle_sums(name, dtype)
+    windows = analysis.auto_image_windows(analysis.summarize(ref_spot), BINS, sigmas=1.5)
+    fin = bc.oracle_finals(name, dtype)
+    exp_image, exp_outside = image_of_plane(fin, c.nd * c.nph, windows.reshape(-1, 4), *BINS)
+    assert exp_image.max() > 0 and exp_outside.max() > 0          # (rays inside and outside the 1.5 sigma windows)
+    got, _ = analysis.collimated_image_sweep(*bc.sweep_args(c), pt=c.pts, device=DEV, dtype=dtype, bins=BINS,
+                                             windows=windows, fused=fused,
+                                             groups_per_batch=c.gpb if fused else c.gpb + 1)
+    shape = (len(c.normals), len(c.wls))
+    assert got["image"].shape == shape + (BINS[1], BINS[0])
+    assert np.array_equal(got["count"], ref_spot[..., 0])
+    if c.bitwise:
+        assert np.array_equal(got["image"], exp_image.reshape(got["image"].shape))
+        assert np.array_equal(got["outside"], exp_outside.reshape(shape))
+
+
+@pytest.mark.parametrize("fused", [True, False], ids=["fused", "unfused"])
+@pytest.mark.parametrize("name", bc.NAMES)
+def test_wavefront_sweep_bitwise_vs_oracle(name, fused):
+    """The 15 raw sums and the summary against wave_oracle, with references built from the oracle's centroid and
+    chief ray (a dead chief ray: a NaN reference, the group counts nothing)."""
+    c = bc.case(name)
+    refs = bc.oracle_refs(name)
+    shape = (len(c.normals), len(c.wls))
+    exp = W.fixed_order_wave_sums(bc.oracle_finals(name), c.nd * c.nph, refs.reshape(-1, 8)).reshape(shape + (15,))
+    got, _ = analysis.collimated_wavefront_sweep(*bc.sweep_args(c), pt=c.pts, device=DEV, refs=refs, fused=fused,
+                                                 groups_per_batch=c.gpb if fused else c.gpb + 1)
+    print(name, "oracle count", exp[..., 0].astype(int).tolist(), "got", got["count"].astype(int).tolist())
+    assert np.array_equal(got["count"], exp[..., 0])
+    assert np.array_equal(got["count"] == 0, np.isnan(refs).any(axis=-1) | (exp[..., 0] == 0))
+    if c.bitwise:
+        assert same_int64(got["raw"], exp)
+        assert_same_summary(got, analysis.summarize_wavefront(exp, refs))
+    else:
+        # (media to 1e-11 over a path of some 1e6 waves: 1e-5 waves per ray)
+        np.testing.assert_allclose(got["rms_opd"], analysis.summarize_wavefront(exp, refs)["rms_opd"], rtol=1e-6,
+                                   atol=1e-4)
+
+
+def test_poly6_fused_equals_unfused_bitwise():
+    """POLY6 media: single rows only; the two pipelines evaluate the same device arithmetic."""
+    c = bc.case("poly6")
+    for dtype in ("float64", "float32"):
+        kw = dict(pt=c.pts, device=DEV, dtype=dtype)
+        fu, _ = analysis.collimated_focus_sweep(*bc.sweep_args(c), require_image_plane=False, fused=True, **kw)
+        un, _ = analysis.collimated_focus_sweep(*bc.sweep_args(c), require_image_plane=False, fused=False, **kw)
+        assert same_int64(fu["raw"], un["raw"])
+    refs = bc.oracle_refs("poly6")
+    fu, _ = analysis.collimated_wavefront_sweep(*bc.sweep_args(c), pt=c.pts, device=DEV, refs=refs, fused=True)
+    un, _ = analysis.collimated_wavefront_sweep(*bc.sweep_args(c), pt=c.pts, device=DEV, refs=refs, fused=False)
+    assert same_int64(fu["raw"], un["raw"])
+
+
+# one ray at offset -dmax; one short of a tile; one full tile with an even n_disps (no zero offset); one over a
+# tile; two tiles and one ray (with two rays per lane the second block has one ragged and one empty tile); and the
+# fan cases' 23177 rays
+SHAPES = [(1, 1), (51, 5), (16, 16), (257, 1), (171, 3), (301, 77)]
+
+
+@pytest.mark.parametrize("nd,nph", SHAPES)
+def test_bundle_shapes_on_c2(nd, nph):
+    c = bc.case("c2")
+    for dtype in ("float64", "float32"):
+        ref_spot, ref_focus = oracle_sums("c2", dtype, nd, nph)
+        assert (ref_spot[..., 0] == nd * nph).all()
+        for fused in (True, False):
+            kw = dict(pt=c.pts, device=DEV, dtype=dtype, fused=fused, groups_per_batch=4)
+            spot, _ = analysis.collimated_spot_sweep(*bc.sweep_args(c, nd, nph), **kw)
+            focus, _ = analysis.collimated_focus_sweep(*bc.sweep_args(c, nd, nph), **kw)
+            assert_spot_and_focus(c, spot, focus, ref_spot, ref_focus)
+    if nd * nph > 1000:
+        return
+    fin = bc.oracle_finals("c2", "float64", nd, nph)
+    refs = np.array(bc.oracle_refs("c2"))
+    refs[..., 0:3] = analysis.summarize(oracle_sums("c2", "float64", nd, nph)[0])["centroid"]
+    exp = W.fixed_order_wave_sums(fin, nd * nph, refs.reshape(-1, 8)).reshape(refs.shape[:2] + (15,))
+    got, _ = analysis.collimated_wavefront_sweep(*bc.sweep_args(c, nd, nph), pt=c.pts, device=DEV, refs=refs)
+    assert same_int64(got["raw"], exp) and (got["count"] == nd * nph).all()
+
+
+@pytest.mark.parametrize("nw", [1, 2, 3, 5, 9])
+def test_row_planning_over_wavelength_counts(nw):
+    """Two directions at one point and a third beam elsewhere, nw wavelengths each: no bundle row (1), one row of two,
+    a row and a single (3), a row of four and a single (5), a full row of eight and a leftover single (9, more than
+    kMaxBundle = 8); groups_per_batch splits the groups into several launches, inside a beam's wavelengths too; a
+    non-zero phi_start."""
+    c = bc.case("same_pt")
+    normals = np.concatenate([c.normals, c.normals[:1]])
+    pts = np.concatenate([c.pts, [[0.5, -1.0, -4.0]]])
+    wls = np.linspace(0.65, 1.0, nw).tolist()
+    nd, nph, phi0 = 37, 8, 0.7
+    fin = np.concatenate([O.ray_trace(c.S, c.M, rt.get_collimated_rays(p, c.dmax, nd, w, nph, phi0, n))[-1]
+                          for p, n in zip(pts, normals) for w in wls])
+    ref_spot = fixed_order_sums(fin, nd * nph).reshape(3, nw, 7)
+    ref_focus = fixed_order_focus_sums(fin, nd * nph).reshape(3, nw, 16)
+    assert (ref_spot[..., 0] == nd * nph).all()
+    assert not np.array_equal(ref_spot[0], ref_spot[1]) and not np.array_equal(ref_spot[0], ref_spot[2])
+    args = (c.system, c.m0, c.m1, normals, wls, c.dmax, nd, nph, phi0)
+    for gpb in (None, max(2, (3 * nw) // 2 + 1), 2 * nw - 1 if nw > 1 else 2):
+        spot, _ = analysis.collimated_spot_sweep(*args, pt=pts, device=DEV, groups_per_batch=gpb)
+        focus, _ = analysis.collimated_focus_sweep(*args, pt=pts, device=DEV, groups_per_batch=gpb)
+        assert_spot_and_focus(c, spot, focus, ref_spot, ref_focus)
+    windows = analysis.auto_image_windows(analysis.summarize(ref_spot), BINS, sigmas=1.5)
+    exp_image, exp_outside = image_of_plane(fin, nd * nph, windows.reshape(-1, 4), *BINS)
+    got, _ = analysis.collimated_image_sweep(*args, pt=pts, device=DEV, bins=BINS, windows=windows,
+                                             groups_per_batch=2 * nw - 1 if nw > 1 else 2)
+    assert np.array_equal(got["image"], exp_image.reshape(got["image"].shape))
+    assert np.array_equal(got["outside"], exp_outside.reshape(3, nw))
+
+
+def test_sweeps_over_devices_are_bitwise_equal():
+    """devices=: two shards on GPU 0 (plus every visible GPU when there are several) give the one-device result bit
+    for bit, for the four sweeps."""
+    c = bc.case("same_pt")
+    args = bc.sweep_args(c)
+    refs = bc.oracle_refs("same_pt")
+    windows = analysis.auto_image_windows(analysis.summarize(oracle_sums("same_pt", "float64")[0]), BINS, 1.5)
+    calls = [(analysis.collimated_spot_sweep, {}), (analysis.collimated_focus_sweep, {}),
+             (analysis.collimated_wavefront_sweep, dict(refs=refs)),
+             (analysis.collimated_image_sweep, dict(bins=BINS, windows=windows))]
+    lists = [[0, 0]] + ([list(range(torch.cuda.device_count()))] if torch.cuda.device_count() > 1 else [])
+    for fn, kw in calls:
+        one, t1 = fn(*args, pt=c.pts, device=DEV, groups_per_batch=4, **kw)
+        for devs in lists:
+            many, tm = fn(*args, pt=c.pts, devices=devs, groups_per_batch=4, **kw)
+            assert_same_summary(many, one)
+            assert [p["device"] for p in tm["per_device"]] == devs
+            assert sum(p["rays"] for p in tm["per_device"]) == t1["rays"]
+
+
+def test_wavefront_refs_are_the_spot_centroid_and_the_oracles_chief_ray():
+    """collimated_wavefront_refs on C2: C0 is the collimated spot sweep's centroid, d0 and p0 the oracle's chief ray,
+    bit for bit, kf is n_final / wavelength; refs=None sweeps against exactly these; windows=None images use the
+    spot sweep's windows."""
+    c = bc.case("c2")
+    args = bc.sweep_args(c)
+    spot, _ = analysis.collimated_spot_sweep(*args, pt=c.pts, device=DEV)
+    beam_kw = dict(displacement_max=c.dmax, n_disps=c.nd, nphis=c.nph, phi_start=c.phi_start)
+    refs = analysis.collimated_wavefront_refs(*args[:5], pt=c.pts, device=DEV, **beam_kw)
+    assert refs.shape == (len(c.normals), len(c.wls), 8)
+    assert same_bits(refs[..., 0:3], spot["centroid"])
+    assert same_bits(refs, analysis.collimated_wavefront_refs(*args[:5], pt=c.pts, spot_summary=spot, device=DEV))
+    for i, (p, n) in enumerate(zip(c.pts, c.normals)):
+        for j, wl in enumerate(c.wls):
+            chief = bc.oracle_chief(c, p, n, wl)
+            assert same_bits(refs[i, j, 3:7], chief[3:7]), (i, j)
+            assert refs[i, j, 7] == float(c.m1.n(wl)) / wl
+    auto, _ = analysis.collimated_wavefront_sweep(*args, pt=c.pts, device=DEV)
+    given, _ = analysis.collimated_wavefront_sweep(*args, pt=c.pts, device=DEV, refs=refs)
+    assert_same_summary(auto, given)
+    img_auto, _ = analysis.collimated_image_sweep(*args, pt=c.pts, device=DEV, bins=BINS)
+    img, _ = analysis.collimated_image_sweep(*args, pt=c.pts, device=DEV, bins=BINS,
+                                             windows=analysis.auto_image_windows(spot, BINS))
+    assert np.array_equal(img_auto["image"], img["image"]) and img["image"].sum() > 0
+
+
+def test_perfect_lens_focuses_a_collimated_beam_to_a_point():
+    """A PerfectLens of focal length f with an image plane at f; beams on axis, 2 degrees off in x and 3 degrees off in
+    y.  The lens obeys the sine condition: the beam along n focuses at f (nx, ny).  Spot RMS radius and RMS wavefront
+    error are zero to rounding, and every bound is ten times the oracle's own figure, computed here on the CPU from
+    the oracle's final planes with the same summaries:
+
+    - rms_radius: the oracle gives 0, 3.65e-08 and 0 (the one-pass variance S_xx / n - mean^2 cancels at 1.7 mm);
+      bound 10 x the largest, 3.65e-07 mm;
+    - rms_opd about the oracle's centroid and chief ray: 0, 8.9e-15 and 1.3e-14 waves; bound 10 x the largest,
+      1.3e-13 waves;
+    - centroid against f (nx, ny): the oracle's largest deviation, times ten, and no less than 4 eps f (the spacing
+      of float64 at the centroid's size)."""
+    f, wl = 50.0, 0.55
+    vac = mat.Vacuum()
+    system = rt.System([rt.PerfectLens(f, [0, 0, 0], [0, 0, 1], 0.6), rt.FlatSurface([0, 0, f], [0, 0, 1], 50.0)],
+                       [vac])
+    S = [surface_to_dict(s) for s in system.surfaces]
+    M = [material_to_dict(m) for m in [vac, vac, vac]]
+    deg = np.pi / 180
+    normals = np.array([[0.0, 0.0, 1.0], bc.unit([np.sin(2 * deg), 0.0, np.cos(2 * deg)]),
+                        bc.unit([0.0, np.sin(3 * deg), np.cos(3 * deg)])])
+    pt, dmax, nd, nph = [0.0, 0.0, -10.0], 5.0, 41, 12
+    per = nd * nph
+    fin = np.concatenate([O.ray_trace(S, M, rt.get_collimated_rays(pt, dmax, nd, wl, nph, 0.0, n))[-1]
+                          for n in normals])
+    ref_spot = analysis.summarize(fixed_order_sums(fin, per).reshape(3, 1, 7))
+    assert (ref_spot["count"] == per).all()
+    refs = np.empty((3, 1, 8))
+    for i, n in enumerate(normals):
+        chief = O.ray_trace(S, M, rt.get_collimated_rays(pt, 0, 1, wl, normal=n))[-1][0]
+        refs[i, 0] = np.r_[ref_spot["centroid"][i, 0], chief[3:7], float(vac.n(wl)) / wl]
+    ref_wave = analysis.summarize_wavefront(
+        W.fixed_order_wave_sums(fin, per, refs.reshape(-1, 8)).reshape(3, 1, 15), refs)
+    closed = f * normals[:, None, :2]
+    b_rms = 10 * ref_spot["rms_radius"].max()
+    b_opd = 10 * ref_wave["rms_opd"].max()
+    b_cen = max(10 * np.abs(ref_spot["centroid"][..., :2] - closed).max(), 4 * EPS * f)
+    print("oracle rms_radius", ref_spot["rms_radius"].ravel(), "rms_opd", ref_wave["rms_opd"].ravel(),
+          "bounds", b_rms, b_opd, b_cen)
+    assert 0 < b_rms < 1e-6 and 0 < b_opd < 1e-12 and b_cen < 1e-12
+    args = (system, vac, vac, normals, [wl], dmax, nd, nph, 0.0)
+    spot, _ = analysis.collimated_spot_sweep(*args, pt=pt, device=DEV)
+    wave, _ = analysis.collimated_wavefront_sweep(*args, pt=pt, device=DEV, refs=refs)
+    print("rms_radius", spot["rms_radius"].ravel(), "rms_opd", wave["rms_opd"].ravel())
+    assert (spot["count"] == per).all() and (wave["count"] == per).all()
+    assert (spot["rms_radius"] <= b_rms).all()
+    assert (wave["rms_opd"] <= b_opd).all()
+    assert (np.abs(spot["centroid"][..., :2] - closed) <= b_cen).all()
+    assert (spot["centroid"][..., 2] == f).all()
+
+
+def test_fan_sweeps_keep_their_answers_on_c2():
+    """The regression guard: the fan sweeps' C2 case still gives the oracle's bits through the shared drivers."""
+    c = sc.case("c2")
+    fin = sc.oracle_finals("c2", "float64")
+    shape = (len(c.fields), len(c.wls))
+    ref_spot = fixed_order_sums(fin, c.nt * c.nph).reshape(shape + (7,))
+    ref_focus = fixed_order_focus_sums(fin, c.nt * c.nph).reshape(shape + (16,))
+    for fused in (True, False):
+        kw = dict(center_ray=c.center_ray, device=DEV, fused=fused, groups_per_batch=c.gpb)
+        spot, _ = analysis.spot_sweep(*sc.sweep_args(c), **kw)
+        focus, _ = analysis.focus_sweep(*sc.sweep_args(c), **kw)
+        assert same_int64(spot["raw"], ref_spot) and same_int64(focus["raw"], ref_focus)
