@@ -57,8 +57,9 @@ extern "C" {
                                 10: + rtpb_focus_stats / rtpb_focus_sweep (through-focus statistics);
                                     rtpb_spot_image / rtpb_image_sweep (spot images) and
                                     rtpb_wavefront_stats / rtpb_wavefront_sweep (wavefront statistics) and the
-                                    four rtpb_*_sweep_collimated (collimated-beam sweeps) joined within 10: new
-                                    symbols only, nothing existing changed */
+                                    four rtpb_*_sweep_collimated (collimated-beam sweeps) joined within 10, and
+                                    so did rtpb_focus_sweep_variants / _variants_collimated (many systems in one
+                                    fused pass): new symbols only, nothing existing changed */
 
 /* ---- error codes ---------------------------------------------------------------------------- */
 #define RTPB_OK 0
@@ -500,6 +501,41 @@ int rtpb_image_sweep_collimated(const rtpb_plan* plan, int32_t device, int64_t n
                                 const double* group_frames, int64_t n_disps, int64_t nphis, const double* offsets,
                                 const double* phi_cos_sin, const double* windows, int32_t nx, int32_t ny,
                                 int32_t* image_out, int32_t* outside_out, void* stream);
+
+/* VARIANT sweeps (tolerance runs): rtpb_focus_sweep / rtpb_focus_sweep_collimated over MANY systems in one call.
+   The systems come in the call, as in rtpb_trace_f64: there is no plan and no per-system device memory.
+   surfaces: HOST, n_variants x nsurf descriptors, variant v's at surfaces + v * nsurf; materials: HOST, n_variants x
+   (nsurf + 1), variant v's at materials + v * (nsurf + 1) (initial medium, the media between the surfaces, final
+   medium).  Every variant has the same number of surfaces; their kinds, geometry and media may all differ.
+   dtype: the storage type (RTPB_F64 / RTPB_F32), a plan's dtype.  group_variant: HOST, n_groups, the variant in
+   [0, n_variants) group g is traced through.  The remaining arguments are those of rtpb_focus_sweep from n_thetas on
+   (rtpb_focus_sweep_collimated from group_frames on), and stats_out (DEVICE, n_groups x 16) holds the same sums.
+   CONTRACT: the statistics of a group of variant v are bit-identical to those rtpb_focus_sweep[_collimated] gives
+   the same group on a plan created (rtpb_plan_create) from variant v's descriptors with storage type dtype --
+   whatever other variants and groups the call holds.  Groups are swept together when they share the source of their
+   rays (the point; for beams the frame too) AND the variant, so a call should hold all the wavelengths of a field.
+   Each variant is checked and lowered on the host by rtpb_plan_create's own code, and its descriptors ride in the
+   call's one upload.  Media are evaluated on the host: a RTPB_POLY6 material (whose device arithmetic the host does
+   not reproduce) is RTPB_E_INVALID -- lower it as RTPB_TABLE at the call's wavelengths.
+   Everything is checked before the device is touched.  RTPB_E_INVALID: a NULL pointer, a non-positive nsurf,
+   n_variants, n_groups or table size, a short workspace (n_groups * ceil(rays per group / 256) * 16 doubles), a
+   group_variant entry outside [0, n_variants), a bad descriptor, a POLY6 material.  RTPB_E_LIMIT: nsurf >
+   RTPB_MAX_SURFACES, n_groups > 65535, or an upload beyond RTPB_MAX_VARIANT_UPLOAD bytes, counted as
+       16 (n_thetas + nphis) + n_groups (8 (4 nsurf + 5) + 12) + 280 n_variants nsurf
+   (a collimated call: 72 n_groups more) -- split such a run into several calls. */
+#define RTPB_MAX_VARIANT_UPLOAD (256ll << 20)
+int rtpb_focus_sweep_variants(const rtpb_surface* surfaces, int32_t nsurf, const rtpb_material* materials,
+                              int32_t n_variants, int32_t dtype, int32_t device, int64_t n_groups,
+                              const double* group_params, const int32_t* group_variant, int64_t n_thetas,
+                              int64_t nphis, const double center_ray[3], const double ex[3], const double ey[3],
+                              const double* theta_cos_sin, const double* phi_cos_sin, double* workspace,
+                              int64_t workspace_len, double* stats_out, void* stream);
+int rtpb_focus_sweep_variants_collimated(const rtpb_surface* surfaces, int32_t nsurf, const rtpb_material* materials,
+                                         int32_t n_variants, int32_t dtype, int32_t device, int64_t n_groups,
+                                         const double* group_params, const int32_t* group_variant,
+                                         const double* group_frames, int64_t n_disps, int64_t nphis,
+                                         const double* offsets, const double* phi_cos_sin, double* workspace,
+                                         int64_t workspace_len, double* stats_out, void* stream);
 
 /* ---- pupil-phase interpolation (scripts/2022_02_06_perfect_imaging_system_psf.py:90-105) */
 /* A 2-D Delaunay triangulation with one value per vertex, in scipy.spatial.Delaunay's representation,

@@ -122,7 +122,12 @@ SIGNATURES = {
                                                        _P]),
     "rtpb_image_sweep_collimated": (ctypes.c_int, [_P, _i32, _i64, _P, _P, _i64, _i64, _P, _P, _P, _i32, _i32, _P, _P,
                                                    _P]),
-    "rtpb_set_tuning": (ctypes.c_int, [ctypes.c_char_p, _i64]),
+    # (the descriptor arrays as plain addresses: a batch passes the variants it touches, an offset into them)
+    "rtpb_focus_sweep_variants": (ctypes.c_int, [_P, _i32, _P, _i32, _i32, _i32, _i64, _P, _P, _i64, _i64, _P, _P, _P,
+                                                 _P, _P, _P, _i64, _P, _P]),
+    "rtpb_focus_sweep_variants_collimated": (ctypes.c_int, [_P, _i32, _P, _i32, _i32, _i32, _i64, _P, _P, _P, _i64,
+                                                            _i64, _P, _P, _P, _i64, _P, _P]),
+    "rtpb_set_tuning":(ctypes.c_int, [ctypes.c_char_p, _i64]),
     "rtpb_timing_enable": (ctypes.c_int, [_i32]),
     "rtpb_timing_collect": (ctypes.c_int, [ctypes.POINTER(_dbl), ctypes.POINTER(_i64)]),
 }

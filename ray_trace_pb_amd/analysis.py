@@ -7,8 +7,13 @@ on the GPU with a deterministic fixed-order reduction (``rtpb_spot_stats``) -- o
 images of integer counts (``rtpb_spot_image``, :func:`image_sweep`), or reduced to the moments of the optical path
 difference (``rtpb_wavefront_stats``, :func:`wavefront_sweep`: RMS wavefront error, diffraction focus, Strehl).
 The ``collimated_*`` sweeps run the same four analyses on ``get_collimated_rays`` beams, one per (field direction,
-wavelength): objects at infinity (``rtpb_*_sweep_collimated``).
+wavelength): objects at infinity (``rtpb_*_sweep_collimated``).  :func:`variant_focus_sweep` and
+:func:`collimated_variant_focus_sweep` run the focus analysis over many systems in one fused pass -- the perturbed
+copies of a tolerance run, which :func:`rigid_move` builds (``rtpb_focus_sweep_variants[_collimated]``).
 """
+import contextlib
+import copy
+import ctypes
 import time
 from types import SimpleNamespace
 
@@ -418,8 +423,9 @@ def _grid(field_points, wavelengths):
 #   nf, nw, per     fields (field points, or beams), wavelengths and rays per group; group = field * nw + wavelength
 #   wavelengths     (nw,) float64
 #   suffix          of the fused C entry point's name after the mode's
-#   head()          -> head(b0, b1): the entry's arguments from group_params up to the mode's tail, for groups
-#                   [b0, b1), and the host arrays they point into (to be kept until the call returns)
+#   head(copies=1)  -> head(b0, b1): the entry's arguments from group_params up to the mode's tail, for groups
+#                   [b0, b1), and the host arrays they point into (to be kept until the call returns); with ``copies``
+#                   the groups repeat that many times (a variant source's: one copy per system)
 #   into(buf, g)    unfused: group g's rays written into the device buffer ``buf``
 def _fan_source(field_points, wavelengths, theta_max, n_thetas, nphis, center_ray):
     """The point-source fans of the four sweeps: ``get_ray_fan(field, theta_max, n_thetas, wavelength, nphis,
@@ -429,13 +435,14 @@ def _fan_source(field_points, wavelengths, theta_max, n_thetas, nphis, center_ra
     field_points, wavelengths = _grid(field_points, wavelengths)
     nf, nw = field_points.shape[0], wavelengths.size
 
-    def head():
+    def head(copies=1):
         from .raytrace import _fan_tables
         c = np.array(center_ray)
         enx, eny, tcs, pcs = _fan_tables(float(theta_max), int(n_thetas), int(nphis), tuple(c.tolist()), c.dtype.str)
         params = np.empty((nf * nw, 4))
         params[:, 0:3] = np.repeat(field_points, nw, axis=0)          # group = field * nw + wavelength
         params[:, 3] = np.tile(wavelengths, nf)
+        params = np.tile(params, (copies, 1))
         vec = [np.ascontiguousarray(np.asarray(v, dtype=np.float64).ravel()) for v in (c, enx, eny)]
 
         def args(b0, b1):
@@ -476,15 +483,16 @@ def _beam_source(normals, wavelengths, displacement_max, n_disps, nphis, phi_sta
     wavelengths = np.atleast_1d(np.asarray(wavelengths, dtype=float))
     nf, nw = normals.shape[0], wavelengths.size
 
-    def head():
+    def head(copies=1):
         from .raytrace import _collimated_frame, _collimated_tables
         offs, pcs = _collimated_tables(displacement_max, int(n_disps), int(nphis), phi_start)
         frames = np.array([np.concatenate([np.asarray(v, dtype=np.float64) for v in _collimated_frame(n)])
                            for n in normals])
-        frames = np.ascontiguousarray(np.repeat(frames, nw, axis=0))
+        frames = np.ascontiguousarray(np.tile(np.repeat(frames, nw, axis=0), (copies, 1)))
         params = np.empty((nf * nw, 4))
         params[:, 0:3] = np.repeat(pts, nw, axis=0)
         params[:, 3] = np.tile(wavelengths, nf)
+        params = np.tile(params, (copies, 1))
 
         def args(b0, b1):
             gp, fr = np.ascontiguousarray(params[b0:b1]), np.ascontiguousarray(frames[b0:b1])
@@ -504,19 +512,22 @@ def _beam_source(normals, wavelengths, displacement_max, n_disps, nphis, phi_sta
 def _sweep(mode, system, initial_material, final_material, source, device, dtype, groups_per_batch, fused, devices):
     """What the public sweeps share: the argument checks, the lowered system, one of the two drivers, the timing
     dict and the mode's host summary.  ``source`` says what a group's rays are (:func:`_fan_source`,
-    :func:`_beam_source`)."""
+    :func:`_beam_source`; a :func:`_variant_source` carries its own systems, and ``system`` is None)."""
     if devices is not None and not fused:
         raise ValueError("devices= needs the fused sweep")
     import torch
     dev = torch.device(device)
     tdt = torch.float64 if dtype in ("float64", np.float64) else torch.float32
     wavelengths = source.wavelengths
-    mats = [initial_material] + list(system.materials) + [final_material]
     # tabulated materials are lowered at the wavelengths the kernels see: the group's wavelength rounded to the
     # storage type (a float32 sweep's rays carry float32 wavelengths, and the table lookup matches exactly)
     keys = wavelengths if tdt == torch.float64 else wavelengths.astype(np.float32).astype(np.float64)
-    low = E.lower(system.surfaces, mats, lambda: np.unique(keys), C.RTPB_F64 if tdt == torch.float64 else C.RTPB_F32)
-    S = len(system.surfaces)
+    code = C.RTPB_F64 if tdt == torch.float64 else C.RTPB_F32
+    if system is None:
+        low, S = source.lower(keys, code), source.nsurf
+    else:
+        mats = [initial_material] + list(system.materials) + [final_material]
+        low, S = E.lower(system.surfaces, mats, lambda: np.unique(keys), code), len(system.surfaces)
     if fused:
         devs = [dev] if devices is None else [torch.device("cuda", int(d)) for d in devices]
         arrays, dt, extra = _sweep_fused(mode, low, S, source, devs, groups_per_batch)
@@ -598,13 +609,16 @@ def _sweep_fused(mode, low, S, source, devs, groups_per_batch):
         torch.cuda.synchronize(dev)
     t0 = time.perf_counter()
     sweep = getattr(C.lib(), mode.entry + source.suffix)
-    with E.plan_ref(low) as plan:
+    # a plan of the lowered system leads the call's arguments -- or, for a variant source, the systems themselves
+    lead = getattr(source, "lead", None)
+    with (E.plan_ref(low) if lead is None else contextlib.nullcontext()) as plan:
         for *_, ev, st in work:
             ev[0].record(st)
         for slot, b0, b1 in launches:
             dev, _, _, tail, _, st = work[slot]
             args, keep = head(b0, b1)
-            C.check(sweep(plan, dev.index or 0, b1 - b0, *args, *tail(b0, b1), st.cuda_stream))
+            first = (plan,) if lead is None else lead(low, b0, b1)
+            C.check(sweep(*first, dev.index or 0, b1 - b0, *args, *tail(b0, b1), st.cuda_stream))
             del keep
         for *_, ev, st in work:
             ev[1].record(st)
@@ -855,6 +869,180 @@ def collimated_wavefront_sweep(system, initial_material, final_material, normals
     refs = _wave_refs(refs, (source.nf, source.nw, 8))
     return _sweep(_wave_mode(refs), system, initial_material, final_material, source, device, "float64",
                   groups_per_batch, fused, devices)
+
+
+def rigid_move(system, surfaces, shift=(0, 0, 0), tilt=(0, 0), pivot=None):
+    """A new ``System`` in which the surfaces with indices ``surfaces`` are copies moved together as one rigid body --
+    an element decentred, despaced or tilted: the perturbation of a tolerance run (:func:`variant_focus_sweep`).
+
+    The body is first rotated by ``tilt`` = (angle about x, angle about y) in radians, about x and then about y,
+    through ``pivot`` (default: the ``center`` of the first listed surface), then translated by ``shift``.  Points
+    (``center``, ``paraxial_center``) are rotated and translated; directions (``normal``, ``input_axis``,
+    ``output_axis``, where the surface has them) are rotated.  The other surfaces are shared with ``system``, which is
+    left as it was, and so are the materials.  A zero angle skips its rotation and a zero shift component its sum, so
+    a zero move lowers to the same descriptors bit for bit (signed zeros included)."""
+    from .raytrace import System
+    idx = [int(k) for k in surfaces]
+    n = len(system.surfaces)
+    if not idx or any(k < -n or k >= n for k in idx):
+        raise ValueError("rigid_move: surfaces must be a non-empty sequence of surface indices of the system")
+    shift = np.asarray(shift, dtype=float).ravel()
+    tilt = np.asarray(tilt, dtype=float).ravel()
+    if shift.shape != (3,) or tilt.shape != (2,):
+        raise ValueError("rigid_move: shift is (dx, dy, dz) and tilt (angle about x, angle about y)")
+    moved = list(system.surfaces)
+    for k in idx:
+        moved[k] = copy.deepcopy(system.surfaces[k])
+    pivot = np.array(moved[idx[0]].center if pivot is None else pivot, dtype=float).ravel()
+    if pivot.shape != (3,):
+        raise ValueError("rigid_move: pivot is a point (x, y, z)")
+    rot = None
+    for axis, angle in enumerate(tilt):
+        if angle != 0:
+            c, s = np.cos(angle), np.sin(angle)
+            r = np.array([[1, 0, 0], [0, c, -s], [0, s, c]]) if axis == 0 else np.array([[c, 0, s], [0, 1, 0],
+                                                                                         [-s, 0, c]])
+            rot = r if rot is None else r @ rot
+    for k in idx:
+        sf = moved[k]
+        for name in ("center", "paraxial_center"):
+            v = np.array(getattr(sf, name), dtype=float)
+            if rot is not None:
+                v = pivot + rot @ (v - pivot)
+            for j in range(3):
+                if shift[j] != 0:
+                    v[j] = v[j] + shift[j]
+            setattr(sf, name, v)
+        if rot is not None:
+            for name in ("normal", "input_axis", "output_axis"):
+                if hasattr(sf, name):
+                    setattr(sf, name, rot @ np.asarray(getattr(sf, name), dtype=float))
+    return System(moved, list(system.materials), names=list(system.names),
+                  surfaces_by_name=np.array(system.surfaces_by_name), aperture_stop=system.aperture_stop)
+
+
+def _variant_source(systems, initial_material, final_material, inner):
+    """The groups of ``inner`` (:func:`_fan_source`, :func:`_beam_source`) once per system: a sweep source of
+    len(systems) * inner.nf "fields", group = (variant * n_fields + field) * n_wavelengths + wavelength, so the single
+    driver cuts its batches at whole field points of whole or partial variants.  The fused call takes the systems'
+    descriptors in place of a plan (``lower``, ``lead``): a batch passes those of the variants it touches, and its
+    ``group_variant`` counts from the first of them."""
+    V, per_variant = len(systems), inner.nf * inner.nw
+    S = len(systems[0].surfaces)
+    src = SimpleNamespace(nf=V * inner.nf, nw=inner.nw, per=inner.per, wavelengths=inner.wavelengths,
+                          suffix="_variants" + inner.suffix, nsurf=S, systems=systems, lower_seconds=0.0)
+
+    def lower(keys, code):
+        # each system through E.lower (its content memo, not the plan cache), the descriptors side by side
+        t0 = time.perf_counter()
+        lows = [E.lower(s.surfaces, [initial_material] + list(s.materials) + [final_material],
+                        lambda: np.unique(keys), code) for s in systems]
+        surf, mats = (C.Surface * (V * S))(), (C.Material * (V * (S + 1)))()
+        ns, nm = S * ctypes.sizeof(C.Surface), (S + 1) * ctypes.sizeof(C.Material)
+        for v, low in enumerate(lows):
+            ctypes.memmove(ctypes.addressof(surf) + v * ns, low.surfaces, ns)
+            ctypes.memmove(ctypes.addressof(mats) + v * nm, low.materials, nm)     # (TABLE pointers: into lows)
+        src.lower_seconds = time.perf_counter() - t0
+        return SimpleNamespace(surf=surf, mats=mats, ns=ns, nm=nm, dtype=code, keep=lows)
+
+    def lead(low, b0, b1):
+        v0, v1 = b0 // per_variant, (b1 - 1) // per_variant + 1
+        return (ctypes.addressof(low.surf) + v0 * low.ns, S, ctypes.addressof(low.mats) + v0 * low.nm, v1 - v0,
+                low.dtype)
+
+    def head():
+        inner_args = inner.head(V)
+
+        def args(b0, b1):
+            a, keep = inner_args(b0, b1)
+            gv = (np.arange(b0, b1) // per_variant - b0 // per_variant).astype(np.int32)
+            return a[:1] + (gv.ctypes.data,) + a[1:], (keep, gv)
+        return args
+
+    src.lower, src.lead, src.head = lower, lead, head
+    return src
+
+
+# the library's bound on the upload of one variant call (include/rtpb.h RTPB_MAX_VARIANT_UPLOAD)
+_VARIANT_UPLOAD_MAX = 256 << 20
+
+
+def _variant_sweep(what, systems, initial_material, final_material, inner, device, dtype, groups_per_batch, fused,
+                   devices, require_image_plane):
+    """What the two variant sweeps share: the checks (before any device call), the fused call through the single
+    driver or, unfused, one ordinary unfused sweep per system, and the summary shaped (n_variants, ...)."""
+    systems = list(systems)
+    if not systems:
+        raise ValueError(what + ": systems is empty")
+    S = len(systems[0].surfaces)
+    if S == 0 or any(len(s.surfaces) != S for s in systems):
+        raise ValueError(what + ": every system must have the same, non-zero number of surfaces")
+    if S > C.RTPB_MAX_SURFACES:
+        raise ValueError(f"at most {C.RTPB_MAX_SURFACES} surfaces per trace")
+    if devices is not None and not fused:
+        raise ValueError("devices= needs the fused sweep")
+    for s in systems:
+        _require_image_plane(s, require_image_plane)
+    V, nf, nw = len(systems), inner.nf, inner.nw
+    if not fused:
+        raws, seconds = [], 0.0
+        for s in systems:
+            one, t = _sweep(_FOCUS, s, initial_material, final_material, inner, device, dtype, groups_per_batch,
+                            False, None)
+            raws.append(one["raw"])
+            seconds += t["seconds"]
+        rays = V * nf * nw * inner.per
+        return summarize_focus(np.stack(raws)), {"seconds": seconds, "rays": rays,
+                                                 "ray_surface_per_s": rays * S / seconds, "variants": V}
+    if groups_per_batch is None:
+        # the library bounds a call's upload: a group's own words and its share of the descriptors, with a margin
+        # of two for the tables and a batch's partial variants; the workspace bound is _sweep_plan's
+        per_group = 8 * (4 * S + 5) + 12 + 72 + -(-280 * S // (nf * nw))
+        groups_per_batch = max(1, min(V * nf * nw, 65535, _VARIANT_UPLOAD_MAX // 2 // per_group,
+                                      (1 << 26) // (-(-inner.per // 256) * 16)))
+        if groups_per_batch >= nw:
+            groups_per_batch -= groups_per_batch % nw
+    source = _variant_source(systems, initial_material, final_material, inner)
+    mode = SimpleNamespace(**vars(_FOCUS))
+    mode.finish = lambda nf_all, nw_, raw: summarize_focus(raw.reshape(V, nf, nw, 16))
+    summary, timing = _sweep(mode, None, initial_material, final_material, source, device, dtype, groups_per_batch,
+                             fused, devices)
+    timing.update(variants=V, lower_seconds=source.lower_seconds)
+    return summary, timing
+
+
+def variant_focus_sweep(systems, initial_material, final_material, field_points, wavelengths, theta_max, n_thetas,
+                        nphis=1, center_ray=(0, 0, 1), device="cuda:0", dtype="float64", groups_per_batch=None,
+                        fused=True, devices=None, require_image_plane=True):
+    """:func:`focus_sweep` over MANY systems in one fused pass -- a Monte-Carlo tolerance run, or an optimiser's
+    population: ``systems`` is a sequence of ``System`` objects with equal numbers of surfaces (perturbed copies of
+    one design, :func:`rigid_move`; their surface kinds, geometry and media may all differ), and every (system, field
+    point, wavelength) is one group of ``rtpb_focus_sweep_variants``.  No plan is created and no per-system device
+    memory: the lowered descriptors of all systems ride in the sweep's one upload, and a group's statistics are
+    bit-identical to :func:`focus_sweep` of its system alone.
+
+    Returns (:func:`summarize_focus` summary with arrays shaped (n_variants, n_fields, n_wavelengths, ...), timing
+    dict as :func:`focus_sweep`'s plus ``"variants"`` and ``"lower_seconds"``, the host time spent lowering the
+    systems): RMS spot, best focus -- the usual compensator -- the RMS radius there and astigmatism per variant.
+    ``fused=False`` runs each system through :func:`focus_sweep`'s unfused pipeline (bit-identical; for tests).
+    POLY6 media are refused by the library (their device arithmetic is not the host's).  ``ValueError`` before any
+    device call: an empty ``systems``, unequal numbers of surfaces, a system without an image plane normal to z
+    (unless ``require_image_plane=False``)."""
+    return _variant_sweep("variant_focus_sweep", systems, initial_material, final_material,
+                          _fan_source(field_points, wavelengths, theta_max, n_thetas, nphis, center_ray), device,
+                          dtype, groups_per_batch, fused, devices, require_image_plane)
+
+
+def collimated_variant_focus_sweep(systems, initial_material, final_material, normals, wavelengths,
+                                   displacement_max, n_disps, nphis=1, phi_start=0., pt=(0, 0, 0), device="cuda:0",
+                                   dtype="float64", groups_per_batch=None, fused=True, devices=None,
+                                   require_image_plane=True):
+    """:func:`variant_focus_sweep` with :func:`collimated_focus_sweep`'s beams (objects at infinity):
+    ``rtpb_focus_sweep_variants_collimated``; a group's statistics are bit-identical to
+    :func:`collimated_focus_sweep` of its system alone."""
+    return _variant_sweep("collimated_variant_focus_sweep", systems, initial_material, final_material,
+                          _beam_source(normals, wavelengths, displacement_max, n_disps, nphis, phi_start, pt), device,
+                          dtype, groups_per_batch, fused, devices, require_image_plane)
 
 
 class GridInterpolator:

@@ -93,14 +93,59 @@ void build_indexed(rtpb_plan& p) {
     p.feat = (p.feat & ~(4 | 8)) | 16;
 }
 
+// The device descriptor of plan surface k: its geometry and the media on either side.
+DevSurface<double> plan_surface(const rtpb_plan& p, size_t k) {
+    DevSurface<double> d = lower_surface(p.surf[k]);
+    lower_surface_media(d, device_material(p, k), device_material(p, k + 1));
+    return d;
+}
+
+// The checks and the host-side lowering of rtpb_plan_create: the descriptors copied into `p`, the TABLE materials'
+// pairs sorted into p.table, the feature bits 1 / 2 / 4 / 8.  The message of a failure is set.
+int plan_fill(rtpb_plan& p, const rtpb_surface* surfaces, int32_t nsurf, const rtpb_material* materials, int32_t nmat,
+              int32_t dtype) {
+    if (nsurf < 0 || (nsurf > 0 && !surfaces)) return fail(RTPB_E_INVALID, "bad surfaces array");
+    if (nsurf > RTPB_MAX_SURFACES)
+        return fail(RTPB_E_LIMIT, "more than RTPB_MAX_SURFACES (" + std::to_string(RTPB_MAX_SURFACES) + ") surfaces");
+    if (nmat != nsurf + 1 || !materials)
+        return fail(RTPB_E_INVALID, "length of materials should be len(surfaces) + 1");
+    if (dtype != RTPB_F64 && dtype != RTPB_F32) return fail(RTPB_E_INVALID, "dtype must be RTPB_F64 or RTPB_F32");
+    p.dtype = dtype;
+    p.nsurf = nsurf;
+    for (int k = 0; k < nsurf; ++k) {
+        if (surfaces[k].kind < RTPB_FLAT || surfaces[k].kind > RTPB_PERFECT_LENS)
+            return fail(RTPB_E_INVALID, "surface " + std::to_string(k) + ": unknown kind");
+        p.surf.push_back(surfaces[k]);
+        if (surfaces[k].kind == RTPB_PERFECT_LENS) p.feat |= 1;
+    }
+    for (int k = 0; k < nmat; ++k) {
+        rtpb_material m = materials[k];
+        if (m.kind < RTPB_CONSTANT || m.kind > RTPB_TABLE)
+            return fail(RTPB_E_INVALID, "material " + std::to_string(k) + ": unknown kind");
+        p.table_off.push_back(static_cast<int32_t>(p.table.size() / 2));
+        if (m.kind == RTPB_POLY6) p.feat |= 3;
+        if (m.kind == RTPB_TABLE) {
+            if (m.table_len <= 0 || !m.table)
+                return fail(RTPB_E_INVALID, "material " + std::to_string(k) + ": empty table");
+            if (p.table.size() / 2 + m.table_len > RTPB_MAX_TABLE)
+                return fail(RTPB_E_LIMIT, "more than RTPB_MAX_TABLE wavelength table entries");
+            p.table.insert(p.table.end(), m.table, m.table + 2 * m.table_len);
+            sort_table(p.table.data() + p.table.size() - 2 * m.table_len, m.table_len);
+        }
+        m.table = nullptr;
+        p.mats.push_back(m);
+    }
+    if (!p.table.empty()) p.feat |= (p.table.size() / 2 <= static_cast<size_t>(kLdsTablePairs)) ? 4 : 8;
+    return RTPB_OK;
+}
+
 template <typename T>
 std::vector<unsigned char> build_blob(const rtpb_plan& p) {
     const size_t S = p.surf.size(), M = p.mats.size(), off_mats = p.off_mats, off_table = p.off_table;
     std::vector<unsigned char> blob(p.blob_bytes, 0);
     auto* ds = reinterpret_cast<DevSurface<T>*>(blob.data());
     for (size_t k = 0; k < S; ++k) {
-        DevSurface<double> d = lower_surface(p.surf[k]);
-        lower_surface_media(d, device_material(p, k), device_material(p, k + 1));
+        const DevSurface<double> d = plan_surface(p, k);
         DevSurface<T>& o = ds[k];
         o.kind = d.kind;
         for (int j = 0; j < 3; ++j) {
@@ -174,48 +219,13 @@ int rtpb_plan_create(const rtpb_surface* surfaces, int32_t nsurf, const rtpb_mat
                      int32_t dtype, rtpb_plan** plan_out) {
     if (!plan_out) return fail(RTPB_E_INVALID, "plan_out is NULL");
     *plan_out = nullptr;
-    if (nsurf < 0 || (nsurf > 0 && !surfaces)) return fail(RTPB_E_INVALID, "bad surfaces array");
-    if (nsurf > RTPB_MAX_SURFACES)
-        return fail(RTPB_E_LIMIT, "more than RTPB_MAX_SURFACES (" + std::to_string(RTPB_MAX_SURFACES) + ") surfaces");
-    if (nmat != nsurf + 1 || !materials)
-        return fail(RTPB_E_INVALID, "length of materials should be len(surfaces) + 1");
-    if (dtype != RTPB_F64 && dtype != RTPB_F32) return fail(RTPB_E_INVALID, "dtype must be RTPB_F64 or RTPB_F32");
     auto* p = new (std::nothrow) rtpb_plan();
     if (!p) return fail(RTPB_E_INVALID, "out of host memory");
-    p->dtype = dtype;
-    p->nsurf = nsurf;
-    for (int k = 0; k < nsurf; ++k) {
-        if (surfaces[k].kind < RTPB_FLAT || surfaces[k].kind > RTPB_PERFECT_LENS) {
-            delete p;
-            return fail(RTPB_E_INVALID, "surface " + std::to_string(k) + ": unknown kind");
-        }
-        p->surf.push_back(surfaces[k]);
-        if (surfaces[k].kind == RTPB_PERFECT_LENS) p->feat |= 1;
+    const int rc = plan_fill(*p, surfaces, nsurf, materials, nmat, dtype);
+    if (rc) {
+        delete p;
+        return rc;
     }
-    for (int k = 0; k < nmat; ++k) {
-        rtpb_material m = materials[k];
-        if (m.kind < RTPB_CONSTANT || m.kind > RTPB_TABLE) {
-            delete p;
-            return fail(RTPB_E_INVALID, "material " + std::to_string(k) + ": unknown kind");
-        }
-        p->table_off.push_back(static_cast<int32_t>(p->table.size() / 2));
-        if (m.kind == RTPB_POLY6) p->feat |= 3;
-        if (m.kind == RTPB_TABLE) {
-            if (m.table_len <= 0 || !m.table) {
-                delete p;
-                return fail(RTPB_E_INVALID, "material " + std::to_string(k) + ": empty table");
-            }
-            if (p->table.size() / 2 + m.table_len > RTPB_MAX_TABLE) {
-                delete p;
-                return fail(RTPB_E_LIMIT, "more than RTPB_MAX_TABLE wavelength table entries");
-            }
-            p->table.insert(p->table.end(), m.table, m.table + 2 * m.table_len);
-            sort_table(p->table.data() + p->table.size() - 2 * m.table_len, m.table_len);
-        }
-        m.table = nullptr;
-        p->mats.push_back(m);
-    }
-    if (!p->table.empty()) p->feat |= (p->table.size() / 2 <= static_cast<size_t>(kLdsTablePairs)) ? 4 : 8;
     if (g_indexed_materials.load()) build_indexed(*p);
     if (p->feat == 1) {
         // PerfectLens code and plain media: the lens-and-flat variant when every surface takes one of its 4 forms

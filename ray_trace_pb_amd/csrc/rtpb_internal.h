@@ -13,6 +13,8 @@
 //   rtpb_sweep_beam.hip    of collimated beams: two instantiation sets of rtpb_sweep_kernel.h (rtpb_stats.h: what
 //                          the sweep shares with the plane kernels; rtpb_sweep_host.h: its row planning, media table
 //                          and upload layout, plain C++)
+//   rtpb_sweep_variants.hip, rtpb_sweep_variants_beam.hip
+//                          the focus sweep over many systems in one call (fans, beams): the variant instantiations
 //   rtpb_surface_ops.hip   propagate_ray2plane and the user-geometry hook kernels
 #pragma once
 
@@ -487,6 +489,12 @@ namespace rtpbi {
 int plan_device_blob(rtpb_plan* p, int dev, void** out);
 // The device material descriptor of plan material k, as the kernels see it (zero Sellmeier = VACUUM).
 DevMaterial<double> device_material(const rtpb_plan& p, size_t k);
+// rtpb_plan_create's checks and host-side lowering into `p` (no device work), and the device descriptor of plan
+// surface k as the blob holds it (lower_surface + lower_surface_media): shared with the variant sweeps, which lower
+// their systems in the call (rtpb_sweep_kernel.h lower_variants).
+int plan_fill(rtpb_plan& p, const rtpb_surface* surfaces, int32_t nsurf, const rtpb_material* materials, int32_t nmat,
+              int32_t dtype);
+DevSurface<double> plan_surface(const rtpb_plan& p, size_t k);
 // RTPB_OK, or RTPB_E_NODEV with the message set.
 int check_device(int dev);
 }  // namespace rtpbi

@@ -27,14 +27,19 @@ struct SweepRows {
 // the whole beam, the bit patterns of the point and of the frame together -- fields at one point that differ in
 // their normal, the ordinary case, never share a row.  Without frames the key's other words are 0, and the rows and
 // their order are those of the point alone.
+// A variant sweep passes its groups' variants (one int32 per group): a row's groups then share the system as well, so
+// a block reads one set of surface descriptors.  The variant is the key's last word: without variants it is 0, and
+// with all variants equal it is one value, so in both cases the rows and their order are those of the source alone.
 inline SweepRows plan_sweep_rows(const double* group_params, int64_t n_groups, bool bundles_allowed,
-                                 int rays_per_lane, int max_bundle, const double* frames = nullptr) {
+                                 int rays_per_lane, int max_bundle, const double* frames = nullptr,
+                                 const int32_t* variants = nullptr) {
     SweepRows r;
-    std::map<std::array<uint64_t, 12>, std::vector<int32_t>> by_point;   // source (bit patterns) -> groups
+    std::map<std::array<uint64_t, 13>, std::vector<int32_t>> by_point;   // source (bit patterns) -> groups
     for (int64_t gi = 0; gi < n_groups; ++gi) {
-        std::array<uint64_t, 12> key{};
+        std::array<uint64_t, 13> key{};
         std::memcpy(key.data(), group_params + 4 * gi, 3 * sizeof(double));
         if (frames) std::memcpy(key.data() + 3, frames + 9 * gi, 9 * sizeof(double));
+        if (variants) key[12] = static_cast<uint32_t>(variants[gi]);
         if (bundles_allowed) by_point[key].push_back(static_cast<int32_t>(gi));
         else r.singles.push_back(static_cast<int32_t>(gi));
     }
@@ -81,16 +86,19 @@ inline void fill_group_media(const rtpb::DevMaterial<double>* mats, size_t n_mat
 // windows, 4, or the wavefront references, 8; nothing for the other sweeps), the beams' frames (frame_doubles per
 // group: normal, n1, n2; 0 for fans), then the int32 index block (bundles, singles, rows).  A beam sweep's tables
 // are the phis' pairs and then its offsets as plain doubles: it passes ceil(n_disps / 2) pair slots for them.
+// A variant sweep's surface descriptors (desc_bytes: n_variants x nsurf DevSurface<double>, a multiple of 8 bytes) lie
+// between the frames and the index block, and its groups' variants (n_groups int32, counted in n_idx) end that block.
 struct SweepLayout {
-    size_t grp, gn, img, win, frm, idx, bytes;
+    size_t grp, gn, img, win, frm, dsc, idx, bytes;
     SweepLayout(int64_t n_thetas, int64_t nphis, int64_t n_groups, size_t media_doubles, size_t n_idx,
-                size_t head_doubles = 0, size_t per_group = 4, size_t frame_doubles = 0) {
+                size_t head_doubles = 0, size_t per_group = 4, size_t frame_doubles = 0, size_t desc_bytes = 0) {
         grp = size_t(n_thetas + nphis) * 2 * sizeof(double);
         gn = grp + size_t(4 * n_groups) * sizeof(double);
         img = gn + size_t(n_groups) * media_doubles * sizeof(double);
         win = img + head_doubles * sizeof(double);
         frm = win + (head_doubles ? per_group * size_t(n_groups) * sizeof(double) : 0);
-        idx = frm + frame_doubles * size_t(n_groups) * sizeof(double);
+        dsc = frm + frame_doubles * size_t(n_groups) * sizeof(double);
+        idx = dsc + desc_bytes;
         bytes = idx + n_idx * sizeof(int32_t);
     }
 };

@@ -2,9 +2,10 @@
 // generate + trace + reduce in one kernel.  The kernel and its host driver are templates on the SOURCE of a group's
 // rays; each source's entry points instantiate them in a translation unit of their own, so the units compile side by
 // side: rtpb_sweep.hip (point-source fans: rtpb_spot_sweep, rtpb_focus_sweep, rtpb_image_sweep, rtpb_wavefront_sweep)
-// and rtpb_sweep_beam.hip (collimated beams: the same four with _collimated).  What the sweep shares with the plane
-// kernels (the statistics, the image's contribution rule) is rtpb_stats.h, the host arithmetic of a call (row
-// planning, media table, upload layout) rtpb_sweep_host.h.
+// and rtpb_sweep_beam.hip (collimated beams: the same four with _collimated); rtpb_sweep_variants.hip and
+// rtpb_sweep_variants_beam.hip hold the focus sweep over many systems (rtpb_focus_sweep_variants[_collimated]).
+// What the sweep shares with the plane kernels (the statistics, the image's contribution rule) is rtpb_stats.h, the
+// host arithmetic of a call (row planning, media table, upload layout) rtpb_sweep_host.h.
 #pragma once
 
 #include "rtpb_stats.h"
@@ -26,13 +27,24 @@ namespace {
 // iphi, position pt + n1 (off cos phi) + n2 (off sin phi), direction normal, phase 0.  Only the generator differs:
 // the index split, the trace and the reductions are the fan's, with the two tables in each other's place -- the
 // table indexed by the remainder (the fan's thetas, the beam's phis) first, the one indexed by the quotient second.
-constexpr int kSrcFan = 0, kSrcBeam = 1;
+//
+// Variant sweep (SRC | kSrcVariant; rtpb_focus_sweep_variants[_collimated]).  Group g traces through the surface
+// descriptors desc + variant[g] * nsurf of the call's own upload instead of a plan's blob: many perturbed copies of
+// one system in one launch.  A block row's groups share their variant (plan_sweep_rows keys on it), so the base of a
+// block's descriptors is one more block-uniform pointer and every descriptor load stays a scalar load; the kinds and
+// geometry codes of a surface may differ from variant to variant.  Host-evaluated media only (FEAT 16 / 17), which
+// arrive per group as before.  The flag is folded into SRC, so the instantiations without it are the code they were.
+constexpr int kSrcFan = 0, kSrcBeam = 1, kSrcVariant = 2;
 constexpr int kFrame = 9;               // a beam's frame: normal, n1, n2
 struct SweepImage;
 struct SweepWave;
 struct SweepArgs {
-    const DevSurface<double>* __restrict__ surf;
-    const DevMaterial<double>* __restrict__ mats;
+    const DevSurface<double>* __restrict__ surf;     // the plan's surfaces; variant sweeps: desc [n_variants][nsurf]
+    union {
+        const DevMaterial<double>* __restrict__ mats;
+        // variant sweeps (FEAT bit 4: mats and table are never read): per group, its variant
+        const int32_t* __restrict__ variant;
+    };
     const double* __restrict__ table;
     // fan: (cos, sin) of the thetas [n_thetas], then of the phis [nphis].  Beam: (cos, sin) of the phis [n_thetas],
     // then the offsets as plain doubles [nphis]
@@ -139,7 +151,11 @@ constexpr int kImageStats = 0;
 // fan's share the field point, and everything after the generator is the same code.
 template <typename TS, int FEAT, bool BUNDLE, int NS = kStats, int SRC = kSrcFan>
 __global__ __launch_bounds__(kBlock) RTPB_SWEEP_ATTR(NS) void sweep_kernel(SweepArgs a) {
-    static_assert(SRC == kSrcFan || SRC == kSrcBeam, "a fan or a beam");
+    constexpr int kGen = SRC & ~kSrcVariant;
+    constexpr bool kVar = (SRC & kSrcVariant) != 0;
+    static_assert(kGen == kSrcFan || kGen == kSrcBeam, "a fan or a beam");
+    static_assert(!kVar || (NS == kFocusStats && (FEAT & 16) != 0 && (FEAT & 2) == 0),
+                  "variants: the focus statistics, host-evaluated media");
     static_assert(!BUNDLE || (FEAT & 16) != 0, "bundles: host-evaluated media");
     static_assert(NS == kStats || NS == kFocusStats || NS == kImageStats || NS == kWaveStats,
                   "spot, focus or wavefront statistics, or the image");
@@ -163,7 +179,7 @@ __global__ __launch_bounds__(kBlock) RTPB_SWEEP_ATTR(NS) void sweep_kernel(Sweep
             ip = jj / a.n_thetas;
         }
         Ray<double> r;
-        if constexpr (SRC == kSrcBeam) {
+        if constexpr (kGen == kSrcBeam) {
             // collimated_kernel's products in its association; the frame is the block's, so scalar loads
             const double* fr = a.frm + kFrame * g;
             const double2 ph = a.tab[it];
@@ -185,7 +201,12 @@ __global__ __launch_bounds__(kBlock) RTPB_SWEEP_ATTR(NS) void sweep_kernel(Sweep
         r.wl = stored<TS>(gp[3]);
         return r;
     };
-    const cptr<DevSurface<double>> surf = (cptr<DevSurface<double>>)(a.surf);
+    cptr<DevSurface<double>> surf = (cptr<DevSurface<double>>)(a.surf);
+    if constexpr (kVar) {
+        // the block row's variant: that of its first group (a bundle row's groups share it)
+        const int32_t g0 = BUNDLE ? a.gidx[a.rows[2 * blockIdx.y]] : a.gidx[blockIdx.y];
+        surf += int64_t(((cptr<int32_t>)(a.variant))[g0]) * a.nsurf;
+    }
     const cptr<DevMaterial<double>> mats = (cptr<DevMaterial<double>>)(a.mats);
     const cptr<double> table = (cptr<double>)(a.table);
     int64_t grp[kSweepRays], tile[kSweepRays];
@@ -326,7 +347,7 @@ __global__ __launch_bounds__(kBlock) RTPB_SWEEP_ATTR(NS) void sweep_kernel(Sweep
             r[q] = gen(tile[q] * kBlock + tid, grp[q]);
             // a beam's positions are complete before the trace begins: without the fence the PerfectLens single rows
             // spill 12 VGPRs instead of the fan's 1
-            if constexpr (SRC == kSrcBeam) RTPB_PIN3(r[q].x, r[q].y, r[q].z);
+            if constexpr (kGen == kSrcBeam) RTPB_PIN3(r[q].x, r[q].y, r[q].z);
         }
         wl0 = r[0].wl;
 #pragma unroll
@@ -517,35 +538,56 @@ struct ImageCall {
     int32_t* outside_out;
 };
 
+// A variant sweep's systems (SRC | kSrcVariant), lowered on the host (lower_variants): no plan and no device blob, the
+// descriptors ride in the call's upload.  All variants have nsurf surfaces and nsurf + 1 materials.
+struct VariantCall {
+    int32_t nsurf = 0, n_variants = 0, dtype = RTPB_F64;
+    int feat = 0;                                   // 1: some variant holds a PerfectLens (FEAT 17 for the call)
+    const int32_t* group_variant = nullptr;         // host, n_groups, each in [0, n_variants)
+    std::vector<DevSurface<double>> desc;           // [n_variants][nsurf], as a plan's blob holds them
+    std::vector<DevMaterial<double>> mats;          // [n_variants][nsurf + 1]
+    std::vector<std::vector<double>> tables;        // per variant: its TABLE materials' (wavelength, n) pairs
+};
+
 // ... and the sweep itself (checked arguments): plan the block rows, fill and send the one upload, launch the sweep
 // kernels of the statistics set, then the final reduction -- or, for the image, clear the outputs and launch the
 // image kernels.  refs: the wavefront mode's references (host, n_groups x kWaveRef); every group of that mode is a
 // single row (the bundle rows' shared first surface keeps no phase) and its storage type is float64.
+// vc (SRC | kSrcVariant, and then no plan): the systems of a variant sweep; a group's media are its own variant's, its
+// block row is keyed on the variant too, and the descriptors and the groups' variants join the upload.
 template <int NS, int SRC = kSrcFan>
 int sweep_impl(const rtpb_plan* plan_c, int32_t device, int64_t n_groups, const double* group_params,
                const SweepSource& src, double* workspace, double* stats_out, void* stream,
-               const ImageCall* im = nullptr, const double* refs = nullptr) {
-    constexpr bool kImage = NS == kImageStats, kWave = NS == kWaveStats, kBeam = SRC == kSrcBeam;
+               const ImageCall* im = nullptr, const double* refs = nullptr, const VariantCall* vc = nullptr) {
+    constexpr bool kImage = NS == kImageStats, kWave = NS == kWaveStats, kBeam = (SRC & ~kSrcVariant) == kSrcBeam;
+    constexpr bool kVar = (SRC & kSrcVariant) != 0;
     auto* plan = const_cast<rtpb_plan*>(plan_c);
     const int64_t gsize = src.n_a * src.n_b;
     const int64_t tiles = (gsize + kBlock - 1) / kBlock;
     DeviceGuard g(device);
     void* blob = nullptr;
-    int rc = plan_device_blob(plan, device, &blob);
-    if (rc) return rc;
+    int rc = RTPB_OK;
+    if constexpr (!kVar) {
+        rc = plan_device_blob(plan, device, &blob);
+        if (rc) return rc;
+    }
     hipStream_t st = static_cast<hipStream_t>(stream);
     // bundle rows need the host-evaluated media, which a POLY6 material rules out
-    const bool pre_n = (plan->feat & 2) == 0;
-    const size_t M = plan->mats.size();
+    const bool pre_n = kVar || (plan->feat & 2) == 0;
+    const int32_t nsurf = kVar ? vc->nsurf : plan->nsurf;
+    const int32_t dtype = kVar ? vc->dtype : plan->dtype;
+    const int feat = kVar ? vc->feat : plan->feat;
+    const size_t M = size_t(nsurf) + 1;
     const SweepRows pr = plan_sweep_rows(group_params, n_groups, pre_n && !kWave, kSweepRays, kMaxBundle,
-                                         kBeam ? src.frames : nullptr);
+                                         kBeam ? src.frames : nullptr, kVar ? vc->group_variant : nullptr);
     // (a beam's second table is its offsets, plain doubles: half as many pair slots)
     const SweepLayout lay(src.n_a, kBeam ? (src.n_b + 1) / 2 : src.n_b, n_groups, pre_n ? M + 3 * (M - 1) : 0,
-                          pr.bundles.size() + pr.singles.size() + pr.rows.size(),
+                          pr.bundles.size() + pr.singles.size() + pr.rows.size() + (kVar ? size_t(n_groups) : 0),
                           kImage  ? sizeof(SweepImage) / sizeof(double)
                           : kWave ? sizeof(SweepWave) / sizeof(double)
                                   : 0,
-                          kWave ? kWaveRef : 4, kBeam ? kFrame : 0);
+                          kWave ? kWaveRef : 4, kBeam ? kFrame : 0,
+                          kVar ? vc->desc.size() * sizeof(DevSurface<double>) : 0);
     StreamScratch dbuf;
     rc = dbuf.alloc(lay.bytes, st);
     if (rc) return rc;
@@ -557,10 +599,19 @@ int sweep_impl(const rtpb_plan* plan_c, int32_t device, int64_t n_groups, const 
     std::memcpy(h + size_t(2 * src.n_a) * sizeof(double), src.tab_b, size_t((kBeam ? 1 : 2) * src.n_b) * sizeof(double));
     std::memcpy(h + lay.grp, group_params, size_t(4 * n_groups) * sizeof(double));
     if constexpr (kBeam) std::memcpy(h + lay.frm, src.frames, size_t(kFrame * n_groups) * sizeof(double));
-    if (pre_n) {
+    if constexpr (kVar) {
+        // each group's media from its own variant's materials and table
+        double* const gn = reinterpret_cast<double*>(h + lay.gn);
+        for (int64_t gi = 0; gi < n_groups; ++gi) {
+            const size_t v = size_t(vc->group_variant[gi]);
+            fill_group_media(vc->mats.data() + v * M, M, vc->tables[v].data(), group_params + 4 * gi, 1, dtype,
+                             gn + gi * (M + 3 * (M - 1)));
+        }
+        std::memcpy(h + lay.dsc, vc->desc.data(), vc->desc.size() * sizeof(DevSurface<double>));
+    } else if (pre_n) {
         std::vector<DevMaterial<double>> dm(M);
         for (size_t k = 0; k < M; ++k) dm[k] = device_material(*plan, k);
-        fill_group_media(dm.data(), M, plan->table.data(), group_params, n_groups, plan->dtype,
+        fill_group_media(dm.data(), M, plan->table.data(), group_params, n_groups, dtype,
                          reinterpret_cast<double*>(h + lay.gn));
     }
     if constexpr (kImage) {
@@ -578,18 +629,24 @@ int sweep_impl(const rtpb_plan* plan_c, int32_t device, int64_t n_groups, const 
     int32_t* hidx = reinterpret_cast<int32_t*>(h + lay.idx);
     hidx = std::copy(pr.bundles.begin(), pr.bundles.end(), hidx);
     hidx = std::copy(pr.singles.begin(), pr.singles.end(), hidx);
-    std::copy(pr.rows.begin(), pr.rows.end(), hidx);
+    hidx = std::copy(pr.rows.begin(), pr.rows.end(), hidx);
+    if constexpr (kVar) std::copy(vc->group_variant, vc->group_variant + n_groups, hidx);
     rc = g_pinned.upload(dbuf.p, lay.bytes, st);
     if (rc) return rc;
     const char* const d = static_cast<const char*>(dbuf.p);
     SweepArgs a{};
-    a.surf = static_cast<const DevSurface<double>*>(blob);
-    a.mats = reinterpret_cast<const DevMaterial<double>*>(static_cast<char*>(blob) + plan->off_mats);
-    a.table = reinterpret_cast<const double*>(static_cast<char*>(blob) + plan->off_table);
+    const int32_t* didx = reinterpret_cast<const int32_t*>(d + lay.idx);
+    if constexpr (kVar) {
+        a.surf = reinterpret_cast<const DevSurface<double>*>(d + lay.dsc);
+        a.variant = didx + pr.bundles.size() + pr.singles.size() + pr.rows.size();
+    } else {
+        a.surf = static_cast<const DevSurface<double>*>(blob);
+        a.mats = reinterpret_cast<const DevMaterial<double>*>(static_cast<char*>(blob) + plan->off_mats);
+        a.table = reinterpret_cast<const double*>(static_cast<char*>(blob) + plan->off_table);
+    }
     a.tab = reinterpret_cast<const double2*>(d);
     a.grp = reinterpret_cast<const double*>(d + lay.grp);
     a.gn = reinterpret_cast<const double*>(d + lay.gn);
-    const int32_t* didx = reinterpret_cast<const int32_t*>(d + lay.idx);
     if constexpr (kImage) a.image = reinterpret_cast<const SweepImage*>(d + lay.img);
     else if constexpr (kWave) a.wave = reinterpret_cast<const SweepWave*>(d + lay.img);
     else a.partials = workspace;
@@ -604,11 +661,11 @@ int sweep_impl(const rtpb_plan* plan_c, int32_t device, int64_t n_groups, const 
             a.c[j] = src.c[j]; a.ex[j] = src.ex[j]; a.ey[j] = src.ey[j];
         }
     }
-    a.nsurf = plan->nsurf;
+    a.nsurf = nsurf;
     sweep_divisor(src.n_a, gsize, a.nt_mul, a.nt_shift);
     auto go = [&](auto tag) {
         using TS = decltype(tag);
-        const int f = plan->feat & 3;                 // lens / POLY6 code (no pre_n: POLY6); tables always compiled in
+        const int f = feat & 3;                       // lens / POLY6 code (no pre_n: POLY6); tables always compiled in
         if constexpr (!kWave) {                       // (the wavefront mode plans no bundle rows)
             if (!pr.rows.empty()) {
                 SweepArgs ap = a;
@@ -626,13 +683,14 @@ int sweep_impl(const rtpb_plan* plan_c, int32_t device, int64_t n_groups, const 
                             static_cast<unsigned>(pr.singles.size()));
             if (pre_n && f == 0) hipLaunchKernelGGL((sweep_kernel<TS, 16, false, NS, SRC>), grid, dim3(kBlock), 0, st, as);
             else if (pre_n) hipLaunchKernelGGL((sweep_kernel<TS, 17, false, NS, SRC>), grid, dim3(kBlock), 0, st, as);
-            else hipLaunchKernelGGL((sweep_kernel<TS, 3, false, NS, SRC>), grid, dim3(kBlock), 0, st, as);   // POLY6 media
+            else if constexpr (!kVar)                                                                        // POLY6 media
+                hipLaunchKernelGGL((sweep_kernel<TS, 3, false, NS, SRC>), grid, dim3(kBlock), 0, st, as);
         }
     };
     if constexpr (kWave) {
         go(double{});
     } else {
-        if (plan->dtype == RTPB_F64) go(double{});
+        if (dtype == RTPB_F64) go(double{});
         else go(float{});
     }
     HIP_TRY(hipGetLastError());
@@ -641,6 +699,67 @@ int sweep_impl(const rtpb_plan* plan_c, int32_t device, int64_t n_groups, const 
         if (rc) return rc;
     }
     return dbuf.release();
+}
+
+// The bound the variant calls hold their upload to (RTPB_MAX_VARIANT_UPLOAD), from the counts alone: the tables, per
+// group its parameters, media, frame (beams) and at most three index words (a slot in bundles or singles, at most one
+// row pair between two groups, its variant), and the descriptors.
+inline size_t variant_upload_bound(int src, const SweepSource& s, int64_t n_groups, int32_t nsurf,
+                                   int32_t n_variants) {
+    const size_t G = size_t(n_groups), S = size_t(nsurf);
+    return size_t(s.n_a + s.n_b) * 2 * sizeof(double) +
+           G * (4 + 4 * S + 1 + (src == kSrcBeam ? kFrame : 0)) * sizeof(double) +
+           size_t(n_variants) * S * sizeof(DevSurface<double>) + 3 * G * sizeof(int32_t);
+}
+
+// rtpb_focus_sweep_variants / _collimated (SRC = kSrcFan / kSrcBeam): the argument checks, then each variant through
+// rtpb_plan_create's own lowering (plan_fill, plan_surface, device_material) into a VariantCall, all before the device
+// is touched; then the sweep.
+template <int SRC>
+int focus_sweep_variants(const rtpb_surface* surfaces, int32_t nsurf, const rtpb_material* materials,
+                         int32_t n_variants, int32_t dtype, int32_t device, int64_t n_groups,
+                         const double* group_params, const int32_t* group_variant, const SweepSource& src,
+                         double* workspace, int64_t workspace_len, double* stats_out, void* stream) {
+    if (!surfaces || !materials || !group_variant || nsurf <= 0 || n_variants <= 0)
+        return fail(RTPB_E_INVALID, "bad focus-sweep-variants arguments");
+    if (dtype != RTPB_F64 && dtype != RTPB_F32) return fail(RTPB_E_INVALID, "dtype must be RTPB_F64 or RTPB_F32");
+    if (nsurf > RTPB_MAX_SURFACES)
+        return fail(RTPB_E_LIMIT, "more than RTPB_MAX_SURFACES (" + std::to_string(RTPB_MAX_SURFACES) + ") surfaces");
+    int rc = sweep_check<kFocusStats, SRC>(n_groups, group_params, src, workspace, workspace_len, stats_out);
+    if (rc) return rc;
+    for (int64_t gi = 0; gi < n_groups; ++gi)
+        if (group_variant[gi] < 0 || group_variant[gi] >= n_variants)
+            return fail(RTPB_E_INVALID, "focus-sweep-variants: group " + std::to_string(gi) + " names variant " +
+                                            std::to_string(group_variant[gi]) + " of " + std::to_string(n_variants));
+    if (variant_upload_bound(SRC, src, n_groups, nsurf, n_variants) > size_t(RTPB_MAX_VARIANT_UPLOAD))
+        return fail(RTPB_E_LIMIT, "focus-sweep-variants: the upload (descriptors, media, indices) exceeds "
+                                  "RTPB_MAX_VARIANT_UPLOAD; split the call");
+    VariantCall vc;
+    vc.nsurf = nsurf;
+    vc.n_variants = n_variants;
+    vc.dtype = dtype;
+    vc.group_variant = group_variant;
+    const size_t S = size_t(nsurf), M = S + 1;
+    vc.desc.resize(size_t(n_variants) * S);
+    vc.mats.resize(size_t(n_variants) * M);
+    vc.tables.resize(size_t(n_variants));
+    for (int32_t v = 0; v < n_variants; ++v) {
+        rtpb_plan p;
+        rc = plan_fill(p, surfaces + size_t(v) * S, nsurf, materials + size_t(v) * M, nsurf + 1, dtype);
+        if (rc) return fail(rc, "variant " + std::to_string(v) + ": " + g_last_error);
+        for (size_t k = 0; k < M; ++k)
+            if (p.mats[k].kind == RTPB_POLY6)
+                return fail(RTPB_E_INVALID, "variant " + std::to_string(v) + ", material " + std::to_string(k) +
+                                                ": POLY6 media are not host-evaluated; lower it as RTPB_TABLE");
+        vc.feat |= p.feat & 1;
+        for (size_t k = 0; k < S; ++k) vc.desc[size_t(v) * S + k] = plan_surface(p, k);
+        for (size_t k = 0; k < M; ++k) vc.mats[size_t(v) * M + k] = device_material(p, k);
+        vc.tables[size_t(v)].swap(p.table);
+    }
+    rc = check_device(device);
+    if (rc) return rc;
+    return sweep_impl<kFocusStats, SRC | kSrcVariant>(nullptr, device, n_groups, group_params, src, workspace,
+                                                       stats_out, stream, nullptr, nullptr, &vc);
 }
 
 }  // namespace
