@@ -59,7 +59,9 @@ extern "C" {
                                     rtpb_wavefront_stats / rtpb_wavefront_sweep (wavefront statistics) and the
                                     four rtpb_*_sweep_collimated (collimated-beam sweeps) joined within 10, and
                                     so did rtpb_focus_sweep_variants / _variants_collimated (many systems in one
-                                    fused pass): new symbols only, nothing existing changed */
+                                    fused pass), then rtpb_wavefront_sweep_variants / _variants_collimated and
+                                    rtpb_final_rays_variants / _variants_collimated: new symbols only, nothing
+                                    existing changed */
 
 /* ---- error codes ---------------------------------------------------------------------------- */
 #define RTPB_OK 0
@@ -536,6 +538,57 @@ int rtpb_focus_sweep_variants_collimated(const rtpb_surface* surfaces, int32_t n
                                          const double* group_frames, int64_t n_disps, int64_t nphis,
                                          const double* offsets, const double* phi_cos_sin, double* workspace,
                                          int64_t workspace_len, double* stats_out, void* stream);
+
+/* The WAVEFRONT statistics over many systems: rtpb_wavefront_sweep / rtpb_wavefront_sweep_collimated with the systems
+   in the call, as above.  There is no dtype argument: the calls are float64, as the wavefront statistics are.  The
+   arguments after group_variant are those of rtpb_wavefront_sweep from n_thetas through refs (HOST, n_groups x 8), of
+   rtpb_wavefront_sweep_collimated from group_frames through refs; stats_out (DEVICE, n_groups x 15).  Every group is
+   swept on its own, with rtpb_trace's own surface steps.
+   CONTRACT: a group's 15 sums are bit-identical to those rtpb_wavefront_sweep[_collimated] gives the same group, with
+   the same reference, on a float64 plan created from its variant's descriptors -- whatever else the call holds.
+   The checks, their order and the error codes are those of rtpb_focus_sweep_variants, with a NULL refs
+   RTPB_E_INVALID; the short workspace is n_groups * ceil(rays per group / 256) * 15 doubles, and the upload counts the
+   references and one word more:
+       16 (n_thetas + nphis) + n_groups (8 (4 nsurf + 5) + 12) + 280 n_variants nsurf + 64 n_groups + 8
+   (a collimated call: 72 n_groups more) against RTPB_MAX_VARIANT_UPLOAD. */
+int rtpb_wavefront_sweep_variants(const rtpb_surface* surfaces, int32_t nsurf, const rtpb_material* materials,
+                                  int32_t n_variants, int32_t device, int64_t n_groups, const double* group_params,
+                                  const int32_t* group_variant, int64_t n_thetas, int64_t nphis,
+                                  const double center_ray[3], const double ex[3], const double ey[3],
+                                  const double* theta_cos_sin, const double* phi_cos_sin, const double* refs,
+                                  double* workspace, int64_t workspace_len, double* stats_out, void* stream);
+int rtpb_wavefront_sweep_variants_collimated(const rtpb_surface* surfaces, int32_t nsurf,
+                                             const rtpb_material* materials, int32_t n_variants, int32_t device,
+                                             int64_t n_groups, const double* group_params,
+                                             const int32_t* group_variant, const double* group_frames,
+                                             int64_t n_disps, int64_t nphis, const double* offsets,
+                                             const double* phi_cos_sin, const double* refs, double* workspace,
+                                             int64_t workspace_len, double* stats_out, void* stream);
+
+/* The FINAL RAYS of a few generated rays per group, each group through its own variant: the fan (beam) of every group
+   is generated from the sweep's own source arguments, traced through the group's variant with rtpb_trace's own surface
+   steps, phase kept, and every ray's final state is stored as 8 float64 {x, y, z, dx, dy, dz, phase, wavelength} to
+   rays_out (DEVICE, n_groups x rays per group x 8, AOS), ray j = itheta + n_thetas * iphi (iphi + nphis * idisp) of
+   group g at row g * rays per group + j.  Nothing else is written.  float64 only; no workspace.
+   CONTRACT: a group's rows are bit-identical to rtpb_ray_fan_tables (rtpb_collimated_rays_tables) followed by
+   rtpb_trace (final plane) on a float64 plan created from its variant's descriptors; a ray that dies on the way
+   stores the row rtpb_trace stores for it.  With the tables of theta_max = 0, n_thetas = nphis = 1 (one zero offset,
+   n_disps = nphis = 1) a group's one ray is its chief ray, the ray get_ray_fan(field, 0, 1, wavelength, center_ray)
+   (get_collimated_rays(pt, 0, 1, wavelength, normal)) gives: the references of rtpb_wavefront_sweep_variants for all
+   (variant, field, wavelength) groups come from one call.
+   The checks and error codes are those of rtpb_focus_sweep_variants without a workspace (a NULL rays_out is
+   RTPB_E_INVALID), the upload bound its own; more than 256 rays per group (one tile) is RTPB_E_LIMIT. */
+int rtpb_final_rays_variants(const rtpb_surface* surfaces, int32_t nsurf, const rtpb_material* materials,
+                             int32_t n_variants, int32_t device, int64_t n_groups, const double* group_params,
+                             const int32_t* group_variant, int64_t n_thetas, int64_t nphis,
+                             const double center_ray[3], const double ex[3], const double ey[3],
+                             const double* theta_cos_sin, const double* phi_cos_sin, double* rays_out, void* stream);
+int rtpb_final_rays_variants_collimated(const rtpb_surface* surfaces, int32_t nsurf, const rtpb_material* materials,
+                                        int32_t n_variants, int32_t device, int64_t n_groups,
+                                        const double* group_params, const int32_t* group_variant,
+                                        const double* group_frames, int64_t n_disps, int64_t nphis,
+                                        const double* offsets, const double* phi_cos_sin, double* rays_out,
+                                        void* stream);
 
 /* ---- pupil-phase interpolation (scripts/2022_02_06_perfect_imaging_system_psf.py:90-105) */
 /* A 2-D Delaunay triangulation with one value per vertex, in scipy.spatial.Delaunay's representation,

@@ -127,6 +127,16 @@ SIGNATURES = {
                                                  _P, _P, _P, _i64, _P, _P]),
     "rtpb_focus_sweep_variants_collimated": (ctypes.c_int, [_P, _i32, _P, _i32, _i32, _i32, _i64, _P, _P, _P, _i64,
                                                             _i64, _P, _P, _P, _i64, _P, _P]),
+    # (float64 only: the focus calls' head without dtype, then the wavefront sweeps' arguments from the source on)
+    "rtpb_wavefront_sweep_variants": (ctypes.c_int, [_P, _i32, _P, _i32, _i32, _i64, _P, _P, _i64, _i64, _P, _P, _P,
+                                                     _P, _P, _P, _P, _i64, _P, _P]),
+    "rtpb_wavefront_sweep_variants_collimated": (ctypes.c_int, [_P, _i32, _P, _i32, _i32, _i64, _P, _P, _P, _i64,
+                                                                _i64, _P, _P, _P, _P, _i64, _P, _P]),
+    # (the source's arguments, then rays_out and the stream)
+    "rtpb_final_rays_variants": (ctypes.c_int, [_P, _i32, _P, _i32, _i32, _i64, _P, _P, _i64, _i64, _P, _P, _P, _P,
+                                                _P, _P, _P]),
+    "rtpb_final_rays_variants_collimated": (ctypes.c_int, [_P, _i32, _P, _i32, _i32, _i64, _P, _P, _P, _i64, _i64,
+                                                           _P, _P, _P, _P]),
     "rtpb_set_tuning":(ctypes.c_int, [ctypes.c_char_p, _i64]),
     "rtpb_timing_enable": (ctypes.c_int, [_i32]),
     "rtpb_timing_collect": (ctypes.c_int, [ctypes.POINTER(_dbl), ctypes.POINTER(_i64)]),

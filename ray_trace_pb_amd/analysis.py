@@ -9,7 +9,10 @@ difference (``rtpb_wavefront_stats``, :func:`wavefront_sweep`: RMS wavefront err
 The ``collimated_*`` sweeps run the same four analyses on ``get_collimated_rays`` beams, one per (field direction,
 wavelength): objects at infinity (``rtpb_*_sweep_collimated``).  :func:`variant_focus_sweep` and
 :func:`collimated_variant_focus_sweep` run the focus analysis over many systems in one fused pass -- the perturbed
-copies of a tolerance run, which :func:`rigid_move` builds (``rtpb_focus_sweep_variants[_collimated]``).
+copies of a tolerance run, which :func:`rigid_move` builds (``rtpb_focus_sweep_variants[_collimated]``);
+:func:`variant_wavefront_sweep` and :func:`collimated_variant_wavefront_sweep` give the same systems' RMS wavefront
+error and Strehl (``rtpb_wavefront_sweep_variants[_collimated]``, with every group's chief ray from one
+``rtpb_final_rays_variants[_collimated]`` launch).
 """
 import contextlib
 import copy
@@ -921,18 +924,30 @@ def rigid_move(system, surfaces, shift=(0, 0, 0), tilt=(0, 0), pivot=None):
                   surfaces_by_name=np.array(system.surfaces_by_name), aperture_stop=system.aperture_stop)
 
 
-def _variant_source(systems, initial_material, final_material, inner):
+def _variant_source(systems, initial_material, final_material, inner, shared=None, typed=True):
     """The groups of ``inner`` (:func:`_fan_source`, :func:`_beam_source`) once per system: a sweep source of
     len(systems) * inner.nf "fields", group = (variant * n_fields + field) * n_wavelengths + wavelength, so the single
     driver cuts its batches at whole field points of whole or partial variants.  The fused call takes the systems'
     descriptors in place of a plan (``lower``, ``lead``): a batch passes those of the variants it touches, and its
-    ``group_variant`` counts from the first of them."""
+    ``group_variant`` counts from the first of them.
+
+    ``shared`` is another variant source of the same systems and media: this one then uses its lowering (made once
+    per storage type, whichever of the two asks first; its ``lower_seconds`` says what it cost).  ``typed=False``
+    leaves the dtype out of ``lead``: the float64-only entry points (wavefront, final rays) have no such argument."""
     V, per_variant = len(systems), inner.nf * inner.nw
     S = len(systems[0].surfaces)
     src = SimpleNamespace(nf=V * inner.nf, nw=inner.nw, per=inner.per, wavelengths=inner.wavelengths,
-                          suffix="_variants" + inner.suffix, nsurf=S, systems=systems, lower_seconds=0.0)
+                          suffix="_variants" + inner.suffix, nsurf=S, systems=systems, lower_seconds=0.0, lowered={})
 
     def lower(keys, code):
+        owner = src if shared is None else shared
+        memo = (code, np.asarray(keys, dtype=np.float64).tobytes())
+        if memo not in owner.lowered:
+            owner.lowered[memo] = lower_now(keys, code)
+            owner.lower_seconds += owner.lowered[memo].seconds
+        return owner.lowered[memo]
+
+    def lower_now(keys, code):
         # each system through E.lower (its content memo, not the plan cache), the descriptors side by side
         t0 = time.perf_counter()
         lows = [E.lower(s.surfaces, [initial_material] + list(s.materials) + [final_material],
@@ -942,13 +957,13 @@ def _variant_source(systems, initial_material, final_material, inner):
         for v, low in enumerate(lows):
             ctypes.memmove(ctypes.addressof(surf) + v * ns, low.surfaces, ns)
             ctypes.memmove(ctypes.addressof(mats) + v * nm, low.materials, nm)     # (TABLE pointers: into lows)
-        src.lower_seconds = time.perf_counter() - t0
-        return SimpleNamespace(surf=surf, mats=mats, ns=ns, nm=nm, dtype=code, keep=lows)
+        return SimpleNamespace(surf=surf, mats=mats, ns=ns, nm=nm, dtype=code, keep=lows,
+                               seconds=time.perf_counter() - t0)
 
     def lead(low, b0, b1):
         v0, v1 = b0 // per_variant, (b1 - 1) // per_variant + 1
-        return (ctypes.addressof(low.surf) + v0 * low.ns, S, ctypes.addressof(low.mats) + v0 * low.nm, v1 - v0,
-                low.dtype)
+        return (ctypes.addressof(low.surf) + v0 * low.ns, S, ctypes.addressof(low.mats) + v0 * low.nm,
+                v1 - v0) + ((low.dtype,) if typed else ())
 
     def head():
         inner_args = inner.head(V)
@@ -967,10 +982,9 @@ def _variant_source(systems, initial_material, final_material, inner):
 _VARIANT_UPLOAD_MAX = 256 << 20
 
 
-def _variant_sweep(what, systems, initial_material, final_material, inner, device, dtype, groups_per_batch, fused,
-                   devices, require_image_plane):
-    """What the two variant sweeps share: the checks (before any device call), the fused call through the single
-    driver or, unfused, one ordinary unfused sweep per system, and the summary shaped (n_variants, ...)."""
+def _variant_systems(what, systems, fused, devices):
+    """The systems of a variant sweep as a list and their common number of surfaces; ``ValueError`` for what no
+    variant call takes."""
     systems = list(systems)
     if not systems:
         raise ValueError(what + ": systems is empty")
@@ -981,6 +995,29 @@ def _variant_sweep(what, systems, initial_material, final_material, inner, devic
         raise ValueError(f"at most {C.RTPB_MAX_SURFACES} surfaces per trace")
     if devices is not None and not fused:
         raise ValueError("devices= needs the fused sweep")
+    return systems, S
+
+
+def _variant_batch(V, S, nf, nw, per, ncols, group_bytes=0):
+    """The default ``groups_per_batch`` of a variant sweep of ``ncols`` statistics (None: no workspace).  The library
+    bounds a call's upload: a group's own words (``group_bytes`` more than the focus sweep's: the wavefront
+    references) and its share of the descriptors, with a margin of two for the tables and a batch's partial variants;
+    the workspace bound is :func:`_sweep_plan`'s."""
+    per_group = 8 * (4 * S + 5) + 12 + 72 + group_bytes + -(-280 * S // (nf * nw))
+    batch = min(V * nf * nw, 65535, _VARIANT_UPLOAD_MAX // 2 // per_group)
+    if ncols is not None:
+        batch = min(batch, (1 << 26) // (-(-per // 256) * ncols))
+    batch = max(1, batch)
+    if batch >= nw:
+        batch -= batch % nw
+    return batch
+
+
+def _variant_sweep(what, systems, initial_material, final_material, inner, device, dtype, groups_per_batch, fused,
+                   devices, require_image_plane):
+    """What the two variant sweeps share: the checks (before any device call), the fused call through the single
+    driver or, unfused, one ordinary unfused sweep per system, and the summary shaped (n_variants, ...)."""
+    systems, S = _variant_systems(what, systems, fused, devices)
     for s in systems:
         _require_image_plane(s, require_image_plane)
     V, nf, nw = len(systems), inner.nf, inner.nw
@@ -995,13 +1032,7 @@ def _variant_sweep(what, systems, initial_material, final_material, inner, devic
         return summarize_focus(np.stack(raws)), {"seconds": seconds, "rays": rays,
                                                  "ray_surface_per_s": rays * S / seconds, "variants": V}
     if groups_per_batch is None:
-        # the library bounds a call's upload: a group's own words and its share of the descriptors, with a margin
-        # of two for the tables and a batch's partial variants; the workspace bound is _sweep_plan's
-        per_group = 8 * (4 * S + 5) + 12 + 72 + -(-280 * S // (nf * nw))
-        groups_per_batch = max(1, min(V * nf * nw, 65535, _VARIANT_UPLOAD_MAX // 2 // per_group,
-                                      (1 << 26) // (-(-inner.per // 256) * 16)))
-        if groups_per_batch >= nw:
-            groups_per_batch -= groups_per_batch % nw
+        groups_per_batch = _variant_batch(V, S, nf, nw, inner.per, 16)
     source = _variant_source(systems, initial_material, final_material, inner)
     mode = SimpleNamespace(**vars(_FOCUS))
     mode.finish = lambda nf_all, nw_, raw: summarize_focus(raw.reshape(V, nf, nw, 16))
@@ -1043,6 +1074,169 @@ def collimated_variant_focus_sweep(systems, initial_material, final_material, no
     return _variant_sweep("collimated_variant_focus_sweep", systems, initial_material, final_material,
                           _beam_source(normals, wavelengths, displacement_max, n_disps, nphis, phi_start, pt), device,
                           dtype, groups_per_batch, fused, devices, require_image_plane)
+
+
+def _rays_mode():
+    """The final-rays call as the single driver sees it (:func:`_stats_mode`): ``rtpb_final_rays`` with a variant
+    source's suffix, no workspace; per device the rows of the shard's groups, (n, rays per group, 8) float64."""
+    def shard(dev, per, g0, n, batch):
+        import torch
+        rays = torch.empty((n, per, 8), dtype=torch.float64, device=dev)
+        return (rays,), lambda b0, b1: (rays[b0 - g0:b1 - g0].data_ptr(),)
+
+    return SimpleNamespace(entry="rtpb_final_rays", ncols=None, shard=shard,
+                           hbm_bytes=lambda per, n: n * per * 64,
+                           finish=lambda nf, nw, rays: rays.reshape(nf, nw, -1, 8))
+
+
+def _variant_refs(what, systems, initial_material, final_material, inner, chief, spot_summary, device,
+                  groups_per_batch, devices, shared=None):
+    """(V, n_fields, n_wavelengths, 8) references of a variant wavefront sweep.  ``inner`` is the sweep's source (None
+    when ``spot_summary`` stands in for the focus sweep), ``chief`` the source of one chief ray per group (the fan of
+    half-angle 0 with one ray, the beam with one zero offset); ``shared`` a variant source whose lowering both
+    passes use."""
+    systems, S = _variant_systems(what, systems, True, devices)
+    V, nf, nw = len(systems), chief.nf, chief.nw
+    if spot_summary is not None:
+        c0 = np.asarray(spot_summary["centroid"], dtype=np.float64)
+        if c0.shape != (V, nf, nw, 3):
+            raise ValueError(what + ": spot_summary must be a variant_focus_sweep summary of the same groups")
+    if shared is None:
+        shared = _variant_source(systems, initial_material, final_material, chief if inner is None else inner)
+    if spot_summary is None:
+        focus = SimpleNamespace(**vars(_FOCUS))
+        focus.finish = lambda nf_all, nw_, raw: summarize_focus(raw.reshape(V, nf, nw, 16))
+        source = _variant_source(systems, initial_material, final_material, inner, shared=shared)
+        spot_summary, _ = _sweep(focus, None, initial_material, final_material, source, device, "float64",
+                                 groups_per_batch or _variant_batch(V, S, nf, nw, inner.per, 16), True, devices)
+        c0 = spot_summary["centroid"]
+    source = _variant_source(systems, initial_material, final_material, chief, shared=shared, typed=False)
+    fin, _ = _sweep(_rays_mode(), None, initial_material, final_material, source, device, "float64",
+                    groups_per_batch or _variant_batch(V, S, nf, nw, 1, None), True, devices)
+    fin = fin.reshape(V, nf, nw, 8)
+    refs = np.empty((V, nf, nw, 8))
+    refs[..., 0:3] = c0
+    refs[..., 3:7] = fin[..., 3:7]
+    refs[..., 7] = [float(final_material.n(w)) / w for w in chief.wavelengths]
+    refs[~np.isfinite(fin[..., :7]).all(axis=-1)] = np.nan
+    return refs
+
+
+def _variant_wave(what, systems, initial_material, final_material, inner, chief, device, refs, spot_summary,
+                  groups_per_batch, fused, devices, dtype):
+    """What the two variant wavefront sweeps share: the checks (before any device call), the references, the fused
+    call through the single driver or, unfused, one ordinary unfused wavefront sweep per system, and the summary
+    shaped (n_variants, ...)."""
+    if dtype not in ("float64", np.float64):
+        raise ValueError("wavefront_sweep is float64 only: a float32 phase of 1e4 ... 1e7 rad has an ulp of a "
+                         "milliradian to a radian")
+    systems, S = _variant_systems(what, systems, fused, devices)
+    V, nf, nw = len(systems), inner.nf, inner.nw
+    if refs is not None:
+        refs = _wave_refs(refs, (V, nf, nw, 8))
+    shared = _variant_source(systems, initial_material, final_material, inner)
+    refs_seconds = 0.0
+    if refs is None:
+        t0 = time.perf_counter()
+        refs = _variant_refs(what, systems, initial_material, final_material, inner, chief, spot_summary, device,
+                             groups_per_batch, devices if fused else None, shared)
+        refs_seconds = time.perf_counter() - t0 - shared.lower_seconds        # (the lowering happens in there)
+    if not fused:
+        raws, seconds = [], 0.0
+        for v, s in enumerate(systems):
+            one, t = _sweep(_wave_mode(np.ascontiguousarray(refs[v])), s, initial_material, final_material, inner,
+                            device, "float64", groups_per_batch, False, None)
+            raws.append(one["raw"])
+            seconds += t["seconds"]
+        rays = V * nf * nw * inner.per
+        return summarize_wavefront(np.stack(raws), refs), {
+            "seconds": seconds, "rays": rays, "ray_surface_per_s": rays * S / seconds, "variants": V,
+            "lower_seconds": shared.lower_seconds, "refs_seconds": refs_seconds}
+    if groups_per_batch is None:
+        groups_per_batch = _variant_batch(V, S, nf, nw, inner.per, 15, 8 * 8)
+    # the references of groups [b0, b1) are contiguous in refs, as _wave_mode slices them
+    mode = _wave_mode(refs.reshape(V * nf, nw, 8))
+    mode.finish = lambda nf_all, nw_, raw: summarize_wavefront(raw.reshape(V, nf, nw, 15), refs)
+    source = _variant_source(systems, initial_material, final_material, inner, shared=shared, typed=False)
+    summary, timing = _sweep(mode, None, initial_material, final_material, source, device, "float64",
+                             groups_per_batch, True, devices)
+    timing.update(variants=V, lower_seconds=shared.lower_seconds, refs_seconds=refs_seconds)
+    return summary, timing
+
+
+def variant_wavefront_refs(systems, initial_material, final_material, field_points, wavelengths,
+                           center_ray=(0, 0, 1), spot_summary=None, device="cuda:0", groups_per_batch=None,
+                           devices=None, **fan_kw):
+    """The references (n_variants, n_fields, n_wavelengths, 8) = (C0, d0, p0, kf) of
+    :func:`variant_wavefront_sweep`'s groups, as :func:`wavefront_refs` builds one system's -- without a trace per
+    system.  C0 is the group's spot centroid, from ``spot_summary`` (a :func:`variant_focus_sweep` summary of the same
+    groups) or from the variant focus sweep that ``fan_kw`` (``theta_max``, ``n_thetas``, ``nphis``) describes.  d0 and
+    p0 are the final direction and phase of the group's chief ray, ``get_ray_fan(field, 0, 1, wavelength,
+    center_ray=center_ray)`` through the group's system: all of them come from one ``rtpb_final_rays_variants`` call
+    per batch, whose rows are those ``ray_trace(planes='final')`` stores.  kf = final_material.n(wavelength) /
+    wavelength.  A group whose chief ray dies gets a reference of NaN.  The systems are lowered once for both passes."""
+    field_points, wavelengths = _grid(field_points, wavelengths)
+    inner = None if spot_summary is not None else _fan_source(field_points, wavelengths, center_ray=center_ray,
+                                                              **{"nphis": 1, **fan_kw})
+    return _variant_refs("variant_wavefront_refs", systems, initial_material, final_material, inner,
+                         _fan_source(field_points, wavelengths, 0.0, 1, 1, center_ray), spot_summary, device,
+                         groups_per_batch, devices)
+
+
+def collimated_variant_wavefront_refs(systems, initial_material, final_material, normals, wavelengths, pt=(0, 0, 0),
+                                      spot_summary=None, device="cuda:0", groups_per_batch=None, devices=None,
+                                      **beam_kw):
+    """:func:`variant_wavefront_refs` for :func:`collimated_variant_wavefront_sweep`'s beams: C0 from ``spot_summary``
+    (a :func:`collimated_variant_focus_sweep` summary) or from the sweep that ``beam_kw`` (``displacement_max``,
+    ``n_disps``, ``nphis``, ``phi_start``) describes; the chief ray of a group is ``get_collimated_rays(pt, 0, 1,
+    wavelength, normal=normal)`` through its system, all of them from one ``rtpb_final_rays_variants_collimated``
+    call per batch."""
+    inner = None if spot_summary is not None else _beam_source(normals, wavelengths, pt=pt,
+                                                               **{"nphis": 1, "phi_start": 0., **beam_kw})
+    return _variant_refs("collimated_variant_wavefront_refs", systems, initial_material, final_material, inner,
+                         _beam_source(normals, wavelengths, 0, 1, 1, 0., pt), spot_summary, device,
+                         groups_per_batch, devices)
+
+
+def variant_wavefront_sweep(systems, initial_material, final_material, field_points, wavelengths, theta_max,
+                            n_thetas, nphis=1, center_ray=(0, 0, 1), device="cuda:0", refs=None, spot_summary=None,
+                            groups_per_batch=None, fused=True, devices=None, dtype="float64"):
+    """:func:`wavefront_sweep` over MANY systems in one fused pass: the tolerance run of a diffraction-limited design,
+    whose budget is written in RMS wavefront error and Strehl with focus as the compensator.  ``systems`` as for
+    :func:`variant_focus_sweep`; every (system, field point, wavelength) is one group of
+    ``rtpb_wavefront_sweep_variants``, and a group's sums are bit-identical to :func:`wavefront_sweep` of its system
+    alone with the same reference.
+
+    ``refs`` (n_variants, n_fields, n_wavelengths, 8) says what each group's OPD is measured against; with
+    ``refs=None`` :func:`variant_wavefront_refs` builds them (C0 from ``spot_summary``, a :func:`variant_focus_sweep`
+    summary of the same groups, or from a focus sweep of its own), so the rays are traced twice -- through one
+    lowering of the systems, shared by the passes.  Returns (:func:`summarize_wavefront` summary with arrays shaped
+    (n_variants, n_fields, n_wavelengths, ...), timing dict as :func:`wavefront_sweep`'s, covering the wavefront pass
+    alone, plus ``"variants"``, ``"lower_seconds"`` (the host time spent lowering the systems) and
+    ``"refs_seconds"`` (building the references without that lowering, 0 when they were given)): ``rms_opd`` and ``strehl`` about the spot
+    centroid, ``rms_opd_best`` and ``strehl_best`` about each variant's own diffraction focus.
+    ``fused=False`` runs each system through :func:`wavefront_sweep`'s unfused pipeline with ``refs[v]``
+    (bit-identical; for tests).  float64 only.  ``ValueError`` before any device call: another dtype, an empty
+    ``systems``, unequal numbers of surfaces, more than ``RTPB_MAX_SURFACES`` of them, ``devices=`` without
+    ``fused``, a ``refs`` of the wrong shape."""
+    return _variant_wave("variant_wavefront_sweep", systems, initial_material, final_material,
+                         _fan_source(field_points, wavelengths, theta_max, n_thetas, nphis, center_ray),
+                         _fan_source(field_points, wavelengths, 0.0, 1, 1, center_ray), device, refs, spot_summary,
+                         groups_per_batch, fused, devices, dtype)
+
+
+def collimated_variant_wavefront_sweep(systems, initial_material, final_material, normals, wavelengths,
+                                       displacement_max, n_disps, nphis=1, phi_start=0., pt=(0, 0, 0),
+                                       device="cuda:0", refs=None, spot_summary=None, groups_per_batch=None,
+                                       fused=True, devices=None, dtype="float64"):
+    """:func:`variant_wavefront_sweep` with :func:`collimated_wavefront_sweep`'s beams (objects at infinity):
+    ``rtpb_wavefront_sweep_variants_collimated``, the references from
+    :func:`collimated_variant_wavefront_refs`; a group's sums are bit-identical to
+    :func:`collimated_wavefront_sweep` of its system alone with the same reference."""
+    return _variant_wave("collimated_variant_wavefront_sweep", systems, initial_material, final_material,
+                         _beam_source(normals, wavelengths, displacement_max, n_disps, nphis, phi_start, pt),
+                         _beam_source(normals, wavelengths, 0, 1, 1, 0., pt), device, refs, spot_summary,
+                         groups_per_batch, fused, devices, dtype)
 
 
 class GridInterpolator:

@@ -3,7 +3,9 @@
 // rays; each source's entry points instantiate them in a translation unit of their own, so the units compile side by
 // side: rtpb_sweep.hip (point-source fans: rtpb_spot_sweep, rtpb_focus_sweep, rtpb_image_sweep, rtpb_wavefront_sweep)
 // and rtpb_sweep_beam.hip (collimated beams: the same four with _collimated); rtpb_sweep_variants.hip and
-// rtpb_sweep_variants_beam.hip hold the focus sweep over many systems (rtpb_focus_sweep_variants[_collimated]).
+// rtpb_sweep_variants_beam.hip hold the focus sweep over many systems (rtpb_focus_sweep_variants[_collimated]),
+// rtpb_sweep_wave_variants.hip and rtpb_sweep_wave_variants_beam.hip the wavefront sweep over many systems and the
+// final rays of small groups (rtpb_wavefront_sweep_variants[_collimated], rtpb_final_rays_variants[_collimated]).
 // What the sweep shares with the plane kernels (the statistics, the image's contribution rule) is rtpb_stats.h, the
 // host arithmetic of a call (row planning, media table, upload layout) rtpb_sweep_host.h.
 #pragma once
@@ -28,9 +30,9 @@ namespace {
 // the index split, the trace and the reductions are the fan's, with the two tables in each other's place -- the
 // table indexed by the remainder (the fan's thetas, the beam's phis) first, the one indexed by the quotient second.
 //
-// Variant sweep (SRC | kSrcVariant; rtpb_focus_sweep_variants[_collimated]).  Group g traces through the surface
-// descriptors desc + variant[g] * nsurf of the call's own upload instead of a plan's blob: many perturbed copies of
-// one system in one launch.  A block row's groups share their variant (plan_sweep_rows keys on it), so the base of a
+// Variant sweep (SRC | kSrcVariant; rtpb_focus_sweep_variants, rtpb_wavefront_sweep_variants, rtpb_final_rays_variants
+// and their _collimated forms).  Group g traces through the surface descriptors desc + variant[g] * nsurf of the
+// call's own upload instead of a plan's blob: many perturbed copies of one system in one launch.  A block row's groups share their variant (plan_sweep_rows keys on it), so the base of a
 // block's descriptors is one more block-uniform pointer and every descriptor load stays a scalar load; the kinds and
 // geometry codes of a surface may differ from variant to variant.  Host-evaluated media only (FEAT 16 / 17), which
 // arrive per group as before.  The flag is folded into SRC, so the instantiations without it are the code they were.
@@ -55,7 +57,7 @@ struct SweepArgs {
     const int32_t* __restrict__ gidx;   // single rows: the group of block row y; bundle rows: see rows
     const int32_t* __restrict__ rows;   // bundle rows: (offset into gidx, number of groups) of block row y
     union {
-        double* __restrict__ partials;              // spot and focus statistics
+        double* __restrict__ partials;              // spot and focus statistics; kFinalRays: the rays' rows
         const SweepImage* __restrict__ image;       // image mode
         const SweepWave* __restrict__ wave;         // wavefront mode
     };
@@ -128,7 +130,7 @@ constexpr int kStateRows = 11;                     // bundle state per lane: x y
 #define RTPB_WAVE_WPE 4
 #endif
 #define RTPB_SWEEP_ATTR(NS) \
-    __attribute__((amdgpu_waves_per_eu((NS) == kWaveStats ? RTPB_WAVE_WPE : RTPB_SWEEP_WPE, 8)))
+    __attribute__((amdgpu_waves_per_eu((NS) == kWaveStats || (NS) == kFinalRays ? RTPB_WAVE_WPE : RTPB_SWEEP_WPE, 8)))
 // An optimisation fence on three per-lane values: the compiler moves no computation on them across it
 #if defined(__HIP_DEVICE_COMPILE__)
 #define RTPB_PIN3(a, b, c) asm volatile("" : "+v"(a), "+v"(b), "+v"(c))
@@ -147,6 +149,10 @@ constexpr int kStateRows = 11;                     // bundle state per lane: x y
 // every surface, its roots and square roots included, and no carried x x + y y) and the final state is the one
 // rtpb_trace stores, phase and all; eight of the fifteen statistics at a time.
 constexpr int kImageStats = 0;
+// NS = kFinalRays (rtpb_final_rays_variants; variants, float64, single rows, groups of at most one tile): no
+// reduction, each ray's final state goes to rays_out[group][ray] as the row rtpb_trace stores for the final plane (a
+// killed ray's NaN pattern included), so the steps are the wavefront mode's.  Lanes past the group's size store nothing.
+constexpr int kFinalRays = 8;
 // SRC = kSrcBeam: the generator of a collimated beam; a bundle row's groups share the beam (pt and frame) as the
 // fan's share the field point, and everything after the generator is the same code.
 template <typename TS, int FEAT, bool BUNDLE, int NS = kStats, int SRC = kSrcFan>
@@ -154,14 +160,18 @@ __global__ __launch_bounds__(kBlock) RTPB_SWEEP_ATTR(NS) void sweep_kernel(Sweep
     constexpr int kGen = SRC & ~kSrcVariant;
     constexpr bool kVar = (SRC & kSrcVariant) != 0;
     static_assert(kGen == kSrcFan || kGen == kSrcBeam, "a fan or a beam");
-    static_assert(!kVar || (NS == kFocusStats && (FEAT & 16) != 0 && (FEAT & 2) == 0),
-                  "variants: the focus statistics, host-evaluated media");
+    static_assert(!kVar || ((NS == kFocusStats || NS == kWaveStats || NS == kFinalRays) && (FEAT & 16) != 0 &&
+                            (FEAT & 2) == 0),
+                  "variants: the focus or wavefront statistics or the final rays, host-evaluated media");
     static_assert(!BUNDLE || (FEAT & 16) != 0, "bundles: host-evaluated media");
-    static_assert(NS == kStats || NS == kFocusStats || NS == kImageStats || NS == kWaveStats,
-                  "spot, focus or wavefront statistics, or the image");
+    static_assert(NS == kStats || NS == kFocusStats || NS == kImageStats || NS == kWaveStats || NS == kFinalRays,
+                  "spot, focus or wavefront statistics, the image, or the final rays");
     constexpr bool kWave = NS == kWaveStats;
     static_assert(!kWave || (!BUNDLE && sizeof(TS) == 8), "wavefront: float64, single rows");
-    constexpr int kRedRows = NS == kImageStats ? 1 : BUNDLE ? 2 : NS == kStats ? kStats : 8;
+    constexpr bool kRays = NS == kFinalRays;
+    static_assert(!kRays || (kVar && !BUNDLE && sizeof(TS) == 8), "final rays: variants, float64, single rows");
+    constexpr bool kPhase = kWave || kRays;          // the trace kernel's full steps, the phase kept
+    constexpr int kRedRows = NS == kImageStats || kRays ? 1 : BUNDLE ? 2 : NS == kStats ? kStats : 8;
     __shared__ double red[kRedRows][kBlock];
     __shared__ double state[BUNDLE ? kStateRows : 1][kBlock];
     const int tid = threadIdx.x;
@@ -236,7 +246,7 @@ __global__ __launch_bounds__(kBlock) RTPB_SWEEP_ATTR(NS) void sweep_kernel(Sweep
         return sd;
     };
     auto code_of = [&](int k) { return surface_code<double>((surf + k)->kind, (surf + k)->rcp_ok); };
-    constexpr int kMode = (kWave ? kNoAt : kPosOnly) | ((FEAT & 16) != 0 ? kUniMedia : 0);
+    constexpr int kMode = (kPhase ? kNoAt : kPosOnly) | ((FEAT & 16) != 0 ? kUniMedia : 0);
     // the statistics read only the final positions: the steps run with kPosOnly semantics (no TIR fill of the
     // position -- the next surface's intersection makes it NaN, and the final plane gets the rule in reduce), and a
     // run of axial spheres carries x x + y y of each intersection point into the next sphere's quadratic.
@@ -250,7 +260,7 @@ __global__ __launch_bounds__(kBlock) RTPB_SWEEP_ATTR(NS) void sweep_kernel(Sweep
             dispatch_code<(FEAT & 1) != 0>(code, [&](auto kind, auto geo) {
                 constexpr int K = decltype(kind)::value;
                 constexpr int A = decltype(geo)::value;
-                constexpr bool kCarry = K == SPHERE && A == kGeoAxial && !kWave;
+                constexpr bool kCarry = K == SPHERE && A == kGeoAxial && !kPhase;
                 if constexpr (kCarry) {
 #pragma unroll
                     for (int q = 0; q < kSweepRays; ++q) rxy[q] = r[q].x * r[q].x + r[q].y * r[q].y;
@@ -360,8 +370,15 @@ __global__ __launch_bounds__(kBlock) RTPB_SWEEP_ATTR(NS) void sweep_kernel(Sweep
         trace_from(0);
 #pragma unroll
         for (int q = 0; q < kSweepRays; ++q) {
-            if constexpr (NS == kImageStats) to_image(r[q], tile[q] * kBlock + tid < a.gsize, grp[q]);
-            else reduce(r[q], tile[q] * kBlock + tid < a.gsize, grp[q], tile[q]);
+            if constexpr (NS == kImageStats) {
+                to_image(r[q], tile[q] * kBlock + tid < a.gsize, grp[q]);
+            } else if constexpr (kRays) {
+                // a plain per-lane store of the row (four 16-byte stores), inside the group's own rows only
+                const int64_t j = tile[q] * kBlock + tid;
+                if (j < a.gsize) store_ray<double, RTPB_AOS>(a.partials, grp[q] * a.gsize + j, 0, r[q]);
+            } else {
+                reduce(r[q], tile[q] * kBlock + tid < a.gsize, grp[q], tile[q]);
+            }
         }
     } else {
         const int32_t off = a.rows[2 * blockIdx.y], nb = a.rows[2 * blockIdx.y + 1];
@@ -530,6 +547,18 @@ int image_sweep_check(const char* what, const char* too_many, int64_t n_groups, 
     return RTPB_OK;
 }
 
+// ... those of the final-rays calls (NS = kFinalRays: no workspace; one tile of rays per group at the most) ...
+template <int SRC>
+int final_rays_check(int64_t n_groups, const double* group_params, const SweepSource& s, const double* rays_out) {
+    if (n_groups <= 0 || !s.complete(SRC) || !group_params || !rays_out)
+        return fail(RTPB_E_INVALID, "bad final-rays arguments");
+    if (s.n_a > kBlock || s.n_b > kBlock || s.n_a * s.n_b > kBlock)
+        return fail(RTPB_E_LIMIT, SRC == kSrcBeam ? "final-rays: more than 256 rays per group (n_disps*nphis)"
+                                                  : "final-rays: more than 256 rays per group (n_thetas*nphis)");
+    if (n_groups > 65535) return fail(RTPB_E_LIMIT, "too many groups or rays per group");
+    return RTPB_OK;
+}
+
 // rtpb_image_sweep's own arguments (NS = kImageStats: no workspace, no statistics)
 struct ImageCall {
     const double* windows;      // host, n_groups x 4
@@ -554,13 +583,15 @@ struct VariantCall {
 // image kernels.  refs: the wavefront mode's references (host, n_groups x kWaveRef); every group of that mode is a
 // single row (the bundle rows' shared first surface keeps no phase) and its storage type is float64.
 // vc (SRC | kSrcVariant, and then no plan): the systems of a variant sweep; a group's media are its own variant's, its
-// block row is keyed on the variant too, and the descriptors and the groups' variants join the upload.
+// block row is keyed on the variant too, and the descriptors and the groups' variants join the upload.  The wavefront
+// mode over variants gives refs and vc both: the two are independent parts of the upload.
+// NS = kFinalRays: no workspace and no reduction; stats_out is rays_out, n_groups x gsize x 8, written by the kernel.
 template <int NS, int SRC = kSrcFan>
 int sweep_impl(const rtpb_plan* plan_c, int32_t device, int64_t n_groups, const double* group_params,
                const SweepSource& src, double* workspace, double* stats_out, void* stream,
                const ImageCall* im = nullptr, const double* refs = nullptr, const VariantCall* vc = nullptr) {
     constexpr bool kImage = NS == kImageStats, kWave = NS == kWaveStats, kBeam = (SRC & ~kSrcVariant) == kSrcBeam;
-    constexpr bool kVar = (SRC & kSrcVariant) != 0;
+    constexpr bool kVar = (SRC & kSrcVariant) != 0, kRays = NS == kFinalRays;
     auto* plan = const_cast<rtpb_plan*>(plan_c);
     const int64_t gsize = src.n_a * src.n_b;
     const int64_t tiles = (gsize + kBlock - 1) / kBlock;
@@ -578,7 +609,7 @@ int sweep_impl(const rtpb_plan* plan_c, int32_t device, int64_t n_groups, const 
     const int32_t dtype = kVar ? vc->dtype : plan->dtype;
     const int feat = kVar ? vc->feat : plan->feat;
     const size_t M = size_t(nsurf) + 1;
-    const SweepRows pr = plan_sweep_rows(group_params, n_groups, pre_n && !kWave, kSweepRays, kMaxBundle,
+    const SweepRows pr = plan_sweep_rows(group_params, n_groups, pre_n && !kWave && !kRays, kSweepRays, kMaxBundle,
                                          kBeam ? src.frames : nullptr, kVar ? vc->group_variant : nullptr);
     // (a beam's second table is its offsets, plain doubles: half as many pair slots)
     const SweepLayout lay(src.n_a, kBeam ? (src.n_b + 1) / 2 : src.n_b, n_groups, pre_n ? M + 3 * (M - 1) : 0,
@@ -649,6 +680,7 @@ int sweep_impl(const rtpb_plan* plan_c, int32_t device, int64_t n_groups, const 
     a.gn = reinterpret_cast<const double*>(d + lay.gn);
     if constexpr (kImage) a.image = reinterpret_cast<const SweepImage*>(d + lay.img);
     else if constexpr (kWave) a.wave = reinterpret_cast<const SweepWave*>(d + lay.img);
+    else if constexpr (kRays) a.partials = stats_out;
     else a.partials = workspace;
     a.n_thetas = src.n_a;
     a.nphis = src.n_b;
@@ -666,7 +698,7 @@ int sweep_impl(const rtpb_plan* plan_c, int32_t device, int64_t n_groups, const 
     auto go = [&](auto tag) {
         using TS = decltype(tag);
         const int f = feat & 3;                       // lens / POLY6 code (no pre_n: POLY6); tables always compiled in
-        if constexpr (!kWave) {                       // (the wavefront mode plans no bundle rows)
+        if constexpr (!kWave && !kRays) {             // (the wavefront and final-rays modes plan no bundle rows)
             if (!pr.rows.empty()) {
                 SweepArgs ap = a;
                 ap.gidx = didx;
@@ -687,14 +719,14 @@ int sweep_impl(const rtpb_plan* plan_c, int32_t device, int64_t n_groups, const 
                 hipLaunchKernelGGL((sweep_kernel<TS, 3, false, NS, SRC>), grid, dim3(kBlock), 0, st, as);
         }
     };
-    if constexpr (kWave) {
+    if constexpr (kWave || kRays) {
         go(double{});
     } else {
         if (dtype == RTPB_F64) go(double{});
         else go(float{});
     }
     HIP_TRY(hipGetLastError());
-    if constexpr (!kImage) {
+    if constexpr (!kImage && !kRays) {
         rc = launch_stats_final(NS, workspace, stats_out, n_groups, tiles, st);
         if (rc) return rc;
     }
@@ -712,29 +744,30 @@ inline size_t variant_upload_bound(int src, const SweepSource& s, int64_t n_grou
            size_t(n_variants) * S * sizeof(DevSurface<double>) + 3 * G * sizeof(int32_t);
 }
 
-// rtpb_focus_sweep_variants / _collimated (SRC = kSrcFan / kSrcBeam): the argument checks, then each variant through
-// rtpb_plan_create's own lowering (plan_fill, plan_surface, device_material) into a VariantCall, all before the device
-// is touched; then the sweep.
-template <int SRC>
-int focus_sweep_variants(const rtpb_surface* surfaces, int32_t nsurf, const rtpb_material* materials,
-                         int32_t n_variants, int32_t dtype, int32_t device, int64_t n_groups,
-                         const double* group_params, const int32_t* group_variant, const SweepSource& src,
-                         double* workspace, int64_t workspace_len, double* stats_out, void* stream) {
+// What the variant calls share before the device is touched (SRC = kSrcFan / kSrcBeam): the checks of the systems'
+// arguments, then `own`, the call's checks of its groups, source and outputs (sweep_check, final_rays_check), the range
+// of group_variant and the upload bound (extra_upload: what the call's mode adds to variant_upload_bound), then each
+// variant through rtpb_plan_create's own lowering (plan_fill, plan_surface, device_material) into vc.  `what` names
+// the call in the messages.
+template <int SRC, typename OwnCheck>
+int lower_variant_call(const std::string& what, const rtpb_surface* surfaces, int32_t nsurf,
+                       const rtpb_material* materials, int32_t n_variants, int32_t dtype, int64_t n_groups,
+                       const int32_t* group_variant, const SweepSource& src, size_t extra_upload, OwnCheck own,
+                       VariantCall& vc) {
     if (!surfaces || !materials || !group_variant || nsurf <= 0 || n_variants <= 0)
-        return fail(RTPB_E_INVALID, "bad focus-sweep-variants arguments");
+        return fail(RTPB_E_INVALID, "bad " + what + " arguments");
     if (dtype != RTPB_F64 && dtype != RTPB_F32) return fail(RTPB_E_INVALID, "dtype must be RTPB_F64 or RTPB_F32");
     if (nsurf > RTPB_MAX_SURFACES)
         return fail(RTPB_E_LIMIT, "more than RTPB_MAX_SURFACES (" + std::to_string(RTPB_MAX_SURFACES) + ") surfaces");
-    int rc = sweep_check<kFocusStats, SRC>(n_groups, group_params, src, workspace, workspace_len, stats_out);
+    int rc = own();
     if (rc) return rc;
     for (int64_t gi = 0; gi < n_groups; ++gi)
         if (group_variant[gi] < 0 || group_variant[gi] >= n_variants)
-            return fail(RTPB_E_INVALID, "focus-sweep-variants: group " + std::to_string(gi) + " names variant " +
+            return fail(RTPB_E_INVALID, what + ": group " + std::to_string(gi) + " names variant " +
                                             std::to_string(group_variant[gi]) + " of " + std::to_string(n_variants));
-    if (variant_upload_bound(SRC, src, n_groups, nsurf, n_variants) > size_t(RTPB_MAX_VARIANT_UPLOAD))
-        return fail(RTPB_E_LIMIT, "focus-sweep-variants: the upload (descriptors, media, indices) exceeds "
-                                  "RTPB_MAX_VARIANT_UPLOAD; split the call");
-    VariantCall vc;
+    if (variant_upload_bound(SRC, src, n_groups, nsurf, n_variants) + extra_upload > size_t(RTPB_MAX_VARIANT_UPLOAD))
+        return fail(RTPB_E_LIMIT, what + ": the upload (descriptors, media, indices) exceeds "
+                                         "RTPB_MAX_VARIANT_UPLOAD; split the call");
     vc.nsurf = nsurf;
     vc.n_variants = n_variants;
     vc.dtype = dtype;
@@ -756,10 +789,65 @@ int focus_sweep_variants(const rtpb_surface* surfaces, int32_t nsurf, const rtpb
         for (size_t k = 0; k < M; ++k) vc.mats[size_t(v) * M + k] = device_material(p, k);
         vc.tables[size_t(v)].swap(p.table);
     }
+    return RTPB_OK;
+}
+
+// rtpb_focus_sweep_variants / _collimated: the prologue, the device, the sweep.
+template <int SRC>
+int focus_sweep_variants(const rtpb_surface* surfaces, int32_t nsurf, const rtpb_material* materials,
+                         int32_t n_variants, int32_t dtype, int32_t device, int64_t n_groups,
+                         const double* group_params, const int32_t* group_variant, const SweepSource& src,
+                         double* workspace, int64_t workspace_len, double* stats_out, void* stream) {
+    VariantCall vc;
+    int rc = lower_variant_call<SRC>(
+        "focus-sweep-variants", surfaces, nsurf, materials, n_variants, dtype, n_groups, group_variant, src, 0,
+        [&] { return sweep_check<kFocusStats, SRC>(n_groups, group_params, src, workspace, workspace_len, stats_out); },
+        vc);
+    if (rc) return rc;
     rc = check_device(device);
     if (rc) return rc;
     return sweep_impl<kFocusStats, SRC | kSrcVariant>(nullptr, device, n_groups, group_params, src, workspace,
                                                        stats_out, stream, nullptr, nullptr, &vc);
+}
+
+// rtpb_wavefront_sweep_variants / _collimated: float64, the references beside the systems.  The upload holds the
+// references and the SweepWave word on top of variant_upload_bound.
+template <int SRC>
+int wavefront_sweep_variants(const rtpb_surface* surfaces, int32_t nsurf, const rtpb_material* materials,
+                             int32_t n_variants, int32_t device, int64_t n_groups, const double* group_params,
+                             const int32_t* group_variant, const SweepSource& src, const double* refs,
+                             double* workspace, int64_t workspace_len, double* stats_out, void* stream) {
+    VariantCall vc;
+    const size_t extra = n_groups > 0 ? size_t(n_groups) * kWaveRef * sizeof(double) + sizeof(SweepWave) : 0;
+    int rc = lower_variant_call<SRC>(
+        "wavefront-sweep-variants", surfaces, nsurf, materials, n_variants, RTPB_F64, n_groups, group_variant, src,
+        extra,
+        [&] {
+            if (!refs) return fail(RTPB_E_INVALID, "bad wavefront-sweep arguments");
+            return sweep_check<kWaveStats, SRC>(n_groups, group_params, src, workspace, workspace_len, stats_out);
+        },
+        vc);
+    if (rc) return rc;
+    rc = check_device(device);
+    if (rc) return rc;
+    return sweep_impl<kWaveStats, SRC | kSrcVariant>(nullptr, device, n_groups, group_params, src, workspace,
+                                                      stats_out, stream, nullptr, refs, &vc);
+}
+
+// rtpb_final_rays_variants / _collimated: float64, at most one tile of rays per group, their final states to rays_out.
+template <int SRC>
+int final_rays_variants(const rtpb_surface* surfaces, int32_t nsurf, const rtpb_material* materials,
+                        int32_t n_variants, int32_t device, int64_t n_groups, const double* group_params,
+                        const int32_t* group_variant, const SweepSource& src, double* rays_out, void* stream) {
+    VariantCall vc;
+    int rc = lower_variant_call<SRC>(
+        "final-rays-variants", surfaces, nsurf, materials, n_variants, RTPB_F64, n_groups, group_variant, src, 0,
+        [&] { return final_rays_check<SRC>(n_groups, group_params, src, rays_out); }, vc);
+    if (rc) return rc;
+    rc = check_device(device);
+    if (rc) return rc;
+    return sweep_impl<kFinalRays, SRC | kSrcVariant>(nullptr, device, n_groups, group_params, src, nullptr, rays_out,
+                                                     stream, nullptr, nullptr, &vc);
 }
 
 }  // namespace

@@ -1,0 +1,201 @@
+"""GPU: the variant wavefront sweeps (analysis.variant_wavefront_sweep / collimated_variant_wavefront_sweep and their
+_refs; rtpb_wavefront_sweep_variants / rtpb_final_rays_variants and the _collimated forms) on the cases of
+tests/variant_cases.py, bit for bit.
+
+Each variant's fans (beams) and chief rays come from the reference generator and are traced alone by the NumPy oracle
+(tests/variant_wave_cases.py); the references and the 15 sums against them must be the oracle's bits, fused and
+unfused.  Then the header's contracts -- a variant's groups are what analysis.wavefront_sweep gives its system alone
+with the same references; the stored rays are rtpb_trace's final plane, killed rays included, and nothing is written
+past them -- permutations, batches that start inside the variant list or split a field's wavelengths, two devices, and
+a despaced doublet whose diffraction focus follows it.  tests/test_variant_wave_host.py checks on the CPU that the
+oracle's answers can tell the variants apart and hold dead and partial groups."""
+import ctypes
+
+import numpy as np
+import pytest
+
+torch = pytest.importorskip("torch")
+
+from ray_trace_pb_amd import _capi as C  # noqa: E402
+from ray_trace_pb_amd import analysis  # noqa: E402
+import ray_trace_pb_amd.materials as mat  # noqa: E402
+import ray_trace_pb_amd.raytrace as rt  # noqa: E402
+from parity import same_bits  # noqa: E402
+import systems  # noqa: E402
+import variant_cases as vc  # noqa: E402
+import variant_wave_cases as vw  # noqa: E402
+
+pytestmark = pytest.mark.gpu
+DEV = "cuda:0"
+
+
+def same_int64(got, ref):
+    got, ref = np.ascontiguousarray(got, dtype=np.float64), np.ascontiguousarray(ref, dtype=np.float64)
+    return got.shape == ref.shape and np.array_equal(got.view(np.int64), ref.view(np.int64))
+
+
+def assert_same_summary(got, exp):
+    assert got.keys() == exp.keys()
+    for k in exp:
+        assert same_bits(got[k], exp[k]), k
+
+
+@pytest.mark.parametrize("fused", [True, False], ids=["fused", "unfused"])
+@pytest.mark.parametrize("name", vw.NAMES)
+def test_variant_wavefront_sweep_bitwise_vs_oracle(name, fused):
+    """refs=None: the references the sweep builds are the oracle's (centroid of the fixed-order spot sums, the
+    oracle's chief ray, kf; NaN for a dead chief), the raw sums the oracle's as int64 views, and every summary entry
+    the same bits as the summary of the oracle's sums; the dead groups count 0 and their summaries are NaN."""
+    c = vc.case(name)
+    o = vw.oracle(name)
+    V = len(c.systems)
+    refs = vw.sweep_refs(c, device=DEV)
+    assert refs.shape == (V, c.nf, len(c.wls), 8) and same_bits(refs, o.refs)
+    got, timing = vw.sweep(c, device=DEV, fused=fused)
+    print(name, "fused" if fused else "unfused", "oracle count", o.sums[..., 0].astype(int).reshape(V, -1).tolist(),
+          "got", got["count"].astype(int).reshape(V, -1).tolist())
+    assert got["raw"].shape == (V, c.nf, len(c.wls), 15)
+    assert timing["variants"] == V and timing["rays"] == V * c.nf * len(c.wls) * c.per
+    assert timing["lower_seconds"] > 0 and timing["refs_seconds"] > 0
+    assert np.array_equal(got["count"], o.sums[..., 0])
+    assert same_int64(got["raw"], o.sums)
+    assert_same_summary(got, analysis.summarize_wavefront(o.sums, o.refs))
+    dead = np.isnan(o.refs).any(axis=-1)
+    assert (got["count"][dead] == 0).all() and (got["count"][~dead] > 0).all()
+    for k in ("rms_opd", "strehl", "shift", "reference_best", "rms_opd_best", "strehl_best"):
+        assert np.isnan(got[k][dead]).all() and np.isfinite(got[k][~dead]).all(), k
+    # the references given are the references built
+    again, t2 = vw.sweep(c, device=DEV, fused=fused, refs=refs)
+    assert_same_summary(again, got)
+    assert t2["refs_seconds"] == 0.0
+
+
+@pytest.mark.parametrize("name", vw.NAMES)
+def test_refs_take_the_centroids_of_a_focus_summary(name):
+    """spot_summary: a variant_focus_sweep summary of the same groups stands in for the focus pass, same bits."""
+    c = vc.case(name)
+    spot, _ = vc.sweep(c, device=DEV)
+    assert same_bits(vw.sweep_refs(c, device=DEV, spot_summary=spot), vw.oracle(name).refs)
+
+
+@pytest.mark.parametrize("name", vw.NAMES)
+def test_each_variant_is_its_own_wavefront_sweep_bit_for_bit(name):
+    """The contract of include/rtpb.h: variant v's groups have the bits of the ordinary wavefront sweep on a plan of
+    variant v's descriptors with the same references, whatever else the call holds."""
+    c = vc.case(name)
+    refs = np.array(vw.oracle(name).refs)
+    got, _ = vw.sweep(c, device=DEV, refs=refs)
+    for v in range(len(c.systems)):
+        alone, _ = vw.sweep_alone(c, v, refs[v], device=DEV)
+        assert np.array_equal(got["count"][v], alone["count"]), v
+        assert same_int64(got["raw"][v], alone["raw"]), v
+        for k in alone:
+            assert same_bits(got[k][v], alone[k]), (v, k)
+
+
+@pytest.mark.parametrize("name", vw.NAMES)
+def test_permuting_the_systems_permutes_the_result(name):
+    c = vc.case(name)
+    V = len(c.systems)
+    base, _ = vw.sweep(c, device=DEV)
+    for perm in (list(range(V))[::-1], [V - 1] * 2 + [0] * 3):
+        got, _ = vw.sweep(c._replace(systems=[c.systems[v] for v in perm]), device=DEV)
+        assert np.array_equal(got["count"], base["count"][perm])
+        for k in base:
+            assert same_bits(got[k], base[k][perm]), (perm, k)
+
+
+@pytest.mark.parametrize("name", vw.NAMES)
+def test_batches_inside_the_variant_list_and_inside_a_field(name):
+    """groups_per_batch = 9 with 6 groups per variant starts a batch in the middle of variant 1; 4 and 7 split a field
+    point's three wavelengths; 1 makes every group a launch.  The references and the sums have the unbatched bits,
+    and those are the oracle's."""
+    c = vc.case(name)
+    o = vw.oracle(name)
+    whole, _ = vw.sweep(c, device=DEV)
+    assert same_int64(whole["raw"], o.sums)
+    for gpb in (9, 4, 7, 1):
+        assert same_bits(vw.sweep_refs(c, device=DEV, groups_per_batch=gpb), o.refs), gpb
+        got, _ = vw.sweep(c, device=DEV, groups_per_batch=gpb)
+        assert np.array_equal(got["count"], o.sums[..., 0]), gpb
+        assert_same_summary(got, whole)
+
+
+def _final_rays(c, inner, guard=3):
+    """rtpb_final_rays_variants[_collimated] called directly on all groups of the case with ``inner``'s rays: the
+    rows (V, nf, nw, per, 8) and the ``guard`` rows after them, which were filled with a sentinel."""
+    V, G = len(c.systems), len(c.systems) * c.nf * len(c.wls)
+    src = analysis._variant_source(c.systems, c.m0, c.m1, inner, typed=False)
+    low = src.lower(src.wavelengths, C.RTPB_F64)
+    args, keep = src.head()(0, G)
+    out = torch.full((G * inner.per + guard, 8), -7.25, dtype=torch.float64, device=DEV)
+    entry = getattr(C.lib(), "rtpb_final_rays" + src.suffix)
+    C.check(entry(*src.lead(low, 0, G), 0, G, *args, out.data_ptr(), torch.cuda.current_stream(out.device).cuda_stream))
+    torch.cuda.synchronize()
+    del keep
+    rows = out.cpu().numpy()
+    return rows[:G * inner.per].reshape(V, c.nf, len(c.wls), inner.per, 8), rows[G * inner.per:]
+
+
+@pytest.mark.parametrize("shape", [(1, 1), (5, 3)], ids=["chief", "5x3"])
+@pytest.mark.parametrize("name", vw.NAMES)
+def test_final_rays_are_the_oracles_final_plane(name, shape):
+    """One ray per group (the chief rays: the tables of a zero half-angle or one zero offset) and 5 x 3 rays per group
+    (lanes past 15 store nothing): every stored row is the oracle's final plane of that ray through the group's
+    variant, bit for bit, the NaN rows of killed rays included, and the rows after the last group's keep their
+    sentinel."""
+    c = vc.case(name)
+    inner = vw.chief_source(c) if shape == (1, 1) else vw.inner_source(c, *shape)
+    rows, guard = _final_rays(c, inner)
+    exp = vw.oracle_rays(name, *shape)
+    assert rows.shape == exp.shape
+    killed = np.isnan(exp).any(axis=-1)
+    print(name, shape, "killed rays per variant", killed.reshape(len(c.systems), -1).sum(axis=1).tolist())
+    assert killed.any() and not killed.all()
+    assert same_bits(rows, exp)
+    assert (guard == -7.25).all()
+    if shape == (1, 1):
+        assert same_bits(rows[..., 0, :], vw.oracle(name).chief)
+
+
+def test_devices_split_the_variants_bit_for_bit():
+    """devices=: two shards on GPU 0 give the one-device result, references included."""
+    c = vc.case("c2_fan")
+    one, t1 = vw.sweep(c, device=DEV)
+    many, tm = vw.sweep(c, devices=[0, 0], groups_per_batch=6)
+    assert_same_summary(many, one)
+    assert [p["device"] for p in tm["per_device"]] == [0, 0]
+    assert sum(p["rays"] for p in tm["per_device"]) == t1["rays"]
+
+
+@pytest.mark.skipif(torch.cuda.device_count() < 2, reason="needs two GPUs")
+def test_two_devices_give_the_bits_of_one():
+    for name in ("c2_fan", "c2_beam"):
+        c = vc.case(name)
+        one, _ = vw.sweep(c, device=DEV)
+        two, tm = vw.sweep(c, devices=[0, 1])
+        assert_same_summary(two, one)
+        assert [p["device"] for p in tm["per_device"]] == [0, 1]
+
+
+def test_a_despaced_doublet_is_refocused_by_the_diffraction_focus():
+    """Physics: the C2 doublet moved along z by 0.05 and 0.2, the image plane staying where it was.  About the spot
+    centroid on that plane the wavefront error changes with the despace; each variant's own diffraction focus lies
+    elsewhere along the axis and the figure about it, focus compensated, is smaller.  The closed form
+    rms_opd_at(nominal, delta) does not hold exactly -- the despaced system works at other conjugates, so its
+    aberrations are others -- so no figure is compared with it and no tolerance is made up for one; the figures are
+    printed."""
+    nominal = systems.c2_system(rt, mat)
+    moves = (0.0, 0.05, 0.2)
+    variants = [analysis.rigid_move(nominal, [1, 2, 3], shift=(0.0, 0.0, dz)) for dz in moves]
+    vac = mat.Vacuum()
+    got, _ = analysis.variant_wavefront_sweep(variants, vac, vac, [[0.0, 0.0, -5.0]], [systems.C2_WAVELENGTHS[1]],
+                                              0.05, 67, 23, device=DEV)
+    rms, best = got["rms_opd"][:, 0, 0], got["rms_opd_best"][:, 0, 0]
+    zbest = got["reference_best"][:, 0, 0, 2]
+    print("despace", moves, "rms_opd", rms.tolist(), "rms_opd_best", best.tolist(), "z of the diffraction focus",
+          zbest.tolist())
+    assert (got["count"] == 67 * 23).all()
+    assert len({float(r) for r in rms}) == 3, "the despace did not change the wavefront about the centroid"
+    assert np.isfinite(best).all() and (best < rms).all()
+    assert len({float(z) for z in zbest}) == 3, "the diffraction focus did not move with the doublet"
