@@ -60,8 +60,9 @@ extern "C" {
                                     four rtpb_*_sweep_collimated (collimated-beam sweeps) joined within 10, and
                                     so did rtpb_focus_sweep_variants / _variants_collimated (many systems in one
                                     fused pass), then rtpb_wavefront_sweep_variants / _variants_collimated and
-                                    rtpb_final_rays_variants / _variants_collimated: new symbols only, nothing
-                                    existing changed */
+                                    rtpb_final_rays_variants / _variants_collimated, then rtpb_footprint_stats /
+                                    rtpb_footprint_sweep / rtpb_footprint_sweep_collimated (per-surface beam
+                                    footprints and vignetting): new symbols only, nothing existing changed */
 
 /* ---- error codes ---------------------------------------------------------------------------- */
 #define RTPB_OK 0
@@ -503,6 +504,51 @@ int rtpb_image_sweep_collimated(const rtpb_plan* plan, int32_t device, int64_t n
                                 const double* group_frames, int64_t n_disps, int64_t nphis, const double* offsets,
                                 const double* phi_cos_sin, const double* windows, int32_t nx, int32_t ny,
                                 int32_t* image_out, int32_t* outside_out, void* stream);
+
+/* FOOTPRINT statistics: per (group, surface), how many rays reach the surface, how many it lets through, and how much
+   of it the beam uses -- which surface vignettes which field, and the clear semi-diameter each surface needs.  They
+   are defined on the history rtpb_trace stores with every plane: for surface s and one ray, A is the ray's row in
+   plane 2s + 1 (at the surface: the intersection point, kept where it lies outside the aperture) and B its row in
+   plane 2s + 2 (after it).  A surface's FRAME is nine doubles {o, e1, e2}: an origin and two unit vectors spanning the
+   plane the footprint is measured in, chosen by the caller.  float64 ONLY (a float32 dtype or plan is
+   RTPB_E_INVALID).  Every operation one rounded IEEE operation in this order, no FMA:
+       the ray ARRIVES when A.x, A.y, A.z are all finite; it PASSES when it arrives and B.x, B.y, B.z are all finite
+       q = A.xyz - o;   u = (q.x*e1.x + q.y*e1.y) + q.z*e1.z;   v likewise with e2;   rho2 = u*u + v*v
+   stats_out (device, n_groups x nsurf x 8 doubles), per (group, surface):
+       0  the number of rays that arrive           1  the number of rays that pass
+       2  max rho2 over the arriving rays (the aperture that would pass all that reaches the surface)
+       3  max rho2 over the passing rays (the aperture in use)
+       4, 5  min and max of u over the passing rays        6, 7  min and max of v over the passing rays
+   An empty set gives -inf for a maximum and +inf for a minimum; a NaN u, v or rho2 (overflow only) is skipped by the
+   comparisons (fmax / fmin) and the ray still counts.  Counts, maxima and minima only: the result does not depend on
+   the order of the rays, so the two-pass reduction (a partial per block, then a group's blocks) is exact.
+   frames: HOST, nsurf x 9, every entry finite, uploaded on `stream`.  nsurf <= RTPB_MAX_SURFACES, n_groups <= 65535
+   (RTPB_E_LIMIT beyond).  The arguments are checked before the device is.
+   rtpb_footprint_stats: a stored float64 AOS history [1 + 2 nsurf][n_groups * group_size][8], planes contiguous (what
+   rtpb_trace writes with every plane selected), the rays of group g at rows g * group_size ... of each plane.
+   workspace: device doubles, >= n_groups * ceil(group_size / 256) * nsurf * 8. */
+int rtpb_footprint_stats(int32_t device, int32_t dtype, const void* history, int64_t group_size, int64_t n_groups,
+                         int32_t nsurf, const double* frames, double* workspace, int64_t workspace_len,
+                         double* stats_out, void* stream);
+
+/* Fused footprint sweep: rtpb_wavefront_sweep's arguments with frames (HOST, n_frames x 9; it rides in the sweep's one
+   upload) and n_frames, which must be the plan's number of surfaces, in the references' place.  The surface steps are
+   those of rtpb_trace with every plane stored (the at-plane is formed, total internal reflection fills the position),
+   run once per ray; no plane reaches HBM, so the sweep runs where no history fits.  Every group is swept on its own.
+   CONTRACT: stats_out (device, n_groups x nsurf x 8) is bit-identical to rtpb_footprint_stats of the stored history of
+   the same rays (rtpb_ray_fan_tables / rtpb_collimated_rays_tables + rtpb_trace, every plane) with the same frames.
+   workspace: device doubles, >= n_groups * ceil(ceil(rays per group / 256) / 2) * nsurf * 8 (one partial per block of
+   two tiles).  float64 plans only; the group and tile limits and error codes of rtpb_wavefront_sweep. */
+int rtpb_footprint_sweep(const rtpb_plan* plan, int32_t device, int64_t n_groups, const double* group_params,
+                         int64_t n_thetas, int64_t nphis, const double center_ray[3], const double ex[3],
+                         const double ey[3], const double* theta_cos_sin, const double* phi_cos_sin,
+                         const double* frames, int32_t n_frames, double* workspace, int64_t workspace_len,
+                         double* stats_out, void* stream);
+int rtpb_footprint_sweep_collimated(const rtpb_plan* plan, int32_t device, int64_t n_groups,
+                                    const double* group_params, const double* group_frames, int64_t n_disps,
+                                    int64_t nphis, const double* offsets, const double* phi_cos_sin,
+                                    const double* frames, int32_t n_frames, double* workspace, int64_t workspace_len,
+                                    double* stats_out, void* stream);
 
 /* VARIANT sweeps (tolerance runs): rtpb_focus_sweep / rtpb_focus_sweep_collimated over MANY systems in one call.
    The systems come in the call, as in rtpb_trace_f64: there is no plan and no per-system device memory.

@@ -137,6 +137,12 @@ SIGNATURES = {
                                                 _P, _P, _P]),
     "rtpb_final_rays_variants_collimated": (ctypes.c_int, [_P, _i32, _P, _i32, _i32, _i64, _P, _P, _P, _i64, _i64,
                                                            _P, _P, _P, _P]),
+    # (the wavefront calls' shape: the surfaces' frames and their count in the references' place)
+    "rtpb_footprint_stats": (ctypes.c_int, [_i32, _i32, _P, _i64, _i64, _i32, _P, _P, _i64, _P, _P]),
+    "rtpb_footprint_sweep": (ctypes.c_int, [_P, _i32, _i64, _P, _i64, _i64, _P, _P, _P, _P, _P, _P, _i32, _P, _i64,
+                                            _P, _P]),
+    "rtpb_footprint_sweep_collimated": (ctypes.c_int, [_P, _i32, _i64, _P, _P, _i64, _i64, _P, _P, _P, _i32, _P,
+                                                       _i64, _P, _P]),
     "rtpb_set_tuning":(ctypes.c_int, [ctypes.c_char_p, _i64]),
     "rtpb_timing_enable": (ctypes.c_int, [_i32]),
     "rtpb_timing_collect": (ctypes.c_int, [ctypes.POINTER(_dbl), ctypes.POINTER(_i64)]),

@@ -12,7 +12,10 @@ wavelength): objects at infinity (``rtpb_*_sweep_collimated``).  :func:`variant_
 copies of a tolerance run, which :func:`rigid_move` builds (``rtpb_focus_sweep_variants[_collimated]``);
 :func:`variant_wavefront_sweep` and :func:`collimated_variant_wavefront_sweep` give the same systems' RMS wavefront
 error and Strehl (``rtpb_wavefront_sweep_variants[_collimated]``, with every group's chief ray from one
-``rtpb_final_rays_variants[_collimated]`` launch).
+``rtpb_final_rays_variants[_collimated]`` launch).  :func:`footprint_sweep` and :func:`collimated_footprint_sweep` look
+at EVERY surface in the same single pass -- per (group, surface) the rays that arrive and pass and the beam's
+footprint: which surface vignettes which field (``rtpb_footprint_sweep[_collimated]``; ``rtpb_footprint_stats`` for a
+stored history).
 """
 import contextlib
 import copy
@@ -542,14 +545,16 @@ def _sweep(mode, system, initial_material, final_material, source, device, dtype
 
 
 def _sweep_unfused(mode, low, S, source, dev, tdt, groups_per_batch):
-    """Ray generation -> trace planes='final' -> ``mode.plane`` per batch of groups, through HBM buffers."""
+    """Ray generation -> trace planes='final' -> ``mode.plane`` per batch of groups, through HBM buffers.  A mode
+    with ``planes = "all"`` (the footprints) gets the batch's whole history, (1 + 2 S, rays, 8) contiguous."""
     import torch
     G, per = source.nf * source.nw, source.per
+    sel = E.resolve_planes(getattr(mode, "planes", "final"), S)
+    P = len(sel)
     if groups_per_batch is None:
-        groups_per_batch = max(1, min(G, (1 << 27) // per))     # ~128M rays in flight
-    sel = E.resolve_planes("final", S)
+        groups_per_batch = max(1, min(G, (1 << 27) // (per * P)))     # ~128M ray records in flight
     rays = torch.empty((groups_per_batch * per, 8), dtype=tdt, device=dev)
-    out = torch.empty((1, groups_per_batch * per, 8), dtype=tdt, device=dev)
+    store = torch.empty(P * groups_per_batch * per * 8, dtype=tdt, device=dev)
     arrays = mode.host(G)
     torch.cuda.synchronize(dev)
     t0 = time.perf_counter()
@@ -558,24 +563,28 @@ def _sweep_unfused(mode, low, S, source, dev, tdt, groups_per_batch):
         for k in range(nb):                      # generate each group in place in the batch buffer
             source.into(rays[k * per:(k + 1) * per], b0 + k)
         m = nb * per
-        E.trace_device(low, rays[:m], sel, out=out[:, :m])
-        for a, t in zip(arrays, mode.plane(out[0, :m], per, b0, nb)):
+        out = store[:P * m * 8].view(P, m, 8)                  # (the planes of a short last batch stay contiguous)
+        E.trace_device(low, rays[:m], sel, out=out)
+        for a, t in zip(arrays, mode.plane(out[0] if P == 1 else out, per, b0, nb)):
             a[b0:b0 + nb] = t.cpu().numpy()
     torch.cuda.synchronize(dev)
     return arrays, time.perf_counter() - t0, {}
 
 
-def _sweep_plan(nf, nw, per, n_devices, groups_per_batch=None, ncols=None):
+def _sweep_plan(nf, nw, per, n_devices, groups_per_batch=None, ncols=None, group_doubles=None):
     """Which groups each launch of a fused sweep takes (no torch, no device): ``nf`` field points x ``nw``
     wavelengths, group = field * nw + wavelength, ``per`` rays each, over ``n_devices``; ``ncols`` statistics per
-    group, None for the image mode, which has no workspace.  Returns (groups_per_batch, the devices' contiguous
-    ranges [(g0, g1), ...], the launches [(device slot, b0, b1), ...] in issue order)."""
+    group, None for the image mode, which has no workspace; ``group_doubles`` (the footprint mode): the doubles a
+    group adds to a batch's workspace and output, held to the same bound.  Returns (groups_per_batch, the devices'
+    contiguous ranges [(g0, g1), ...], the launches [(device slot, b0, b1), ...] in issue order)."""
     from .raytrace import shard_bounds
     G = nf * nw
     if groups_per_batch is None:
         groups_per_batch = min(G, 65535)
         if ncols is not None:
             groups_per_batch = min(groups_per_batch, (1 << 26) // (-(-per // 256) * ncols))   # workspace <= 512 MB
+        if group_doubles is not None:
+            groups_per_batch = min(groups_per_batch, (1 << 26) // group_doubles)
         groups_per_batch = max(1, groups_per_batch)
         # whole field points per batch: a field point's groups share each ray's generation and first surface
         # (the kernel's bundle rows), so batches do not split them
@@ -602,7 +611,8 @@ def _sweep_fused(mode, low, S, source, devs, groups_per_batch):
     import torch
     head = source.head()
     nf, nw, per = source.nf, source.nw, source.per
-    groups_per_batch, bounds, launches = _sweep_plan(nf, nw, per, len(devs), groups_per_batch, mode.ncols)
+    groups_per_batch, bounds, launches = _sweep_plan(nf, nw, per, len(devs), groups_per_batch, mode.ncols,
+                                                     getattr(mode, "group_doubles", None))
     work = []          # per device: its groups, the mode's outputs and argument tail, an event pair, its stream
     for (g0, g1), dev in zip(bounds, devs):
         outputs, tail = mode.shard(dev, per, g0, max(g1 - g0, 1), groups_per_batch)
@@ -872,6 +882,184 @@ def collimated_wavefront_sweep(system, initial_material, final_material, normals
     refs = _wave_refs(refs, (source.nf, source.nw, 8))
     return _sweep(_wave_mode(refs), system, initial_material, final_material, source, device, "float64",
                   groups_per_batch, fused, devices)
+
+
+FOOT_STAT_NAMES = ("arrive", "pass", "max_rho2_arrive", "max_rho2_pass", "min_u", "max_u", "min_v", "max_v")
+
+
+def _float64_only(what, *values):
+    """``ValueError`` for float32 input (NumPy or torch): the footprint statistics are defined on the float64 history."""
+    for v in values:
+        dt = getattr(v, "dtype", None)
+        if dt is not None and str(dt).replace("torch.", "") == "float32":
+            raise ValueError(what + " is float64 only: the footprint statistics are defined on the float64 history, "
+                             "and float32 input would be another set of rays")
+
+
+def footprint_frames(system):
+    """The default frames (S, 9) = (o, e1, e2) per surface of :func:`footprint_sweep`: o the surface's ``center``, and
+    (e1, e2) the basis ``get_ray_fan`` builds across its ``center_ray``, taken across the surface's ``input_axis``
+    (for a flat, a mirror or a lens its normal) -- e1 = y x axis normalised (axis x x where that vanishes, as
+    ``get_collimated_rays`` does), e2 = axis x e1.  An axis of exactly (0, 0, 1) gives e1 = (1, 0, 0), e2 = (0, 1, 0):
+    u and v are then x and y about the surface's centre."""
+    from .raytrace import _collimated_frame, _fan_tables
+    out = np.empty((len(system.surfaces), 9))
+    for k, s in enumerate(system.surfaces):
+        axis = np.asarray(getattr(s, "input_axis", getattr(s, "normal", (0.0, 0.0, 1.0))), dtype=np.float64).ravel()
+        with np.errstate(invalid="ignore", divide="ignore"):
+            e1, e2 = _fan_tables(0.0, 1, 1, tuple(axis.tolist()), axis.dtype.str)[:2]
+        if not (np.isfinite(e1).all() and np.isfinite(e2).all()):
+            _, e1, e2 = _collimated_frame(axis)
+        out[k, 0:3] = np.asarray(s.center, dtype=np.float64).ravel()
+        out[k, 3:6], out[k, 6:9] = e1, e2
+    return out
+
+
+def _foot_frames(frames, S):
+    frames = np.ascontiguousarray(frames, dtype=np.float64)
+    if frames.shape != (S, 9):
+        raise ValueError(f"frames must have shape {S} x 9: one (o, e1, e2) per surface")
+    if not np.isfinite(frames).all():
+        raise ValueError("frames must be finite")
+    return frames
+
+
+def footprint_stats_raw(history, group_size, frames, stream=None):
+    """The footprint statistics (n_groups, S, 8; ``FOOT_STAT_NAMES``) of a stored history: a torch CUDA
+    (1 + 2 S, N, 8) float64 tensor as ``ray_trace(planes='all')`` returns it, N = n_groups * group_size, against
+    ``frames`` (S, 9), host values (:func:`footprint_frames`) -- ``rtpb_footprint_stats``.  Per surface s, with A the
+    ray's row in plane 2 s + 1 and B its row in plane 2 s + 2: the rays whose A position is finite (they arrive), those
+    whose B position is finite too (they pass), the largest rho2 = u u + v v of either set and the extremes of u and v
+    of the passing rays, (u, v) being A's position in the surface's frame.  A float32 history raises ``ValueError``."""
+    import torch
+    _float64_only("footprint_stats_raw", history, frames)
+    if history.dim() != 3 or history.shape[0] % 2 != 1 or history.shape[0] < 3 or history.shape[2] != 8:
+        raise ValueError("history must have shape (1 + 2 S, N, 8)")
+    S, n = (history.shape[0] - 1) // 2, history.shape[1]
+    if n % group_size:
+        raise ValueError("history length must be a multiple of group_size")
+    ngroups = n // group_size
+    frames = _foot_frames(frames, S)
+    history = history.contiguous()
+    ws = torch.empty(ngroups * -(-group_size // 256) * S * 8, dtype=torch.float64, device=history.device)
+    stats = torch.empty((ngroups, S, 8), dtype=torch.float64, device=history.device)
+    if stream is None:
+        stream = torch.cuda.current_stream(history.device).cuda_stream
+    C.check(C.lib().rtpb_footprint_stats(history.device.index or 0, C.RTPB_F64, history.data_ptr(), group_size,
+                                         ngroups, S, frames.ctypes.data, ws.data_ptr(), ws.numel(), stats.data_ptr(),
+                                         stream))
+    return stats
+
+
+def summarize_footprint(raw, rays_per_group, aperture_rads):
+    """Footprint summary from the raw statistics (..., S, 8; ``FOOT_STAT_NAMES``), the rays a group started with and
+    the surfaces' ``aperture_rad`` (S,); host, NumPy.  Returns
+
+    - ``raw``; ``arrive`` and ``passed`` (..., S) int64, the rays that reach surface s and those it lets through;
+    - ``missed`` = passed[s - 1] - arrive[s] (passed[-1] = ``rays_per_group``): rays that left surface s - 1 and have
+      no intersection with surface s (or fail its front-side test), and ``clipped`` = arrive[s] - passed[s]: rays the
+      surface itself stops (aperture, total internal reflection, numerical aperture);
+    - ``semi_diameter`` = sqrt(max rho2 of the passing rays), the clear semi-diameter in use, and
+      ``semi_diameter_needed`` = sqrt(max rho2 of the arriving rays), what would pass everything that arrives; NaN
+      where the set is empty;
+    - ``box`` (..., S, 4) = (min u, max u, min v, max v) of the passing rays, NaN where there are none;
+    - ``fill`` = semi_diameter / aperture_rad;
+    - ``limiting_surface`` (...), the surface with the largest missed + clipped (the first of equals), -1 for a group
+      that loses nothing."""
+    raw = np.asarray(raw, dtype=np.float64)
+    ap = np.asarray(aperture_rads, dtype=np.float64)
+    if raw.ndim < 2 or raw.shape[-1] != 8 or ap.shape != (raw.shape[-2],):
+        raise ValueError("raw must have shape (..., S, 8) and aperture_rads (S,)")
+    arrive, passed = raw[..., 0].astype(np.int64), raw[..., 1].astype(np.int64)
+    before = np.concatenate((np.full(passed.shape[:-1] + (1,), int(rays_per_group), dtype=np.int64),
+                             passed[..., :-1]), axis=-1)
+    missed, clipped = before - arrive, arrive - passed
+    with np.errstate(invalid="ignore", divide="ignore"):
+        semi = np.where(raw[..., 3] >= 0, np.sqrt(np.maximum(raw[..., 3], 0.0)), np.nan)
+        need = np.where(raw[..., 2] >= 0, np.sqrt(np.maximum(raw[..., 2], 0.0)), np.nan)
+        fill = semi / ap
+    box = raw[..., 4:8].copy()
+    box[np.isinf(box) & (np.sign(box) == (1.0, -1.0, 1.0, -1.0))] = np.nan     # the empty set's +inf / -inf
+    lost = missed + clipped
+    limiting = np.where(lost.max(axis=-1) > 0, lost.argmax(axis=-1), -1)
+    return {"raw": raw, "arrive": arrive, "passed": passed, "missed": missed, "clipped": clipped,
+            "semi_diameter": semi, "semi_diameter_needed": need, "box": box, "fill": fill,
+            "limiting_surface": limiting}
+
+
+def _aperture_rads(system):
+    return np.array([float(getattr(s, "aperture_rad", np.nan)) for s in system.surfaces])
+
+
+def footprint_stats(history, group_size, frames, aperture_rads):
+    """Footprint summary (:func:`summarize_footprint`) per contiguous group of ``group_size`` rays of a stored torch
+    CUDA (1 + 2 S, N, 8) float64 history."""
+    return summarize_footprint(footprint_stats_raw(history, group_size, frames).cpu().numpy(), group_size,
+                               aperture_rads)
+
+
+def _foot_mode(frames, per, aperture_rads):
+    """The footprint sweep as the drivers see it (:func:`_stats_mode`): ``rtpb_footprint_sweep`` fused; unfused the
+    whole history of a batch (``planes='all'``) reduced by ``rtpb_footprint_stats``.  ``frames`` is C-contiguous
+    (S, 9) float64.  Per device: a batch's workspace (one partial per block of two tiles, S x 8 doubles each) and the
+    shard's statistics."""
+    S = frames.shape[0]
+    blocks = -(-(-(-per // 256)) // 2)
+
+    def shard(dev, per, g0, n, batch):
+        import torch
+        ws = torch.empty(batch * blocks * S * 8, dtype=torch.float64, device=dev)
+        stats = torch.empty((n, S, 8), dtype=torch.float64, device=dev)
+        return (stats,), lambda b0, b1: (frames.ctypes.data, S, ws.data_ptr(), ws.numel(),
+                                         stats[b0 - g0:b1 - g0].data_ptr())
+
+    return SimpleNamespace(
+        entry="rtpb_footprint_sweep", ncols=None, shard=shard, planes="all",
+        # what a group adds to a batch's device memory, in doubles: its partials and its statistics
+        group_doubles=(blocks + 1) * S * 8,
+        # the block partials written and read back, and the statistics (the rays never leave the registers)
+        hbm_bytes=lambda per, n: n * blocks * S * 8 * 8 * 2 + n * S * 8 * 8,
+        host=lambda G: (np.zeros((G, S, 8)),),
+        plane=lambda out, per, b0, nb: (footprint_stats_raw(out, per, frames),),
+        finish=lambda nf, nw, raw: summarize_footprint(raw.reshape(nf, nw, S, 8), per, aperture_rads))
+
+
+def footprint_sweep(system, initial_material, final_material, field_points, wavelengths, theta_max, n_thetas, nphis=1,
+                    center_ray=(0, 0, 1), frames=None, device="cuda:0", groups_per_batch=None, fused=True,
+                    devices=None):
+    """Beam footprints and vignetting at EVERY surface, for every (field point, wavelength): :func:`spot_sweep`'s
+    fans, with each ray's intersection point and its state after the surface looked at once per surface in the same
+    pass (``rtpb_footprint_sweep``: the history kernel's own surface steps, no plane stored, so it runs where no
+    history fits; with ``fused=False`` fan generation -> trace planes='all' -> ``rtpb_footprint_stats``, which holds
+    a batch's whole history; bit-identical).
+
+    ``frames`` (S, 9) = (o, e1, e2) per surface says where each footprint is measured; ``frames=None`` takes
+    :func:`footprint_frames`.  Returns (:func:`summarize_footprint` summary with arrays shaped (n_fields,
+    n_wavelengths, S, ...), timing dict as :func:`spot_sweep`'s): per group and surface the rays that arrive and
+    pass, the rays that missed the surface and those it clipped, the clear semi-diameter in use against
+    ``aperture_rad``, and per group the surface that loses the most rays.
+
+    float64 only: there is no ``dtype``, and float32 field points, wavelengths or frames raise ``ValueError``."""
+    _float64_only("footprint_sweep", field_points, wavelengths, frames)
+    S = len(system.surfaces)
+    frames = _foot_frames(footprint_frames(system) if frames is None else frames, S)
+    return _sweep(_foot_mode(frames, n_thetas * nphis, _aperture_rads(system)), system, initial_material,
+                  final_material, _fan_source(field_points, wavelengths, theta_max, n_thetas, nphis, center_ray),
+                  device, "float64", groups_per_batch, fused, devices)
+
+
+def collimated_footprint_sweep(system, initial_material, final_material, normals, wavelengths, displacement_max,
+                               n_disps, nphis=1, phi_start=0., pt=(0, 0, 0), frames=None, device="cuda:0",
+                               groups_per_batch=None, fused=True, devices=None):
+    """Footprints and vignetting of :func:`collimated_spot_sweep`'s beams: :func:`footprint_sweep` with that source
+    (``rtpb_footprint_sweep_collimated``, or unfused through ``rtpb_footprint_stats``; bit-identical).  float64
+    only."""
+    _float64_only("collimated_footprint_sweep", normals, wavelengths, pt, frames)
+    S = len(system.surfaces)
+    frames = _foot_frames(footprint_frames(system) if frames is None else frames, S)
+    return _sweep(_foot_mode(frames, n_disps * nphis, _aperture_rads(system)), system, initial_material,
+                  final_material, _beam_source(normals, wavelengths, displacement_max, n_disps, nphis, phi_start, pt),
+                  device, "float64", groups_per_batch, fused, devices)
 
 
 def rigid_move(system, surfaces, shift=(0, 0, 0), tilt=(0, 0), pivot=None):

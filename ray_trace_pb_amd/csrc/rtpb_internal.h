@@ -15,6 +15,10 @@
 //                          and upload layout, plain C++)
 //   rtpb_sweep_variants.hip, rtpb_sweep_variants_beam.hip
 //                          the focus sweep over many systems in one call (fans, beams): the variant instantiations
+//   rtpb_sweep_foot.hip, rtpb_sweep_foot_beam.hip
+//                          the fused footprint sweep (per-surface beam footprints and vignetting; fans, beams)
+//   rtpb_footprint.hip     the footprint statistics of a stored history and their second pass (rtpb_foot.h: the
+//                          per-ray term, plain C++)
 //   rtpb_surface_ops.hip   propagate_ray2plane and the user-geometry hook kernels
 #pragma once
 
@@ -454,6 +458,11 @@ struct StreamScratch {
 // The second pass of the plane statistics and of the sweeps (spot_final_kernel, rtpb_analysis.hip): n_stats is 7
 // (spot), 16 (focus) or 15 (wavefront) sums per group, from partials[n_groups][tiles][n_stats].
 int launch_stats_final(int n_stats, double* partials, double* stats, int64_t n_groups, int64_t tiles, hipStream_t st);
+
+// The second pass of the footprint statistics (foot_final_kernel, rtpb_footprint.hip): a group's blocks combined, from
+// partials[n_groups][blocks][nsurf][8] into stats[n_groups][nsurf][8].  n_groups <= 65535, nsurf <= RTPB_MAX_SURFACES.
+int launch_foot_final(const double* partials, double* stats, int64_t n_groups, int64_t blocks, int32_t nsurf,
+                      hipStream_t st);
 
 // What the two image calls share (rtpb_image.hip): the checks of the image arguments -- `call` names the call in the
 // message ("spot-image", "image-sweep"), group_size is the rays per group -- and the zeroing of a call's n_groups

@@ -1,11 +1,14 @@
 // rtpb_stats.h -- what the plane kernels (rtpb_analysis.hip, rtpb_image.hip) and the fused sweep (rtpb_sweep.hip)
 // share: the statistics sets, the one definition of a ray's contribution to the focus statistics, to the wavefront
-// statistics and to a spot image,
+// statistics and to a spot image, the footprint statistics' term (rtpb_foot.h, plain C++ so that the host can run it)
+// and its wave and block reductions,
 // the wave's aggregated image adds, the reduction's argument block and its block-wide tree.  Everything here has
 // internal linkage, as it had inside the one unit: each unit's kernels take its own SpotArgs.
 #pragma once
 
 #include "rtpb_internal.h"
+
+#include "rtpb_foot.h"
 
 namespace {
 
@@ -184,6 +187,58 @@ __device__ __forceinline__ void block_tree_sum(double (&v)[R], double (*buf)[rtp
             for (int j = 0; j < R; ++j) v[j] = v[j] + __shfl_down(v[j], w, 64);
         }
     }
+}
+
+// Footprint statistics (rtpb_foot.h: foot_ray, foot_merge).  One term per lane combined over the wave, the result in
+// every lane: the four steps inside a row of 16 lanes are DPP moves (lane ^ 1 and lane ^ 2 by quad permutation, then the
+// row rotated by 4 and by 8: every quad then holds all four quads), the two across rows lane shuffles.  Sums of small
+// integers, maxima and minima: any order gives the same bits.
+template <int CTRL>
+__device__ __forceinline__ double foot_dpp(double v) {
+    const long long b = __double_as_longlong(v);
+    const int lo = __builtin_amdgcn_mov_dpp(static_cast<int>(b), CTRL, 0xF, 0xF, false);
+    const int hi = __builtin_amdgcn_mov_dpp(static_cast<int>(b >> 32), CTRL, 0xF, 0xF, false);
+    return __longlong_as_double((static_cast<long long>(hi) << 32) | static_cast<unsigned int>(lo));
+}
+template <int CTRL>
+__device__ __forceinline__ void foot_dpp_step(rtpb::FootRay& f) {
+    rtpb::FootRay o;
+#pragma unroll
+    for (int c = 0; c < rtpb::kFootCols; ++c) o.v[c] = foot_dpp<CTRL>(f.v[c]);
+    rtpb::foot_merge(f, o);
+}
+__device__ __forceinline__ void foot_wave_reduce(rtpb::FootRay& f) {
+    foot_dpp_step<0xB1>(f);         // quad_perm [1, 0, 3, 2]
+    foot_dpp_step<0x4E>(f);         // quad_perm [2, 3, 0, 1]
+    foot_dpp_step<0x124>(f);        // row_ror 4
+    foot_dpp_step<0x128>(f);        // row_ror 8
+#pragma unroll
+    for (int w = 16; w <= 32; w <<= 1) {
+        rtpb::FootRay o;
+#pragma unroll
+        for (int c = 0; c < rtpb::kFootCols; ++c) o.v[c] = __shfl_xor(f.v[c], w, 64);
+        rtpb::foot_merge(f, o);
+    }
+}
+
+// ... and over a block's four waves through tab (LDS, [4][kFootCols]); the result is valid in threads 0 ... 7, thread
+// c holding column c (returned).  One barrier; tab is free again after the next one.
+__device__ __forceinline__ double foot_block_reduce(rtpb::FootRay& f, double (*tab)[rtpb::kFootCols]) {
+    static_assert(rtpbi::kBlock == 256, "four waves");
+    const int t = threadIdx.x;
+    foot_wave_reduce(f);
+    if ((t & 63) == 0) {
+#pragma unroll
+        for (int c = 0; c < rtpb::kFootCols; ++c) tab[t >> 6][c] = f.v[c];
+    }
+    __syncthreads();
+    double v = 0.0;
+    if (t < rtpb::kFootCols) {
+        v = tab[0][t];
+#pragma unroll
+        for (int w = 1; w < 4; ++w) v = rtpb::foot_col(t, v, tab[w][t]);
+    }
+    return v;
 }
 
 }  // namespace

@@ -5,7 +5,8 @@
 // and rtpb_sweep_beam.hip (collimated beams: the same four with _collimated); rtpb_sweep_variants.hip and
 // rtpb_sweep_variants_beam.hip hold the focus sweep over many systems (rtpb_focus_sweep_variants[_collimated]),
 // rtpb_sweep_wave_variants.hip and rtpb_sweep_wave_variants_beam.hip the wavefront sweep over many systems and the
-// final rays of small groups (rtpb_wavefront_sweep_variants[_collimated], rtpb_final_rays_variants[_collimated]).
+// final rays of small groups (rtpb_wavefront_sweep_variants[_collimated], rtpb_final_rays_variants[_collimated]);
+// rtpb_sweep_foot.hip and rtpb_sweep_foot_beam.hip the footprint sweep (rtpb_footprint_sweep[_collimated]).
 // What the sweep shares with the plane kernels (the statistics, the image's contribution rule) is rtpb_stats.h, the
 // host arithmetic of a call (row planning, media table, upload layout) rtpb_sweep_host.h.
 #pragma once
@@ -40,6 +41,7 @@ constexpr int kSrcFan = 0, kSrcBeam = 1, kSrcVariant = 2;
 constexpr int kFrame = 9;               // a beam's frame: normal, n1, n2
 struct SweepImage;
 struct SweepWave;
+struct SweepFoot;
 struct SweepArgs {
     const DevSurface<double>* __restrict__ surf;     // the plan's surfaces; variant sweeps: desc [n_variants][nsurf]
     union {
@@ -60,6 +62,7 @@ struct SweepArgs {
         double* __restrict__ partials;              // spot and focus statistics; kFinalRays: the rays' rows
         const SweepImage* __restrict__ image;       // image mode
         const SweepWave* __restrict__ wave;         // wavefront mode
+        const SweepFoot* __restrict__ foot;         // footprint mode
     };
     // ray j of a group: j % n_thetas indexes the first table, j / n_thetas the second (the beam's n_thetas is its
     // nphis, its nphis its n_disps)
@@ -92,6 +95,13 @@ struct SweepWave {
     double* partials;
 };
 static_assert(sizeof(SweepWave) == sizeof(double), "the references follow it");
+
+// The footprint mode's block of the upload, in the same place: where the block partials go, followed by the surfaces'
+// frames (kFootFrame doubles each, rtpb_foot.h) -- one per surface of the plan, not per group
+struct SweepFoot {
+    double* partials;
+};
+static_assert(sizeof(SweepFoot) == sizeof(double), "the frames follow it");
 
 template <typename TS>
 __device__ __forceinline__ double stored(double v) { return static_cast<double>(static_cast<TS>(v)); }
@@ -129,8 +139,9 @@ constexpr int kStateRows = 11;                     // bundle state per lane: x y
 #ifndef RTPB_WAVE_WPE
 #define RTPB_WAVE_WPE 4
 #endif
-#define RTPB_SWEEP_ATTR(NS) \
-    __attribute__((amdgpu_waves_per_eu((NS) == kWaveStats || (NS) == kFinalRays ? RTPB_WAVE_WPE : RTPB_SWEEP_WPE, 8)))
+#define RTPB_SWEEP_ATTR(NS)                                                                                      \
+    __attribute__((amdgpu_waves_per_eu(                                                                          \
+        (NS) == kWaveStats || (NS) == kFinalRays || (NS) == kFootStats ? RTPB_WAVE_WPE : RTPB_SWEEP_WPE, 8)))
 // An optimisation fence on three per-lane values: the compiler moves no computation on them across it
 #if defined(__HIP_DEVICE_COMPILE__)
 #define RTPB_PIN3(a, b, c) asm volatile("" : "+v"(a), "+v"(b), "+v"(c))
@@ -153,6 +164,16 @@ constexpr int kImageStats = 0;
 // reduction, each ray's final state goes to rays_out[group][ray] as the row rtpb_trace stores for the final plane (a
 // killed ray's NaN pattern included), so the steps are the wavefront mode's.  Lanes past the group's size store nothing.
 constexpr int kFinalRays = 8;
+// NS = kFootStats (rtpb_footprint_sweep; float64, single rows only, no variants; the value is the mode's tag, its
+// columns are kFootCols): the footprint statistics of EVERY surface (rtpb_foot.h).  They are defined on the history's
+// "at" and "after" planes, so the steps are the history kernel's (mode 0: the at-plane formed and handed to emit_at,
+// which keeps its position; the TIR fill; no carried x x + y y).  After each surface the lane's rays are combined
+// (foot_ray, foot_merge; lanes past the group's size and rays whose tile lies past the group's tiles contribute
+// nothing), then the wave's lanes (foot_wave_reduce), and lane 0 of each wave writes the wave's row of that surface
+// into the block's LDS table -- its own row, so the surface loop holds no barrier.  After the loop one barrier, and the
+// block's threads combine the four waves' rows and store them as the block's partial [group][block][surface][8];
+// foot_final_kernel (rtpb_footprint.hip) combines a group's blocks.  nsurf <= RTPB_MAX_SURFACES, the plans' bound.
+constexpr int kFootStats = 32;
 // SRC = kSrcBeam: the generator of a collimated beam; a bundle row's groups share the beam (pt and frame) as the
 // fan's share the field point, and everything after the generator is the same code.
 template <typename TS, int FEAT, bool BUNDLE, int NS = kStats, int SRC = kSrcFan>
@@ -164,16 +185,25 @@ __global__ __launch_bounds__(kBlock) RTPB_SWEEP_ATTR(NS) void sweep_kernel(Sweep
                             (FEAT & 2) == 0),
                   "variants: the focus or wavefront statistics or the final rays, host-evaluated media");
     static_assert(!BUNDLE || (FEAT & 16) != 0, "bundles: host-evaluated media");
-    static_assert(NS == kStats || NS == kFocusStats || NS == kImageStats || NS == kWaveStats || NS == kFinalRays,
-                  "spot, focus or wavefront statistics, the image, or the final rays");
+    static_assert(NS == kStats || NS == kFocusStats || NS == kImageStats || NS == kWaveStats || NS == kFinalRays ||
+                      NS == kFootStats,
+                  "spot, focus, wavefront or footprint statistics, the image, or the final rays");
+    constexpr bool kFoot = NS == kFootStats;
+    static_assert(!kFoot || (!kVar && !BUNDLE && sizeof(TS) == 8), "footprints: float64, single rows, no variants");
     constexpr bool kWave = NS == kWaveStats;
     static_assert(!kWave || (!BUNDLE && sizeof(TS) == 8), "wavefront: float64, single rows");
     constexpr bool kRays = NS == kFinalRays;
     static_assert(!kRays || (kVar && !BUNDLE && sizeof(TS) == 8), "final rays: variants, float64, single rows");
     constexpr bool kPhase = kWave || kRays;          // the trace kernel's full steps, the phase kept
-    constexpr int kRedRows = NS == kImageStats || kRays ? 1 : BUNDLE ? 2 : NS == kStats ? kStats : 8;
+    constexpr int kRedRows = NS == kImageStats || kRays || kFoot ? 1 : BUNDLE ? 2 : NS == kStats ? kStats : 8;
     __shared__ double red[kRedRows][kBlock];
     __shared__ double state[BUNDLE ? kStateRows : 1][kBlock];
+    // footprints: per wave, one row per surface (16 KB)
+    double (*foot_tab)[RTPB_MAX_SURFACES][kFootCols] = nullptr;
+    if constexpr (kFoot) {
+        __shared__ double foot_lds[kBlock / 64][RTPB_MAX_SURFACES][kFootCols];
+        foot_tab = foot_lds;
+    }
     const int tid = threadIdx.x;
     auto gen = [&](int64_t j, int64_t g) {
         const double* gp = a.grp + 4 * g;
@@ -246,7 +276,7 @@ __global__ __launch_bounds__(kBlock) RTPB_SWEEP_ATTR(NS) void sweep_kernel(Sweep
         return sd;
     };
     auto code_of = [&](int k) { return surface_code<double>((surf + k)->kind, (surf + k)->rcp_ok); };
-    constexpr int kMode = (kPhase ? kNoAt : kPosOnly) | ((FEAT & 16) != 0 ? kUniMedia : 0);
+    constexpr int kMode = (kFoot ? 0 : kPhase ? kNoAt : kPosOnly) | ((FEAT & 16) != 0 ? kUniMedia : 0);
     // the statistics read only the final positions: the steps run with kPosOnly semantics (no TIR fill of the
     // position -- the next surface's intersection makes it NaN, and the final plane gets the rule in reduce), and a
     // run of axial spheres carries x x + y y of each intersection point into the next sphere's quadratic.
@@ -254,13 +284,14 @@ __global__ __launch_bounds__(kBlock) RTPB_SWEEP_ATTR(NS) void sweep_kernel(Sweep
     // step, so the rays' registers carry from surface to surface without the copies a per-surface join of the kind
     // branches needs (the ODT path of C5: 12 axial spheres, a lens, a flat = 3 runs).
     double rxy[kSweepRays];
+    bool live[kSweepRays];              // footprints: the lane's ray q is one of its group's
     auto trace_from = [&](int s) {
         while (s < a.nsurf) {
             const int code = code_of(s);
             dispatch_code<(FEAT & 1) != 0>(code, [&](auto kind, auto geo) {
                 constexpr int K = decltype(kind)::value;
                 constexpr int A = decltype(geo)::value;
-                constexpr bool kCarry = K == SPHERE && A == kGeoAxial && !kPhase;
+                constexpr bool kCarry = K == SPHERE && A == kGeoAxial && !kPhase && !kFoot;
                 if constexpr (kCarry) {
 #pragma unroll
                     for (int q = 0; q < kSweepRays; ++q) rxy[q] = r[q].x * r[q].x + r[q].y * r[q].y;
@@ -272,13 +303,38 @@ __global__ __launch_bounds__(kBlock) RTPB_SWEEP_ATTR(NS) void sweep_kernel(Sweep
                     for (int q = 0; q < kSweepRays; ++q) n_next[q] = (BUNDLE || q == 0) ? mat_n(q, s + 1) : n_next[0];
                     auto none = [](const Ray<double>&) {};
                     Ray<double> o[kSweepRays];
+                    [[maybe_unused]] double at[kSweepRays][3];
 #pragma unroll
                     for (int q = 0; q < kSweepRays; ++q) {
                         const DevSurface<double> sd = (BUNDLE || q == 0) ? surface_for(q, s, base)
                                                                          : surface_for(0, s, base);
-                        surface_step<double, K, A, kMode>(sd, r[q], n_cur[q], n_next[q], iwl[q], none, o[q],
-                                                          static_cast<GuardBranch*>(nullptr),
-                                                          kCarry ? &rxy[q] : nullptr);
+                        if constexpr (kFoot) {
+                            auto keep = [&](const Ray<double>& p) {
+                                at[q][0] = p.x; at[q][1] = p.y; at[q][2] = p.z;
+                            };
+                            surface_step<double, K, A, kMode>(sd, r[q], n_cur[q], n_next[q], iwl[q], keep, o[q],
+                                                              static_cast<GuardBranch*>(nullptr));
+                        } else {
+                            surface_step<double, K, A, kMode>(sd, r[q], n_cur[q], n_next[q], iwl[q], none, o[q],
+                                                              static_cast<GuardBranch*>(nullptr),
+                                                              kCarry ? &rxy[q] : nullptr);
+                        }
+                    }
+                    if constexpr (kFoot) {
+                        // the surface's frame: the block's, so scalar loads
+                        const cptr<double> fp = (cptr<double>)(a.foot + 1) + kFootFrame * s;
+                        const double fr[kFootFrame] = {fp[0], fp[1], fp[2], fp[3], fp[4], fp[5], fp[6], fp[7], fp[8]};
+                        FootRay acc = foot_none();
+#pragma unroll
+                        for (int q = 0; q < kSweepRays; ++q) {
+                            if (live[q])
+                                foot_merge(acc, foot_ray(at[q][0], at[q][1], at[q][2], o[q].x, o[q].y, o[q].z, fr));
+                        }
+                        foot_wave_reduce(acc);
+                        if ((tid & 63) == 0) {
+#pragma unroll
+                            for (int c = 0; c < kFootCols; ++c) foot_tab[tid >> 6][s][c] = acc.v[c];
+                        }
                     }
 #pragma unroll
                     for (int q = 0; q < kSweepRays; ++q) {
@@ -367,7 +423,25 @@ __global__ __launch_bounds__(kBlock) RTPB_SWEEP_ATTR(NS) void sweep_kernel(Sweep
         }
 #pragma unroll
         for (int q = 0; q < kSweepRays; ++q) n_cur[q] = q == 0 ? mat_n(0, 0) : n_cur[0];
+        if constexpr (kFoot) {
+#pragma unroll
+            for (int q = 0; q < kSweepRays; ++q) live[q] = tile[q] * kBlock + tid < a.gsize;
+        }
         trace_from(0);
+        if constexpr (kFoot) {
+            // the block's partial: the four waves' rows combined, [group][block][surface][kFootCols]
+            __syncthreads();
+            double* out = ((cptr<SweepFoot>)(a.foot))->partials +
+                          (grp[0] * int64_t(gridDim.x) + blockIdx.x) * a.nsurf * kFootCols;
+            for (int k = tid; k < a.nsurf * kFootCols; k += kBlock) {
+                const int s = k / kFootCols, c = k % kFootCols;
+                double v = foot_tab[0][s][c];
+#pragma unroll
+                for (int w = 1; w < kBlock / 64; ++w) v = foot_col(c, v, foot_tab[w][s][c]);
+                out[k] = v;
+            }
+            return;
+        }
 #pragma unroll
         for (int q = 0; q < kSweepRays; ++q) {
             if constexpr (NS == kImageStats) {
@@ -559,6 +633,41 @@ int final_rays_check(int64_t n_groups, const double* group_params, const SweepSo
     return RTPB_OK;
 }
 
+// ... those of the footprint sweeps (NS = kFootStats: float64 plans, one finite frame per surface of the plan, a
+// workspace of one partial per block of two tiles) ...
+template <int SRC>
+int foot_sweep_check(const rtpb_plan* plan, int64_t n_groups, const double* group_params, const SweepSource& s,
+                     const double* frames, int32_t n_frames, double* workspace, int64_t workspace_len,
+                     double* stats_out) {
+    if (!plan) return fail(RTPB_E_INVALID, "plan is NULL");
+    if (plan->dtype != RTPB_F64)
+        return fail(RTPB_E_INVALID, "footprint-sweep: float64 plans only (the statistics are defined on the float64 "
+                                    "history)");
+    if (n_groups <= 0 || !s.complete(SRC) || !group_params || !frames || !workspace || !stats_out)
+        return fail(RTPB_E_INVALID, "bad footprint-sweep arguments");
+    if (n_frames != plan->nsurf)
+        return fail(RTPB_E_INVALID, "footprint-sweep: n_frames (" + std::to_string(n_frames) +
+                                        ") is not the plan's number of surfaces (" + std::to_string(plan->nsurf) + ")");
+    for (int64_t k = 0; k < int64_t(n_frames) * kFootFrame; ++k)
+        if (!(frames[k] - frames[k] == 0.0))
+            return fail(RTPB_E_INVALID, "footprint-sweep: frame " + std::to_string(k / kFootFrame) + " is not finite");
+    if (plan->nsurf > RTPB_MAX_SURFACES)
+        return fail(RTPB_E_LIMIT, "footprint-sweep: more than RTPB_MAX_SURFACES surfaces");
+    if (n_groups > 65535) return fail(RTPB_E_LIMIT, "footprint-sweep: too many groups or rays per group");
+    // (n_a * n_b: a product past int64 is past the limit too)
+    if (s.n_a > (0x7fffffffll * kBlock) / s.n_b)
+        return fail(RTPB_E_LIMIT, "footprint-sweep: too many groups or rays per group");
+    const int64_t tiles = (s.n_a * s.n_b + kBlock - 1) / kBlock;
+    const int64_t blocks = (tiles + kSweepRays - 1) / kSweepRays;
+    if (workspace_len / (int64_t(n_frames) * kFootCols) / blocks < n_groups)
+        return fail(RTPB_E_INVALID,
+                    SRC == kSrcBeam ? "footprint-sweep: workspace too small: need n_groups * ceil(ceil(n_disps*nphis"
+                                      "/256)/2) * nsurf * 8 doubles"
+                                    : "footprint-sweep: workspace too small: need n_groups * ceil(ceil(n_thetas*nphis"
+                                      "/256)/2) * nsurf * 8 doubles");
+    return RTPB_OK;
+}
+
 // rtpb_image_sweep's own arguments (NS = kImageStats: no workspace, no statistics)
 struct ImageCall {
     const double* windows;      // host, n_groups x 4
@@ -586,12 +695,15 @@ struct VariantCall {
 // block row is keyed on the variant too, and the descriptors and the groups' variants join the upload.  The wavefront
 // mode over variants gives refs and vc both: the two are independent parts of the upload.
 // NS = kFinalRays: no workspace and no reduction; stats_out is rays_out, n_groups x gsize x 8, written by the kernel.
+// NS = kFootStats: refs is the surfaces' frames (host, nsurf x kFootFrame), the workspace holds the blocks' partials
+// (n_groups x ceil(tiles / kSweepRays) x nsurf x kFootCols) and stats_out is n_groups x nsurf x kFootCols.
 template <int NS, int SRC = kSrcFan>
 int sweep_impl(const rtpb_plan* plan_c, int32_t device, int64_t n_groups, const double* group_params,
                const SweepSource& src, double* workspace, double* stats_out, void* stream,
                const ImageCall* im = nullptr, const double* refs = nullptr, const VariantCall* vc = nullptr) {
     constexpr bool kImage = NS == kImageStats, kWave = NS == kWaveStats, kBeam = (SRC & ~kSrcVariant) == kSrcBeam;
-    constexpr bool kVar = (SRC & kSrcVariant) != 0, kRays = NS == kFinalRays;
+    constexpr bool kVar = (SRC & kSrcVariant) != 0, kRays = NS == kFinalRays, kFoot = NS == kFootStats;
+    static_assert(!kFoot || !kVar, "footprints: no variants");
     auto* plan = const_cast<rtpb_plan*>(plan_c);
     const int64_t gsize = src.n_a * src.n_b;
     const int64_t tiles = (gsize + kBlock - 1) / kBlock;
@@ -609,15 +721,18 @@ int sweep_impl(const rtpb_plan* plan_c, int32_t device, int64_t n_groups, const 
     const int32_t dtype = kVar ? vc->dtype : plan->dtype;
     const int feat = kVar ? vc->feat : plan->feat;
     const size_t M = size_t(nsurf) + 1;
-    const SweepRows pr = plan_sweep_rows(group_params, n_groups, pre_n && !kWave && !kRays, kSweepRays, kMaxBundle,
-                                         kBeam ? src.frames : nullptr, kVar ? vc->group_variant : nullptr);
-    // (a beam's second table is its offsets, plain doubles: half as many pair slots)
+    const SweepRows pr = plan_sweep_rows(group_params, n_groups, pre_n && !kWave && !kRays && !kFoot, kSweepRays,
+                                         kMaxBundle, kBeam ? src.frames : nullptr,
+                                         kVar ? vc->group_variant : nullptr);
+    // (a beam's second table is its offsets, plain doubles: half as many pair slots; the footprint mode's block is
+    // all head: SweepFoot and the surfaces' frames, nothing per group)
     const SweepLayout lay(src.n_a, kBeam ? (src.n_b + 1) / 2 : src.n_b, n_groups, pre_n ? M + 3 * (M - 1) : 0,
                           pr.bundles.size() + pr.singles.size() + pr.rows.size() + (kVar ? size_t(n_groups) : 0),
                           kImage  ? sizeof(SweepImage) / sizeof(double)
                           : kWave ? sizeof(SweepWave) / sizeof(double)
+                          : kFoot ? sizeof(SweepFoot) / sizeof(double) + size_t(nsurf) * kFootFrame
                                   : 0,
-                          kWave ? kWaveRef : 4, kBeam ? kFrame : 0,
+                          kWave ? kWaveRef : kFoot ? 0 : 4, kBeam ? kFrame : 0,
                           kVar ? vc->desc.size() * sizeof(DevSurface<double>) : 0);
     StreamScratch dbuf;
     rc = dbuf.alloc(lay.bytes, st);
@@ -657,6 +772,12 @@ int sweep_impl(const rtpb_plan* plan_c, int32_t device, int64_t n_groups, const 
         std::memcpy(h + lay.img, &head, sizeof(head));
         std::memcpy(h + lay.win, refs, size_t(kWaveRef * n_groups) * sizeof(double));
     }
+    if constexpr (kFoot) {
+        // (refs: the surfaces' frames, nsurf x kFootFrame)
+        const SweepFoot head{workspace};
+        std::memcpy(h + lay.img, &head, sizeof(head));
+        std::memcpy(h + lay.img + sizeof(head), refs, size_t(nsurf) * kFootFrame * sizeof(double));
+    }
     int32_t* hidx = reinterpret_cast<int32_t*>(h + lay.idx);
     hidx = std::copy(pr.bundles.begin(), pr.bundles.end(), hidx);
     hidx = std::copy(pr.singles.begin(), pr.singles.end(), hidx);
@@ -680,6 +801,7 @@ int sweep_impl(const rtpb_plan* plan_c, int32_t device, int64_t n_groups, const 
     a.gn = reinterpret_cast<const double*>(d + lay.gn);
     if constexpr (kImage) a.image = reinterpret_cast<const SweepImage*>(d + lay.img);
     else if constexpr (kWave) a.wave = reinterpret_cast<const SweepWave*>(d + lay.img);
+    else if constexpr (kFoot) a.foot = reinterpret_cast<const SweepFoot*>(d + lay.img);
     else if constexpr (kRays) a.partials = stats_out;
     else a.partials = workspace;
     a.n_thetas = src.n_a;
@@ -698,7 +820,7 @@ int sweep_impl(const rtpb_plan* plan_c, int32_t device, int64_t n_groups, const 
     auto go = [&](auto tag) {
         using TS = decltype(tag);
         const int f = feat & 3;                       // lens / POLY6 code (no pre_n: POLY6); tables always compiled in
-        if constexpr (!kWave && !kRays) {             // (the wavefront and final-rays modes plan no bundle rows)
+        if constexpr (!kWave && !kRays && !kFoot) {   // (the wavefront, final-rays and footprint modes plan no bundle rows)
             if (!pr.rows.empty()) {
                 SweepArgs ap = a;
                 ap.gidx = didx;
@@ -719,14 +841,17 @@ int sweep_impl(const rtpb_plan* plan_c, int32_t device, int64_t n_groups, const 
                 hipLaunchKernelGGL((sweep_kernel<TS, 3, false, NS, SRC>), grid, dim3(kBlock), 0, st, as);
         }
     };
-    if constexpr (kWave || kRays) {
+    if constexpr (kWave || kRays || kFoot) {
         go(double{});
     } else {
         if (dtype == RTPB_F64) go(double{});
         else go(float{});
     }
     HIP_TRY(hipGetLastError());
-    if constexpr (!kImage && !kRays) {
+    if constexpr (kFoot) {
+        rc = launch_foot_final(workspace, stats_out, n_groups, (tiles + kSweepRays - 1) / kSweepRays, nsurf, st);
+        if (rc) return rc;
+    } else if constexpr (!kImage && !kRays) {
         rc = launch_stats_final(NS, workspace, stats_out, n_groups, tiles, st);
         if (rc) return rc;
     }
