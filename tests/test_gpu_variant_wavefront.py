@@ -16,7 +16,6 @@ import pytest
 
 torch = pytest.importorskip("torch")
 
-from ray_trace_pb_amd import _capi as C  # noqa: E402
 from ray_trace_pb_amd import analysis  # noqa: E402
 import ray_trace_pb_amd.materials as mat  # noqa: E402
 import ray_trace_pb_amd.raytrace as rt  # noqa: E402
@@ -124,17 +123,8 @@ def test_batches_inside_the_variant_list_and_inside_a_field(name):
 def _final_rays(c, inner, guard=3):
     """rtpb_final_rays_variants[_collimated] called directly on all groups of the case with ``inner``'s rays: the
     rows (V, nf, nw, per, 8) and the ``guard`` rows after them, which were filled with a sentinel."""
-    V, G = len(c.systems), len(c.systems) * c.nf * len(c.wls)
-    src = analysis._variant_source(c.systems, c.m0, c.m1, inner, typed=False)
-    low = src.lower(src.wavelengths, C.RTPB_F64)
-    args, keep = src.head()(0, G)
-    out = torch.full((G * inner.per + guard, 8), -7.25, dtype=torch.float64, device=DEV)
-    entry = getattr(C.lib(), "rtpb_final_rays" + src.suffix)
-    C.check(entry(*src.lead(low, 0, G), 0, G, *args, out.data_ptr(), torch.cuda.current_stream(out.device).cuda_stream))
-    torch.cuda.synchronize()
-    del keep
-    rows = out.cpu().numpy()
-    return rows[:G * inner.per].reshape(V, c.nf, len(c.wls), inner.per, 8), rows[G * inner.per:]
+    assert (inner.nf, inner.nw) == (c.nf, len(c.wls))
+    return vw.final_rays(c.systems, c.m0, c.m1, inner, DEV, guard)          # (shared with test_gpu_wave_oracle.py)
 
 
 @pytest.mark.parametrize("shape", [(1, 1), (5, 3)], ids=["chief", "5x3"])

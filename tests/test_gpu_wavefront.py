@@ -128,7 +128,12 @@ def test_fused_wavefront_sweep_bitwise_equals_unfused(name):
     """One-kernel wavefront sweep == fan kernel + trace(planes='final') + rtpb_wavefront_stats with the same
     references, all 15 columns and every summary entry bit for bit: single rows only (c5_bundles: 9 wavelengths
     per field point, which the other sweeps bundle), lens and lens-free instantiations, x-z plane steps, dead
-    rows, and dead chief rays -- a NaN reference counts nothing (tir: every group; stress: exactly those groups)."""
+    rows, and dead chief rays -- a NaN reference counts nothing (tir: every group; stress: exactly those groups).
+
+    The references come from the chief ray, and the chief ray is dead exactly where a case is interesting: on tir
+    all six references are NaN, so this test counts nothing there and says only that both paths return zeros; the
+    phase and direction of the rays that survive beside the reflection are not looked at.  Those are compared with
+    the oracle, against references taken from the survivors, in tests/test_gpu_wave_oracle.py."""
     args, gpb, refs = _case(name)
     fu, _ = analysis.wavefront_sweep(*args, device=DEV, refs=refs, groups_per_batch=gpb, fused=True)
     un, _ = analysis.wavefront_sweep(*args, device=DEV, refs=refs, groups_per_batch=5, fused=False)

@@ -72,6 +72,27 @@ def oracle(name):
 
 
 @functools.lru_cache(maxsize=None)
+def survivor_oracle(name):
+    """refs (V, nf, nw, 8) and sums (V, nf, nw, 15) of a case against references taken from each variant's surviving
+    rays (wave_oracle.survivor_refs_of; NaN where a group has none), each variant traced alone by the oracle: for
+    cases whose chief rays die beside rays that live.  Computed once; read-only."""
+    c = vc.case(name)
+    rays = vc.rays_of(c)
+    nw = len(c.wls)
+    refs, sums = [], []
+    for s in c.systems:
+        S, M = dicts(c, s)
+        fin = np.concatenate([O.ray_trace(S, M, r)[-1] for r in rays])
+        ref = W.survivor_refs_of(fin, c.nf, c.wls, c.m1)
+        refs.append(ref)
+        sums.append(W.fixed_order_wave_sums(fin, c.per, ref.reshape(-1, 8)).reshape(c.nf, nw, 15))
+    out = SimpleNamespace(refs=np.stack(refs), sums=np.stack(sums))
+    for a in vars(out).values():
+        a.setflags(write=False)
+    return out
+
+
+@functools.lru_cache(maxsize=None)
 def oracle_rays(name, n_a, n_b):
     """(V, nf, nw, n_a * n_b, 8): the oracle's final plane of each group's n_a x n_b rays through each variant; with
     one ray the chief rays, else the case's own half-angle or radius.  Computed once; read-only."""
@@ -110,6 +131,28 @@ def sweep_alone(c, v, refs, **kw):
     """Variant v alone through the ordinary wavefront sweep, against its own references."""
     fn = analysis.wavefront_sweep if c.kind == "fan" else analysis.collimated_wavefront_sweep
     return fn(c.systems[v], c.m0, c.m1, *c.args, refs=refs, **c.kw, **kw)
+
+
+SENTINEL = -7.25
+
+
+def final_rays(systems, m0, m1, inner, device, guard=3):
+    """rtpb_final_rays_variants[_collimated] called directly on every group of ``inner`` through every system: the
+    rows (V, nf, nw, per, 8) and the ``guard`` rows after them, which were filled with SENTINEL.  (GPU.)"""
+    import torch
+
+    from ray_trace_pb_amd import _capi as C
+    V, G = len(systems), len(systems) * inner.nf * inner.nw
+    src = analysis._variant_source(systems, m0, m1, inner, typed=False)
+    low = src.lower(src.wavelengths, C.RTPB_F64)
+    args, keep = src.head()(0, G)
+    out = torch.full((G * inner.per + guard, 8), SENTINEL, dtype=torch.float64, device=device)
+    entry = getattr(C.lib(), "rtpb_final_rays" + src.suffix)
+    C.check(entry(*src.lead(low, 0, G), 0, G, *args, out.data_ptr(), torch.cuda.current_stream(out.device).cuda_stream))
+    torch.cuda.synchronize()
+    del keep
+    rows = out.cpu().numpy()
+    return rows[:G * inner.per].reshape(V, inner.nf, inner.nw, inner.per, 8), rows[G * inner.per:]
 
 
 def inner_source(c, n_a=None, n_b=None):
