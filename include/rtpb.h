@@ -62,7 +62,9 @@ extern "C" {
                                     fused pass), then rtpb_wavefront_sweep_variants / _variants_collimated and
                                     rtpb_final_rays_variants / _variants_collimated, then rtpb_footprint_stats /
                                     rtpb_footprint_sweep / rtpb_footprint_sweep_collimated (per-surface beam
-                                    footprints and vignetting): new symbols only, nothing existing changed */
+                                    footprints and vignetting), then rtpb_spot_energy / rtpb_energy_sweep /
+                                    rtpb_energy_sweep_collimated (encircled and ensquared energy) joined within 10:
+                                    new symbols only, nothing existing changed */
 
 /* ---- error codes ---------------------------------------------------------------------------- */
 #define RTPB_OK 0
@@ -504,6 +506,48 @@ int rtpb_image_sweep_collimated(const rtpb_plan* plan, int32_t device, int64_t n
                                 const double* group_frames, int64_t n_disps, int64_t nphis, const double* offsets,
                                 const double* phi_cos_sin, const double* windows, int32_t nx, int32_t ny,
                                 int32_t* image_out, int32_t* outside_out, void* stream);
+
+/* ENCIRCLED and ENSQUARED energy: per group, the fraction of the rays within radius r of a centre (EE50 / EE80 / EE90
+   of a lens specification) and within a square of half-side r about it (detector pixels), as two histograms of nr
+   equal bins over [0, r_max), 1 <= nr <= RTPB_MAX_ENERGY_BINS, and the distance of the farthest ray in each measure.
+   A group's PARAMETERS are four doubles {cx, cy, scale, 0} with scale = nr / r_max, evaluated by the caller.  A ray
+   COUNTS exactly when it counts for rtpb_spot_stats / rtpb_spot_image (x and y finite, in the storage type).  For a
+   counting ray, every step one rounded IEEE operation in this order, no FMA:
+       dx = x - cx;  dy = y - cy
+       rho = sqrt(dx*dx + dy*dy)          (the correctly rounded square root)
+       m   = max(|dx|, |dy|)
+       tc  = rho * scale;   ts = m * scale
+   The ray is INSIDE the circle curve iff 0 <= tc < nr, compared in floating point, so NaN or infinite parameters and
+   overflowing products are outside; only then hist[g][0][(int)tc] += 1, otherwise outside[g][0] += 1.  The square
+   curve is the same with ts, hist[g][1] and outside[g][1].  hist[g][k].sum() + outside[g][k] is the group's spot
+   count, exactly, for both k.  farthest[g][0] is the largest rho over the counting rays and farthest[g][1] the
+   largest m: 0.0 for a group with no counting ray, +inf where a product overflows; a NaN cannot arise from finite
+   x, y and a finite centre.  A centre that is NOT FINITE (cx or cy NaN or infinite) puts every counting ray outside
+   both curves and leaves farthest untouched (0.0 when all of the group's rays see it).  Integer counts and a
+   maximum: the result does not depend on the order in which rays arrive (the maximum is an unsigned 64-bit atomic
+   max on the bit pattern, non-negative doubles ordering as their bits).
+   hist_out (device, n_groups*2*nr int32), outside_out (device, n_groups*2 int32), farthest_out (device, n_groups*2
+   doubles): each call zeroes its n_groups slices on `stream` before counting; no workspace.  At most 2^31 - 1 rays
+   per group (RTPB_E_LIMIT).  The arguments are checked before the device is.
+   rtpb_spot_energy: one (N, 8) AOS plane split into groups as for rtpb_spot_stats; params: DEVICE, n_groups x 4. */
+#define RTPB_MAX_ENERGY_BINS 4096
+int rtpb_spot_energy(int32_t device, int32_t dtype, const void* plane, int64_t group_size, int64_t n_groups,
+                     const double* params, int32_t nr, int32_t* hist_out, int32_t* outside_out, double* farthest_out,
+                     void* stream);
+
+/* Fused energy sweeps: rtpb_image_sweep / rtpb_image_sweep_collimated with each counted ray added to its group's two
+   curves instead of its image -- the same arguments up to the source's tables, row planning and kernel, and their
+   group and tile limits.  params: HOST, n_groups x 4 (it rides in the sweep's one upload).  The results are
+   identical to generating, tracing (final plane) and rtpb_spot_energy in the plan's storage type. */
+int rtpb_energy_sweep(const rtpb_plan* plan, int32_t device, int64_t n_groups, const double* group_params,
+                      int64_t n_thetas, int64_t nphis, const double center_ray[3], const double ex[3],
+                      const double ey[3], const double* theta_cos_sin, const double* phi_cos_sin,
+                      const double* params, int32_t nr, int32_t* hist_out, int32_t* outside_out,
+                      double* farthest_out, void* stream);
+int rtpb_energy_sweep_collimated(const rtpb_plan* plan, int32_t device, int64_t n_groups, const double* group_params,
+                                 const double* group_frames, int64_t n_disps, int64_t nphis, const double* offsets,
+                                 const double* phi_cos_sin, const double* params, int32_t nr, int32_t* hist_out,
+                                 int32_t* outside_out, double* farthest_out, void* stream);
 
 /* FOOTPRINT statistics: per (group, surface), how many rays reach the surface, how many it lets through, and how much
    of it the beam uses -- which surface vignettes which field, and the clear semi-diameter each surface needs.  They

@@ -15,7 +15,9 @@ error and Strehl (``rtpb_wavefront_sweep_variants[_collimated]``, with every gro
 ``rtpb_final_rays_variants[_collimated]`` launch).  :func:`footprint_sweep` and :func:`collimated_footprint_sweep` look
 at EVERY surface in the same single pass -- per (group, surface) the rays that arrive and pass and the beam's
 footprint: which surface vignettes which field (``rtpb_footprint_sweep[_collimated]``; ``rtpb_footprint_stats`` for a
-stored history).
+stored history).  :func:`energy_sweep` and :func:`collimated_energy_sweep` give the encircled and ensquared energy
+curves of every group (``rtpb_energy_sweep[_collimated]``; ``rtpb_spot_energy`` for a stored plane), from which
+:func:`energy_radius` reads EE50 / EE80.
 """
 import contextlib
 import copy
@@ -794,6 +796,182 @@ def _image_mode(windows, nx, ny):
         plane=lambda out, per, b0, nb: spot_image_raw(out, per, win[b0:b0 + nb], (nx, ny)))
 
 
+def _energy_bins(bins):
+    """nr from one int."""
+    try:
+        ok = np.ndim(bins) == 0 and float(bins) == int(bins)
+    except (TypeError, ValueError):
+        ok = False
+    if not ok or not 1 <= int(bins) <= C.RTPB_MAX_ENERGY_BINS:
+        raise ValueError(f"bins must be one int in 1 ... {C.RTPB_MAX_ENERGY_BINS}")
+    return int(bins)
+
+
+def energy_params(centers, r_max, bins):
+    """Parameters (..., 4) float64 {cx, cy, scale, 0} of energy curves with ``bins`` bins over [0, r_max):
+    ``centers`` (..., 2) -- or (..., 3), the z ignored, as ``summary["centroid"]`` -- and ``r_max``, a scalar or
+    shaped as the groups.  scale = bins / r_max, evaluated here: bin i covers i / scale <= r < (i + 1) / scale up to
+    rounding (the rule itself is tc = rho * scale, inside iff 0 <= tc < bins, i = int(tc))."""
+    nr = _energy_bins(bins)
+    c = np.asarray(centers, dtype=np.float64)
+    if c.ndim == 0 or c.shape[-1] not in (2, 3):
+        raise ValueError("centers must have shape (..., 2) or (..., 3)")
+    r = np.asarray(r_max, dtype=np.float64)
+    try:
+        out = np.zeros(np.broadcast_shapes(c.shape[:-1], r.shape) + (4,))
+    except ValueError:
+        raise ValueError("r_max must be a scalar or shaped as the groups of centers")
+    out[..., 0] = c[..., 0]
+    out[..., 1] = c[..., 1]
+    with np.errstate(divide="ignore", invalid="ignore"):
+        out[..., 2] = nr / r
+    return out
+
+
+def auto_energy_params(summary, bins, sigmas=4.0):
+    """The parameters :func:`energy_sweep` chooses from a :func:`spot_sweep` summary: centred on each group's
+    centroid, r_max = ``sigmas * rms_radius`` -- or 1.0 where the group is empty or its RMS radius is not a positive
+    finite number (:func:`auto_image_windows`' rule; a dead group's centroid is NaN and its curves hold nothing)."""
+    rms = np.asarray(summary["rms_radius"], dtype=np.float64)
+    with np.errstate(invalid="ignore"):
+        r_max = sigmas * rms
+        good = (np.asarray(summary["count"]) > 0) & np.isfinite(r_max) & (r_max > 0)
+    return energy_params(summary["centroid"], np.where(good, r_max, 1.0), bins)
+
+
+def spot_energy_raw(plane, group_size, params, bins, stream=None):
+    """Energy histograms of a torch CUDA (N, 8) plane, N = n_groups * group_size (``rtpb_spot_energy``): per group the
+    counts of the rays' distances from the centre in ``bins`` bins, by the radius (k = 0, the circle curve) and by
+    max(|dx|, |dy|) (k = 1, the square curve); ``params`` (n_groups, 4) as :func:`energy_params` gives them.  Returns
+    (hist (n_groups, 2, bins) int32, outside (n_groups, 2) int32, farthest (n_groups, 2) float64), torch: a ray with
+    finite x and y lands in exactly one bin of each curve or in its ``outside``; ``farthest`` is the largest distance
+    of each kind over those rays."""
+    import torch
+    nr = _energy_bins(bins)
+    n = plane.shape[0]
+    if n % group_size:
+        raise ValueError("plane length must be a multiple of group_size")
+    ngroups = n // group_size
+    if torch.is_tensor(params):
+        p = params.to(device=plane.device, dtype=torch.float64).contiguous()
+    else:
+        p = torch.from_numpy(np.array(params, dtype=np.float64)).to(plane.device)
+    if tuple(p.shape) != (ngroups, 4):
+        raise ValueError("params must have shape (n_groups, 4)")
+    plane = plane.contiguous()
+    hist = torch.empty((ngroups, 2, nr), dtype=torch.int32, device=plane.device)
+    outside = torch.empty((ngroups, 2), dtype=torch.int32, device=plane.device)
+    farthest = torch.empty((ngroups, 2), dtype=torch.float64, device=plane.device)
+    if stream is None:
+        stream = torch.cuda.current_stream(plane.device).cuda_stream
+    C.check(C.lib().rtpb_spot_energy(plane.device.index or 0,
+                                     C.RTPB_F64 if plane.dtype == torch.float64 else C.RTPB_F32, plane.data_ptr(),
+                                     group_size, ngroups, p.data_ptr(), nr, hist.data_ptr(), outside.data_ptr(),
+                                     farthest.data_ptr(), stream))
+    return hist, outside, farthest
+
+
+def summarize_energy(hist, outside, farthest, params):
+    """The energy curves from the raw counts (host, NumPy): ``hist`` (..., 2, nr), ``outside`` and ``farthest``
+    (..., 2), ``params`` (..., 4).  ``count`` (int64) is the group's spot count; ``radii`` (..., nr + 1) =
+    arange(nr + 1) / scale are the bin edges; ``encircled`` and ``ensquared`` (..., nr + 1) the fraction of the
+    counted rays within radius (half-side) ``radii[i]`` of the centre -- cumulative counts / count, starting at 0, NaN
+    for an empty group; their last value is 1 - outside / count.  ``outside``, ``farthest``, ``params`` and ``hist``
+    are kept."""
+    hist = np.asarray(hist)
+    outside = np.asarray(outside).astype(np.int64)
+    params = np.asarray(params, dtype=np.float64)
+    nr = hist.shape[-1]
+    count = hist[..., 0, :].sum(axis=-1, dtype=np.int64) + outside[..., 0]
+    cum = np.zeros(hist.shape[:-1] + (nr + 1,), dtype=np.int64)
+    np.cumsum(hist, axis=-1, dtype=np.int64, out=cum[..., 1:])
+    with np.errstate(divide="ignore", invalid="ignore"):
+        radii = np.arange(nr + 1) / params[..., 2, None]
+        frac = cum / count[..., None, None]
+    return {"count": count, "radii": radii, "encircled": frac[..., 0, :], "ensquared": frac[..., 1, :],
+            "outside": outside, "farthest": np.asarray(farthest, dtype=np.float64), "params": params, "hist": hist}
+
+
+def energy_radius(summary, fraction, kind="encircled"):
+    """The radius (``kind="ensquared"``: the half-side) at which a group's curve reaches ``fraction`` of its counted
+    rays, from a :func:`summarize_energy` summary: linear interpolation inside the bin where the curve crosses.  NaN
+    where the fraction is not reached inside r_max (or the group is empty); 0 for ``fraction <= 0``."""
+    if kind not in ("encircled", "ensquared"):
+        raise ValueError('kind must be "encircled" or "ensquared"')
+    curve, radii = summary[kind], summary["radii"]
+    fraction = float(fraction)
+    if fraction <= 0:
+        return np.zeros(curve.shape[:-1])
+    with np.errstate(invalid="ignore", divide="ignore"):
+        reached = curve >= fraction                                # (a NaN curve never does; curve[..., 0] = 0 < fraction)
+        i = np.maximum(np.argmax(reached, axis=-1), 1)[..., None]
+        c0, c1 = np.take_along_axis(curve, i - 1, -1)[..., 0], np.take_along_axis(curve, i, -1)[..., 0]
+        r0, r1 = np.take_along_axis(radii, i - 1, -1)[..., 0], np.take_along_axis(radii, i, -1)[..., 0]
+        r = r0 + (fraction - c0) / (c1 - c0) * (r1 - r0)
+    return np.where(reached.any(axis=-1), r, np.nan)
+
+
+def energy_sweep(system, initial_material, final_material, field_points, wavelengths, theta_max, n_thetas, nphis=1,
+                 center_ray=(0, 0, 1), device="cuda:0", dtype="float64", bins=64, params=None, sigmas=4.0,
+                 groups_per_batch=None, fused=True, devices=None):
+    """ENCIRCLED and ENSQUARED energy for every (field point, wavelength): :func:`spot_sweep`'s fans, each ray's
+    distance from the group's centre counted into two ``bins``-bin histograms in the same pass
+    (``rtpb_energy_sweep``; with ``fused=False`` fan generation -> trace planes='final' -> ``rtpb_spot_energy``;
+    identical results).
+
+    ``params`` (n_fields, n_wavelengths, 4), as :func:`energy_params` gives them, holds each group's centre and
+    r_max.  With ``params=None`` a :func:`spot_sweep` with the same arguments runs first and each group is centred
+    on its centroid with r_max = ``sigmas * rms_radius`` (:func:`auto_energy_params`), so the rays are traced twice.
+    ``devices`` and ``groups_per_batch`` as for :func:`spot_sweep`.
+
+    Returns (summary, timing): :func:`summarize_energy`'s dict with arrays shaped (n_fields, n_wavelengths, ...) --
+    ``encircled`` / ``ensquared`` against ``radii``, ``count``, ``outside``, ``farthest`` (the largest radius and
+    half-side of a counted ray: an r_max that holds everything), ``hist``, ``params``; :func:`energy_radius` reads
+    EE50 / EE80 off it.  The timing dict has :func:`spot_sweep`'s shape and covers the energy pass alone."""
+    nr = _energy_bins(bins)
+    if params is None:
+        spot, _ = spot_sweep(system, initial_material, final_material, field_points, wavelengths, theta_max,
+                             n_thetas, nphis, center_ray=center_ray, device=device, dtype=dtype,
+                             groups_per_batch=groups_per_batch, fused=fused, devices=devices)
+        params = auto_energy_params(spot, nr, sigmas)
+    params = np.ascontiguousarray(params, dtype=np.float64)
+    field_points, wavelengths = _grid(field_points, wavelengths)
+    if params.shape != (field_points.shape[0], wavelengths.size, 4):
+        raise ValueError("params must have shape (n_fields, n_wavelengths, 4)")
+    return _sweep(_energy_mode(params, nr), system, initial_material, final_material,
+                  _fan_source(field_points, wavelengths, theta_max, n_thetas, nphis, center_ray), device, dtype,
+                  groups_per_batch, fused, devices)
+
+
+def _energy_mode(params, nr):
+    """The energy sweep as the drivers see it (:func:`_image_mode`): ``rtpb_energy_sweep`` fused,
+    ``spot_energy_raw`` per plane, no workspace; per device the shard's histograms, outside counts and maxima.
+    ``params`` is C-contiguous (n_fields, n_wavelengths, 4) float64, so the parameters of groups [b0, b1) are
+    contiguous in it."""
+    par = params.reshape(-1, 4)
+
+    def shard(dev, per, g0, n, batch):
+        import torch
+        hist = torch.empty((n, 2, nr), dtype=torch.int32, device=dev)
+        outside = torch.empty((n, 2), dtype=torch.int32, device=dev)
+        farthest = torch.empty((n, 2), dtype=torch.float64, device=dev)
+        return (hist, outside, farthest), lambda b0, b1: (par[b0:b1].ctypes.data, nr,
+                                                          hist[b0 - g0:b1 - g0].data_ptr(),
+                                                          outside[b0 - g0:b1 - g0].data_ptr(),
+                                                          farthest[b0 - g0:b1 - g0].data_ptr())
+
+    def finish(nf, nw, hist, outside, farthest):
+        return summarize_energy(hist.reshape(nf, nw, 2, nr), outside.reshape(nf, nw, 2),
+                                farthest.reshape(nf, nw, 2), params)
+
+    return SimpleNamespace(
+        entry="rtpb_energy_sweep", ncols=None, shard=shard, finish=finish,
+        # the counters and maxima, cleared and then added to (the rays never leave the registers)
+        hbm_bytes=lambda per, n: n * ((2 * nr + 2) * 4 + 2 * 8) * 2,
+        host=lambda G: (np.zeros((G, 2, nr), dtype=np.int32), np.zeros((G, 2), dtype=np.int32), np.zeros((G, 2))),
+        plane=lambda out, per, b0, nb: spot_energy_raw(out, per, par[b0:b0 + nb], nr))
+
+
 def collimated_spot_sweep(system, initial_material, final_material, normals, wavelengths, displacement_max, n_disps,
                           nphis=1, phi_start=0., pt=(0, 0, 0), device="cuda:0", dtype="float64",
                           groups_per_batch=None, fused=True, devices=None):
@@ -841,6 +1019,26 @@ def collimated_image_sweep(system, initial_material, final_material, normals, wa
     if windows.shape != (source.nf, source.nw, 4):
         raise ValueError("windows must have shape (n_fields, n_wavelengths, 4)")
     return _sweep(_image_mode(windows, nx, ny), system, initial_material, final_material, source, device, dtype,
+                  groups_per_batch, fused, devices)
+
+
+def collimated_energy_sweep(system, initial_material, final_material, normals, wavelengths, displacement_max, n_disps,
+                            nphis=1, phi_start=0., pt=(0, 0, 0), device="cuda:0", dtype="float64", bins=64,
+                            params=None, sigmas=4.0, groups_per_batch=None, fused=True, devices=None):
+    """Encircled and ensquared energy of :func:`collimated_spot_sweep`'s beams: :func:`energy_sweep` with that source
+    (``rtpb_energy_sweep_collimated``, or unfused through ``rtpb_spot_energy``; identical results).  With
+    ``params=None`` a :func:`collimated_spot_sweep` of the same beams chooses them."""
+    nr = _energy_bins(bins)
+    beam = (normals, wavelengths, displacement_max, n_disps, nphis, phi_start, pt)
+    if params is None:
+        spot, _ = collimated_spot_sweep(system, initial_material, final_material, *beam, device=device, dtype=dtype,
+                                        groups_per_batch=groups_per_batch, fused=fused, devices=devices)
+        params = auto_energy_params(spot, nr, sigmas)
+    params = np.ascontiguousarray(params, dtype=np.float64)
+    source = _beam_source(*beam)
+    if params.shape != (source.nf, source.nw, 4):
+        raise ValueError("params must have shape (n_fields, n_wavelengths, 4)")
+    return _sweep(_energy_mode(params, nr), system, initial_material, final_material, source, device, dtype,
                   groups_per_batch, fused, devices)
 
 

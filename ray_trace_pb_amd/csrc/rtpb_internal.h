@@ -471,6 +471,12 @@ int image_check(const char* call, int32_t nx, int32_t ny, int64_t group_size, in
                 const void* image_out, const void* outside_out);
 int image_clear(int32_t* image_out, int32_t* outside_out, int64_t n_groups, int32_t nx, int32_t ny, hipStream_t st);
 
+// The same for the energy calls (rtpb_energy.hip; "spot-energy", "energy-sweep"): nr bins, the three outputs.
+int energy_check(const char* call, int32_t nr, int64_t group_size, int64_t n_groups, const void* params,
+                 const void* hist_out, const void* outside_out, const void* farthest_out);
+int energy_clear(int32_t* hist_out, int32_t* outside_out, double* farthest_out, int64_t n_groups, int32_t nr,
+                 hipStream_t st);
+
 }  // namespace rtpbi
 
 // ---------------------------------------------------------------------------------- plans

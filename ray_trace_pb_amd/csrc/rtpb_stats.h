@@ -1,6 +1,6 @@
-// rtpb_stats.h -- what the plane kernels (rtpb_analysis.hip, rtpb_image.hip) and the fused sweep (rtpb_sweep.hip)
-// share: the statistics sets, the one definition of a ray's contribution to the focus statistics, to the wavefront
-// statistics and to a spot image, the footprint statistics' term (rtpb_foot.h, plain C++ so that the host can run it)
+// rtpb_stats.h -- what the plane kernels (rtpb_analysis.hip, rtpb_image.hip, rtpb_energy.hip) and the fused sweep
+// (rtpb_sweep.hip) share: the statistics sets, the one definition of a ray's contribution to the focus statistics, to
+// the wavefront statistics, to a spot image and to the energy curves, the footprint statistics' term (rtpb_foot.h, plain C++ so that the host can run it)
 // and its wave and block reductions,
 // the wave's aggregated image adds, the reduction's argument block and its block-wide tree.  Everything here has
 // internal linkage, as it had inside the one unit: each unit's kernels take its own SpotArgs.
@@ -146,6 +146,63 @@ __device__ __forceinline__ void wave_image_add(int bin, int32_t* __restrict__ im
         if (lane == leader) atomicAdd(image + b, __popcll(same));
         pending &= ~same;
     }
+}
+
+// Encircled / ensquared energy (rtpb_spot_energy / rtpb_energy_sweep): two radial histograms of the final positions
+// per group, int32 counts, and the farthest ray of each.  The one definition of a ray's contribution, for the plane
+// kernel and the fused sweep alike: x and y are the ray's final position rounded to the storage type, p the group's
+// parameters {cx, cy, scale, 0} with scale = nr / r_max.  A ray counts when the spot statistics count it (x and y
+// finite).  dx = x - cx, dy = y - cy, rho = sqrt(dx dx + dy dy) (the correctly rounded root, tsqrt), m = max(|dx|,
+// |dy|), tc = rho * scale, ts = m * scale, each one rounded operation; the ray is inside the circle curve iff
+// 0 <= tc < nr and inside the square curve iff 0 <= ts < nr, compared in floating point (a NaN or infinite scale, or
+// an overflowing product, is outside), and only then is the value converted to an integer.  bin[k] is the bin,
+// kImageOutside for a counting ray that is not inside, kImageSkip for a ray that does not count (k = 0 the circle,
+// 1 the square); far[k] is rho and m, +0 for a ray that does not count.  A centre that is not finite (NaN or
+// infinite cx or cy) puts every counting ray outside both curves with far = +0: it leaves the group's farthest
+// untouched.  With a finite centre rho and m are never NaN and never negative (+inf where a product overflows), so
+// they order as their bit patterns.
+struct EnergyRay {
+    int bin[2];
+    double far[2];
+};
+RTPB_HD EnergyRay energy_bins(double x, double y, const double (&p)[4], int nr) {
+    if (!(x - x == 0.0 && y - y == 0.0)) return EnergyRay{{kImageSkip, kImageSkip}, {0.0, 0.0}};
+    if (!(p[0] - p[0] == 0.0 && p[1] - p[1] == 0.0)) return EnergyRay{{kImageOutside, kImageOutside}, {0.0, 0.0}};
+    const double dx = x - p[0], dy = y - p[1];
+    const double rho = rtpb::tsqrt<double>(dx * dx + dy * dy);
+    const double ax = __builtin_fabs(dx), ay = __builtin_fabs(dy);      // (a -0.0 offset is +0 from here on)
+    const double m = ax > ay ? ax : ay;
+    const double tc = rho * p[2], ts = m * p[2];
+    EnergyRay e{{kImageOutside, kImageOutside}, {rho, m}};
+    if (tc >= 0.0 && tc < double(nr)) e.bin[0] = static_cast<int>(tc);
+    if (ts >= 0.0 && ts < double(nr)) e.bin[1] = static_cast<int>(ts);
+    return e;
+}
+
+// One wave's largest v into *out, v >= +0 and not NaN (so the doubles order as their bit patterns, and +0 is all zero
+// bits: the cleared output).  Every lane of the wave must call it; a lane with nothing to add passes +0.  The wave is
+// reduced first and one lane issues one unsigned 64-bit atomic max -- and only when the wave's maximum is above what
+// *out holds already: the value only ever grows, so a stale read can cost a redundant atomic and never a lost one, and
+// all but a group's first few waves leave the one address alone (+0, the cleared value, is never above it).
+__device__ __forceinline__ void wave_max_bits(double v, double* __restrict__ out) {
+    unsigned long long b = static_cast<unsigned long long>(__double_as_longlong(v));
+#pragma unroll
+    for (int w = 32; w > 0; w >>= 1) {
+        const unsigned long long o = __shfl_xor(b, w, 64);
+        b = o > b ? o : b;
+    }
+    unsigned long long* const p = reinterpret_cast<unsigned long long*>(out);
+    if (__lane_id() == 0 && b > __builtin_nontemporal_load(p)) atomicMax(p, b);
+}
+
+// One wave's contributions to one group's energy curves (hist: the group's 2 * nr counters, outside and farthest: its
+// two of each; all wave-uniform), e from energy_bins.  Every lane of the wave must call it.
+__device__ __forceinline__ void wave_energy_add(const EnergyRay& e, int nr, int32_t* __restrict__ hist,
+                                                int32_t* __restrict__ outside, double* __restrict__ farthest) {
+    wave_image_add(e.bin[0], hist, outside);
+    wave_image_add(e.bin[1], hist + nr, outside + 1);
+    wave_max_bits(e.far[0], farthest);
+    wave_max_bits(e.far[1], farthest + 1);
 }
 
 struct SpotArgs {

@@ -6,7 +6,8 @@
 // rtpb_sweep_variants_beam.hip hold the focus sweep over many systems (rtpb_focus_sweep_variants[_collimated]),
 // rtpb_sweep_wave_variants.hip and rtpb_sweep_wave_variants_beam.hip the wavefront sweep over many systems and the
 // final rays of small groups (rtpb_wavefront_sweep_variants[_collimated], rtpb_final_rays_variants[_collimated]);
-// rtpb_sweep_foot.hip and rtpb_sweep_foot_beam.hip the footprint sweep (rtpb_footprint_sweep[_collimated]).
+// rtpb_sweep_foot.hip and rtpb_sweep_foot_beam.hip the footprint sweep (rtpb_footprint_sweep[_collimated]);
+// rtpb_sweep_energy.hip and rtpb_sweep_energy_beam.hip the energy sweep (rtpb_energy_sweep[_collimated]).
 // What the sweep shares with the plane kernels (the statistics, the image's contribution rule) is rtpb_stats.h, the
 // host arithmetic of a call (row planning, media table, upload layout) rtpb_sweep_host.h.
 #pragma once
@@ -42,6 +43,7 @@ constexpr int kFrame = 9;               // a beam's frame: normal, n1, n2
 struct SweepImage;
 struct SweepWave;
 struct SweepFoot;
+struct SweepEnergy;
 struct SweepArgs {
     const DevSurface<double>* __restrict__ surf;     // the plan's surfaces; variant sweeps: desc [n_variants][nsurf]
     union {
@@ -63,6 +65,7 @@ struct SweepArgs {
         const SweepImage* __restrict__ image;       // image mode
         const SweepWave* __restrict__ wave;         // wavefront mode
         const SweepFoot* __restrict__ foot;         // footprint mode
+        const SweepEnergy* __restrict__ energy;     // energy mode
     };
     // ray j of a group: j % n_thetas indexes the first table, j / n_thetas the second (the beam's n_thetas is its
     // nphis, its nphis its n_disps)
@@ -102,6 +105,16 @@ struct SweepFoot {
     double* partials;
 };
 static_assert(sizeof(SweepFoot) == sizeof(double), "the frames follow it");
+
+// The energy mode's block of the upload, in the same place: the outputs and the number of bins, followed by the
+// groups' parameters (4 doubles each: cx, cy, scale, 0; rtpb_stats.h energy_bins)
+struct SweepEnergy {
+    int32_t* hist;       // [n_groups][2][nr]
+    int32_t* outside;    // [n_groups][2]
+    double* farthest;    // [n_groups][2]
+    int32_t nr, pad;
+};
+static_assert(sizeof(SweepEnergy) % sizeof(double) == 0, "the parameters follow it");
 
 template <typename TS>
 __device__ __forceinline__ double stored(double v) { return static_cast<double>(static_cast<TS>(v)); }
@@ -160,6 +173,11 @@ constexpr int kStateRows = 11;                     // bundle state per lane: x y
 // every surface, its roots and square roots included, and no carried x x + y y) and the final state is the one
 // rtpb_trace stores, phase and all; eight of the fifteen statistics at a time.
 constexpr int kImageStats = 0;
+// NS = kEnergyStats (rtpb_energy_sweep; the value is the mode's tag, the two curves): the image mode with another rule
+// per ray -- each counted ray goes into its group's circle and square histograms and into the two maxima
+// (energy_bins, wave_energy_add).  Everything else is the image mode's: which rays count, the kPosOnly steps, single
+// and bundle rows, both storage types, the occupancy class, no red tiles.
+constexpr int kEnergyStats = 2;
 // NS = kFinalRays (rtpb_final_rays_variants; variants, float64, single rows, groups of at most one tile): no
 // reduction, each ray's final state goes to rays_out[group][ray] as the row rtpb_trace stores for the final plane (a
 // killed ray's NaN pattern included), so the steps are the wavefront mode's.  Lanes past the group's size store nothing.
@@ -186,8 +204,8 @@ __global__ __launch_bounds__(kBlock) RTPB_SWEEP_ATTR(NS) void sweep_kernel(Sweep
                   "variants: the focus or wavefront statistics or the final rays, host-evaluated media");
     static_assert(!BUNDLE || (FEAT & 16) != 0, "bundles: host-evaluated media");
     static_assert(NS == kStats || NS == kFocusStats || NS == kImageStats || NS == kWaveStats || NS == kFinalRays ||
-                      NS == kFootStats,
-                  "spot, focus, wavefront or footprint statistics, the image, or the final rays");
+                      NS == kFootStats || NS == kEnergyStats,
+                  "spot, focus, wavefront or footprint statistics, the image, the energy curves, or the final rays");
     constexpr bool kFoot = NS == kFootStats;
     static_assert(!kFoot || (!kVar && !BUNDLE && sizeof(TS) == 8), "footprints: float64, single rows, no variants");
     constexpr bool kWave = NS == kWaveStats;
@@ -195,7 +213,8 @@ __global__ __launch_bounds__(kBlock) RTPB_SWEEP_ATTR(NS) void sweep_kernel(Sweep
     constexpr bool kRays = NS == kFinalRays;
     static_assert(!kRays || (kVar && !BUNDLE && sizeof(TS) == 8), "final rays: variants, float64, single rows");
     constexpr bool kPhase = kWave || kRays;          // the trace kernel's full steps, the phase kept
-    constexpr int kRedRows = NS == kImageStats || kRays || kFoot ? 1 : BUNDLE ? 2 : NS == kStats ? kStats : 8;
+    constexpr bool kCounts = NS == kImageStats || NS == kEnergyStats;     // integer counters, no statistics
+    constexpr int kRedRows = kCounts || kRays || kFoot ? 1 : BUNDLE ? 2 : NS == kStats ? kStats : 8;
     __shared__ double red[kRedRows][kBlock];
     __shared__ double state[BUNDLE ? kStateRows : 1][kBlock];
     // footprints: per wave, one row per surface (16 KB)
@@ -405,6 +424,18 @@ __global__ __launch_bounds__(kBlock) RTPB_SWEEP_ATTR(NS) void sweep_kernel(Sweep
         }
         wave_image_add(bin, im->image + g * ny * nx, im->outside + g);
     };
+    // ... and the energy mode's, by the same rule
+    auto to_energy = [&](const Ray<double>& rr, bool ok, int64_t g) {
+        const cptr<SweepEnergy> en = (cptr<SweepEnergy>)(a.energy);
+        const cptr<double> par = (cptr<double>)(a.energy + 1) + 4 * g;
+        const int nr = en->nr;
+        EnergyRay e{{kImageSkip, kImageSkip}, {0.0, 0.0}};
+        if (ok && !is_nan(rr.dx)) {
+            const double p[4] = {par[0], par[1], par[2], par[3]};
+            e = energy_bins(stored<TS>(rr.x), stored<TS>(rr.y), p, nr);
+        }
+        wave_energy_add(e, nr, en->hist + g * 2 * nr, en->outside + 2 * g, en->farthest + 2 * g);
+    };
     if constexpr (!BUNDLE) {
 #pragma unroll
         for (int q = 0; q < kSweepRays; ++q) {
@@ -446,6 +477,8 @@ __global__ __launch_bounds__(kBlock) RTPB_SWEEP_ATTR(NS) void sweep_kernel(Sweep
         for (int q = 0; q < kSweepRays; ++q) {
             if constexpr (NS == kImageStats) {
                 to_image(r[q], tile[q] * kBlock + tid < a.gsize, grp[q]);
+            } else if constexpr (NS == kEnergyStats) {
+                to_energy(r[q], tile[q] * kBlock + tid < a.gsize, grp[q]);
             } else if constexpr (kRays) {
                 // a plain per-lane store of the row (four 16-byte stores), inside the group's own rows only
                 const int64_t j = tile[q] * kBlock + tid;
@@ -546,6 +579,7 @@ __global__ __launch_bounds__(kBlock) RTPB_SWEEP_ATTR(NS) void sweep_kernel(Sweep
 #pragma unroll
             for (int q = 0; q < kSweepRays; ++q) {
                 if constexpr (NS == kImageStats) to_image(r[q], t0 * kBlock + tid < a.gsize, grp[q]);
+                else if constexpr (NS == kEnergyStats) to_energy(r[q], t0 * kBlock + tid < a.gsize, grp[q]);
                 else reduce(r[q], t0 * kBlock + tid < a.gsize, grp[q], t0);
             }
         }
@@ -676,6 +710,31 @@ struct ImageCall {
     int32_t* outside_out;
 };
 
+// ... those of the energy sweeps (no workspace, no statistics; `what` names the call in the messages) ...
+template <int SRC = kSrcFan>
+int energy_sweep_check(const char* what, const char* too_many, int64_t n_groups, const double* group_params,
+                       const SweepSource& s, const double* params, int32_t nr, int32_t* hist_out,
+                       int32_t* outside_out, double* farthest_out) {
+    if (n_groups <= 0 || !s.complete(SRC) || !group_params)
+        return fail(RTPB_E_INVALID, SRC == kSrcBeam ? "bad energy-sweep-collimated arguments"
+                                                    : "bad energy-sweep arguments");
+    // (n_a * n_b: a product past int64 is past the limit too)
+    const int64_t gsize = s.n_a > 0x7fffffffll / s.n_b ? 0x80000000ll : s.n_a * s.n_b;
+    int rc = energy_check(what, nr, gsize, n_groups, params, hist_out, outside_out, farthest_out);
+    if (rc) return rc;
+    if (n_groups > 65535) return fail(RTPB_E_LIMIT, too_many);
+    return RTPB_OK;
+}
+
+// rtpb_energy_sweep's own arguments (NS = kEnergyStats: no workspace, no statistics)
+struct EnergyCall {
+    const double* params;       // host, n_groups x 4
+    int32_t nr;
+    int32_t* hist_out;
+    int32_t* outside_out;
+    double* farthest_out;
+};
+
 // A variant sweep's systems (SRC | kSrcVariant), lowered on the host (lower_variants): no plan and no device blob, the
 // descriptors ride in the call's upload.  All variants have nsurf surfaces and nsurf + 1 materials.
 struct VariantCall {
@@ -697,10 +756,14 @@ struct VariantCall {
 // NS = kFinalRays: no workspace and no reduction; stats_out is rays_out, n_groups x gsize x 8, written by the kernel.
 // NS = kFootStats: refs is the surfaces' frames (host, nsurf x kFootFrame), the workspace holds the blocks' partials
 // (n_groups x ceil(tiles / kSweepRays) x nsurf x kFootCols) and stats_out is n_groups x nsurf x kFootCols.
+// NS = kEnergyStats: en holds the call's parameters and outputs, as im does the image's; no workspace, no statistics.
 template <int NS, int SRC = kSrcFan>
 int sweep_impl(const rtpb_plan* plan_c, int32_t device, int64_t n_groups, const double* group_params,
                const SweepSource& src, double* workspace, double* stats_out, void* stream,
-               const ImageCall* im = nullptr, const double* refs = nullptr, const VariantCall* vc = nullptr) {
+               const ImageCall* im = nullptr, const double* refs = nullptr, const VariantCall* vc = nullptr,
+               const EnergyCall* en = nullptr) {
+    constexpr bool kEnergy = NS == kEnergyStats;
+    static_assert(!kEnergy || (SRC & kSrcVariant) == 0, "energy curves: no variants");
     constexpr bool kImage = NS == kImageStats, kWave = NS == kWaveStats, kBeam = (SRC & ~kSrcVariant) == kSrcBeam;
     constexpr bool kVar = (SRC & kSrcVariant) != 0, kRays = NS == kFinalRays, kFoot = NS == kFootStats;
     static_assert(!kFoot || !kVar, "footprints: no variants");
@@ -728,8 +791,9 @@ int sweep_impl(const rtpb_plan* plan_c, int32_t device, int64_t n_groups, const 
     // all head: SweepFoot and the surfaces' frames, nothing per group)
     const SweepLayout lay(src.n_a, kBeam ? (src.n_b + 1) / 2 : src.n_b, n_groups, pre_n ? M + 3 * (M - 1) : 0,
                           pr.bundles.size() + pr.singles.size() + pr.rows.size() + (kVar ? size_t(n_groups) : 0),
-                          kImage  ? sizeof(SweepImage) / sizeof(double)
-                          : kWave ? sizeof(SweepWave) / sizeof(double)
+                          kImage    ? sizeof(SweepImage) / sizeof(double)
+                          : kEnergy ? sizeof(SweepEnergy) / sizeof(double)
+                          : kWave   ? sizeof(SweepWave) / sizeof(double)
                           : kFoot ? sizeof(SweepFoot) / sizeof(double) + size_t(nsurf) * kFootFrame
                                   : 0,
                           kWave ? kWaveRef : kFoot ? 0 : 4, kBeam ? kFrame : 0,
@@ -767,6 +831,13 @@ int sweep_impl(const rtpb_plan* plan_c, int32_t device, int64_t n_groups, const 
         rc = image_clear(im->image_out, im->outside_out, n_groups, im->nx, im->ny, st);
         if (rc) return rc;
     }
+    if constexpr (kEnergy) {
+        const SweepEnergy head{en->hist_out, en->outside_out, en->farthest_out, en->nr, 0};
+        std::memcpy(h + lay.img, &head, sizeof(head));
+        std::memcpy(h + lay.win, en->params, size_t(4 * n_groups) * sizeof(double));
+        rc = energy_clear(en->hist_out, en->outside_out, en->farthest_out, n_groups, en->nr, st);
+        if (rc) return rc;
+    }
     if constexpr (kWave) {
         const SweepWave head{workspace};
         std::memcpy(h + lay.img, &head, sizeof(head));
@@ -800,6 +871,7 @@ int sweep_impl(const rtpb_plan* plan_c, int32_t device, int64_t n_groups, const 
     a.grp = reinterpret_cast<const double*>(d + lay.grp);
     a.gn = reinterpret_cast<const double*>(d + lay.gn);
     if constexpr (kImage) a.image = reinterpret_cast<const SweepImage*>(d + lay.img);
+    else if constexpr (kEnergy) a.energy = reinterpret_cast<const SweepEnergy*>(d + lay.img);
     else if constexpr (kWave) a.wave = reinterpret_cast<const SweepWave*>(d + lay.img);
     else if constexpr (kFoot) a.foot = reinterpret_cast<const SweepFoot*>(d + lay.img);
     else if constexpr (kRays) a.partials = stats_out;
@@ -851,7 +923,7 @@ int sweep_impl(const rtpb_plan* plan_c, int32_t device, int64_t n_groups, const 
     if constexpr (kFoot) {
         rc = launch_foot_final(workspace, stats_out, n_groups, (tiles + kSweepRays - 1) / kSweepRays, nsurf, st);
         if (rc) return rc;
-    } else if constexpr (!kImage && !kRays) {
+    } else if constexpr (!kImage && !kEnergy && !kRays) {
         rc = launch_stats_final(NS, workspace, stats_out, n_groups, tiles, st);
         if (rc) return rc;
     }
