@@ -63,7 +63,8 @@ extern "C" {
                                     rtpb_final_rays_variants / _variants_collimated, then rtpb_footprint_stats /
                                     rtpb_footprint_sweep / rtpb_footprint_sweep_collimated (per-surface beam
                                     footprints and vignetting), then rtpb_spot_energy / rtpb_energy_sweep /
-                                    rtpb_energy_sweep_collimated (encircled and ensquared energy) joined within 10:
+                                    rtpb_energy_sweep_collimated (encircled and ensquared energy), then
+                                    rtpb_huygens_psf (the diffraction PSF of a plane) joined within 10:
                                     new symbols only, nothing existing changed */
 
 /* ---- error codes ---------------------------------------------------------------------------- */
@@ -548,6 +549,49 @@ int rtpb_energy_sweep_collimated(const rtpb_plan* plan, int32_t device, int64_t 
                                  const double* group_frames, int64_t n_disps, int64_t nphis, const double* offsets,
                                  const double* phi_cos_sin, const double* params, int32_t nr, int32_t* hist_out,
                                  int32_t* outside_out, double* farthest_out, void* stream);
+
+/* HUYGENS PSF: per group, the complex field on a grid of image-plane pixels as the coherent sum of the rays' plane
+   wavelets -- the diffraction spot itself, from which the true Strehl ratio and the MTF follow on the host.  No
+   interpolation, no triangulation, no FFT sampling constraint; a vignetted pupil is fewer rays.
+   A group's REFERENCE is the wavefront calls' eight doubles {C0, d0, p0, kf}.  A group's WINDOW is four doubles
+   {cx, cy, sx, sy}: pixel (ix, iy) of the nx x ny field lies at
+       X = ((double)ix - cx) * sx;   Y = ((double)iy - cy) * sy        (one rounded subtract, one rounded multiply)
+   from C0 in the image plane, so with cx = (nx - 1) / 2 the centre pixel is exactly C0.  float64 ONLY, for the
+   wavefront calls' reason (a float32 dtype is RTPB_E_INVALID).  Per ray j of a group, with (n, w, ex, ey) the count
+   flag, the OPD in waves and the direction offset that the wavefront statistics define above (the same operations,
+   the same counting rule), every step one rounded IEEE operation in this order, no FMA:
+       a  = n * weight[j]                      (weight[j] = 1 when weights == NULL)
+       qx = ex * kf;   qy = ey * kf
+   and per (ray, pixel):
+       t  = (w + qx * X) + qy * Y
+       fr = t - rint(t)                        (exact; |fr| <= 0.5: whole waves leave before the sine is taken)
+       (s, c) = sincospi(2 * fr)               (the device library's double sincospi)
+       re += a * c;   im += a * s
+   e = d - d0 in d's place removes a linear phase common to all rays: |E|^2 is unchanged and t stays small.
+   A ray that does NOT COUNT adds nothing: it is skipped, not multiplied by zero, so a NaN weight on a dead ray, or
+   a NaN window, cannot reach the sum through it.  On a counting ray a non-finite t or a propagates: a NaN or
+   infinite window entry, or a NaN weight on a live ray, gives NaN in every pixel it touches (a NaN window: the
+   group's whole field).  A NaN in the reference makes every ray not count: the field is +0 everywhere and the norm
+   0, whatever the window.
+   field_out (device, n_groups * ny * nx * 2 doubles): re, im interleaved, pixel (ix, iy) of group g at
+   ((g * ny + iy) * nx + ix) * 2: it views as complex128 (n_groups, ny, nx).  norm_out (device, n_groups doubles): the
+   sum of a over the group's counting rays, the amplitude an aberration-free wavefront reaches at C0, so
+   |E|^2 / norm^2 at C0 is the Strehl ratio.  Every element of both is written: the caller need not clear them.
+   DETERMINISTIC: each pixel's sums, and the norm, are taken in an order fixed by (group_size, nx, ny) alone: the
+   rays are split into segments of whole 256-ray tiles (as many as spread a group over about 1024 blocks, one where
+   the window alone does), one thread adds a segment's rays in ray order, and a second pass adds the segments'
+   partial sums in segment order.  No atomics; two calls give the same bits, whatever the stream and however the
+   groups are divided among calls.
+   plane: one (N, 8) AOS float64 plane split into groups as for rtpb_wavefront_stats.  refs: HOST, n_groups x 8;
+   windows: HOST, n_groups x 4 (one upload on `stream`); weights: DEVICE, group_size doubles shared by all groups, or
+   NULL.  1 <= nx, ny <= RTPB_MAX_PSF_SIDE (RTPB_E_LIMIT above, RTPB_E_INVALID below), n_groups <= 65535
+   (RTPB_E_LIMIT), group_size >= 1; no workspace (the partial sums of split groups are stream-ordered scratch of at
+   most 256 MiB).  The cost is group_size * nx * ny sincospi per group.  The
+   arguments are checked before the device is. */
+#define RTPB_MAX_PSF_SIDE 2048
+int rtpb_huygens_psf(int32_t device, int32_t dtype, const void* plane, int64_t group_size, int64_t n_groups,
+                     const double* refs, const double* windows, const double* weights, int32_t nx, int32_t ny,
+                     double* field_out, double* norm_out, void* stream);
 
 /* FOOTPRINT statistics: per (group, surface), how many rays reach the surface, how many it lets through, and how much
    of it the beam uses -- which surface vignettes which field, and the clear semi-diameter each surface needs.  They

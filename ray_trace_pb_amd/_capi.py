@@ -20,6 +20,7 @@ RTPB_CONSTANT, RTPB_SELLMEIER, RTPB_POLY6, RTPB_TABLE = 0, 1, 2, 3
 RTPB_MAX_SURFACES = 63
 RTPB_MAX_IMAGE_SIDE = 4096
 RTPB_MAX_ENERGY_BINS = 4096
+RTPB_MAX_PSF_SIDE = 2048
 RTPB_PLANES_FINAL, RTPB_OUT_SOA = 0x1, 0x2          # plane_mask_flags of rtpb_trace_f64 / _f32
 RTPB_OK, RTPB_E_INVALID, RTPB_E_HIP, RTPB_E_NODEV, RTPB_E_LIMIT = 0, -1, -2, -3, -4
 
@@ -150,6 +151,8 @@ SIGNATURES = {
                                          _P]),
     "rtpb_energy_sweep_collimated": (ctypes.c_int, [_P, _i32, _i64, _P, _P, _i64, _i64, _P, _P, _P, _i32, _P, _P, _P,
                                                     _P]),
+    # (the wavefront plane call's head; refs and windows on the host, weights on the device, the sides, two outputs)
+    "rtpb_huygens_psf": (ctypes.c_int, [_i32, _i32, _P, _i64, _i64, _P, _P, _P, _i32, _i32, _P, _P, _P]),
     "rtpb_set_tuning":(ctypes.c_int, [ctypes.c_char_p, _i64]),
     "rtpb_timing_enable": (ctypes.c_int, [_i32]),
     "rtpb_timing_collect": (ctypes.c_int, [ctypes.POINTER(_dbl), ctypes.POINTER(_i64)]),

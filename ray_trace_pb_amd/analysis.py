@@ -17,7 +17,9 @@ at EVERY surface in the same single pass -- per (group, surface) the rays that a
 footprint: which surface vignettes which field (``rtpb_footprint_sweep[_collimated]``; ``rtpb_footprint_stats`` for a
 stored history).  :func:`energy_sweep` and :func:`collimated_energy_sweep` give the encircled and ensquared energy
 curves of every group (``rtpb_energy_sweep[_collimated]``; ``rtpb_spot_energy`` for a stored plane), from which
-:func:`energy_radius` reads EE50 / EE80.
+:func:`energy_radius` reads EE50 / EE80.  :func:`huygens_psf` and :func:`collimated_huygens_psf` give the diffraction spot
+itself -- each group's field as the coherent sum of its rays' wavelets on a grid of image-plane pixels
+(``rtpb_huygens_psf`` on the traced final plane), hence the true Strehl ratio and, through :func:`psf_mtf`, the MTF.
 """
 import contextlib
 import copy
@@ -1080,6 +1082,269 @@ def collimated_wavefront_sweep(system, initial_material, final_material, normals
     refs = _wave_refs(refs, (source.nf, source.nw, 8))
     return _sweep(_wave_mode(refs), system, initial_material, final_material, source, device, "float64",
                   groups_per_batch, fused, devices)
+
+
+def _psf_sides(n, ny=None):
+    """(nx, ny) from one side, or two."""
+    sides = (n, n if ny is None else ny)
+    try:
+        ok = all(np.ndim(s) == 0 and float(s) == int(s) and 1 <= int(s) <= C.RTPB_MAX_PSF_SIDE for s in sides)
+    except (TypeError, ValueError):
+        ok = False
+    if not ok:
+        raise ValueError(f"the sides of a PSF window must be ints in 1 ... {C.RTPB_MAX_PSF_SIDE}")
+    return int(sides[0]), int(sides[1])
+
+
+def psf_windows(half_width, n, ny=None):
+    """Windows (..., 4) float64 {cx, cy, sx, sy} of Huygens PSFs with ``n`` x ``ny`` pixels (``ny`` = ``n`` when None)
+    reaching ``half_width`` to either side of the reference point: c = (side - 1) / 2 and s = half_width / c, so pixel
+    i lies at (i - c) * s, the outermost at -+half_width and, for an odd side, the centre pixel exactly on the
+    reference point.  A side of 1 gives s = 0: its one pixel is the reference point.  ``half_width`` is a scalar
+    (the result is (1, 4), which broadcasts over the groups) or shaped as the groups."""
+    nx, ny = _psf_sides(n, ny)
+    h = np.atleast_1d(np.asarray(half_width, dtype=np.float64))
+    out = np.empty(h.shape + (4,))
+    out[..., 0], out[..., 1] = (nx - 1) / 2, (ny - 1) / 2
+    out[..., 2] = h / out[..., 0] if nx > 1 else 0.0
+    out[..., 3] = h / out[..., 1] if ny > 1 else 0.0
+    return out
+
+
+def fan_area_weights(theta_max, n_thetas, nphis):
+    """The pupil area each ray of ``get_ray_fan(pt, theta_max, n_thetas, wavelength, nphis)`` stands for, up to a
+    common factor: |sin theta| of its polar angle (the rays are evenly spaced in theta and in phi, so a ray's patch of
+    the sphere is sin theta dtheta dphi).  Ray k = iphi * n_thetas + itheta, thetas = linspace(-theta_max,
+    theta_max, n_thetas).  (n_thetas * nphis,) float64."""
+    return np.tile(np.abs(np.sin(np.linspace(-theta_max, theta_max, int(n_thetas)))), int(nphis))
+
+
+def beam_area_weights(displacement_max, n_disps, nphis):
+    """The same for ``get_collimated_rays(pt, displacement_max, n_disps, wavelength, nphis)``: |offset| of the ray's
+    ring (evenly spaced radii and angles: a patch is r dr dphi).  Ray k = idisp * nphis + iphi, offsets =
+    linspace(-displacement_max, displacement_max, n_disps).  (n_disps * nphis,) float64."""
+    return np.repeat(np.abs(np.linspace(-displacement_max, displacement_max, int(n_disps))), int(nphis))
+
+
+def huygens_psf_raw(plane, group_size, refs, windows, nx, ny, weights=None, stream=None):
+    """The Huygens field of a torch CUDA (N, 8) float64 plane, N = n_groups * group_size (``rtpb_huygens_psf``): per
+    group, E(X, Y) = sum a exp(2 pi i (w + kf (ex X + ey Y))) over its counting rays on the ``nx`` x ``ny`` pixels
+    of its window, with w (the OPD in waves) and e = d - d0 measured against ``refs`` (n_groups, 8) exactly as
+    :func:`wavefront_stats_raw` does and a = ``weights[j]`` for ray j of every group (``None``: 1).  ``windows`` is
+    (n_groups, 4), or (1, 4) for all groups, as :func:`psf_windows` gives them; ``weights`` ``group_size`` doubles,
+    NumPy or torch.  Returns (field (n_groups, ny, nx) complex128, norm (n_groups,) float64), torch: norm is the sum
+    of a over the counting rays, what |E| would be at the reference point without aberrations.
+
+    A NaN reference counts no ray: field 0, norm 0.  A NaN window, or a NaN weight on a ray that counts, gives NaN.
+    Each pixel is summed in an order fixed by (group_size, nx, ny): two calls give the same bits, and a group gives
+    the same bits whichever groups share its call.  The cost is group_size * nx * ny
+    complex exponentials per group.  float64 only, as the wavefront statistics."""
+    import torch
+    if plane.dtype != torch.float64:
+        raise ValueError("the Huygens PSF needs a float64 plane: a float32 phase of 1e4 ... 1e7 rad has an ulp of a "
+                         "milliradian to a radian")
+    nx, ny = _psf_sides(nx, ny)
+    n = plane.shape[0]
+    if n % group_size:
+        raise ValueError("plane length must be a multiple of group_size")
+    ngroups = n // group_size
+    refs = _wave_refs(refs, (ngroups, 8))
+    win = np.asarray(windows, dtype=np.float64)
+    if win.shape not in ((ngroups, 4), (1, 4)):
+        raise ValueError("windows must have shape (n_groups, 4) or (1, 4)")
+    win = np.ascontiguousarray(np.broadcast_to(win, (ngroups, 4)))
+    if weights is not None:
+        if not torch.is_tensor(weights):
+            weights = torch.from_numpy(np.ascontiguousarray(weights, dtype=np.float64))
+        weights = weights.to(device=plane.device, dtype=torch.float64).contiguous()
+        if tuple(weights.shape) != (group_size,):
+            raise ValueError("weights must have shape (group_size,)")
+    plane = plane.contiguous()
+    field = torch.empty((ngroups, ny, nx), dtype=torch.complex128, device=plane.device)
+    norm = torch.empty((ngroups,), dtype=torch.float64, device=plane.device)
+    if stream is None:
+        stream = torch.cuda.current_stream(plane.device).cuda_stream
+    C.check(C.lib().rtpb_huygens_psf(plane.device.index or 0, C.RTPB_F64, plane.data_ptr(), group_size, ngroups,
+                                     refs.ctypes.data, win.ctypes.data,
+                                     None if weights is None else weights.data_ptr(), nx, ny, field.data_ptr(),
+                                     norm.data_ptr(), stream))
+    return field, norm
+
+
+def summarize_psf(field, norm, windows):
+    """The diffraction spot from the Huygens field (host, NumPy): ``field`` (..., ny, nx) complex, ``norm`` (...) and
+    ``windows`` (..., 4) or (1, 4).  Returns
+
+    - ``psf`` (..., ny, nx) = |E|^2 / norm^2: an aberration-free system has 1.0 at the reference point;
+    - ``x`` (..., nx) and ``y`` (..., ny), the pixels' offsets from the reference point, (i - c) * s;
+    - ``strehl``, the psf at the centre pixel -- the true Strehl ratio about the reference point, valid at any
+      aberration where the Marechal estimate of :func:`summarize_wavefront` is not -- NaN for a window without a
+      centre pixel (an even side, or a c that is no pixel index);
+    - ``peak`` and ``peak_offset`` (..., 2), the largest psf and the (x, y) where it lies: a tilt of the wavefront
+      moves the peak off the reference point;
+    - ``field``, ``norm`` and ``windows``.
+
+    A group without rays (norm 0) is NaN throughout."""
+    field = np.asarray(field)
+    norm = np.asarray(norm, dtype=np.float64)
+    ny, nx = field.shape[-2:]
+    lead = field.shape[:-2]
+    win = np.asarray(windows, dtype=np.float64)
+    win = np.broadcast_to(win.reshape(4) if win.shape == (1, 4) else win, lead + (4,))
+    with np.errstate(invalid="ignore", divide="ignore"):
+        psf = (field.real * field.real + field.imag * field.imag) / (norm * norm)[..., None, None]
+    x = (np.arange(nx, dtype=np.float64) - win[..., 0, None]) * win[..., 2, None]
+    y = (np.arange(ny, dtype=np.float64) - win[..., 1, None]) * win[..., 3, None]
+    cx, cy = win[..., 0], win[..., 1]
+    with np.errstate(invalid="ignore"):
+        has = (cx == np.floor(cx)) & (cy == np.floor(cy)) & (cx >= 0) & (cx < nx) & (cy >= 0) & (cy < ny)
+    ix = np.where(has, cx, 0).astype(np.int64)[..., None, None]
+    iy = np.where(has, cy, 0).astype(np.int64)[..., None, None]
+    centre = np.take_along_axis(np.take_along_axis(psf, iy, -2), ix, -1)[..., 0, 0]
+    flat = psf.reshape(lead + (ny * nx,))
+    dead = np.isnan(flat).any(axis=-1)
+    k = np.argmax(np.where(np.isnan(flat), -np.inf, flat), axis=-1)[..., None]
+    peak = np.where(dead, np.nan, np.take_along_axis(flat, k, -1)[..., 0])
+    off = np.stack((np.take_along_axis(x, k % nx, -1)[..., 0], np.take_along_axis(y, k // nx, -1)[..., 0]), -1)
+    return {"psf": psf, "x": x, "y": y, "strehl": np.where(has, centre, np.nan), "peak": peak,
+            "peak_offset": np.where(dead[..., None], np.nan, off), "field": field, "norm": norm, "windows": win}
+
+
+def psf_mtf(psf, sx, sy):
+    """The modulation transfer function of a PSF (host, NumPy): |FFT2(psf)| divided by its zero-frequency term, with
+    the zero frequency moved to the middle.  ``psf`` is (..., ny, nx) on pixels ``sx`` by ``sy`` apart (the windows'
+    s).  Returns (mtf (..., ny, nx), fx (nx,), fy (ny,)): the frequency axes in cycles per length unit, increasing,
+    ``np.fft.fftshift(np.fft.fftfreq(nx, sx))``; the DC term, 1.0, is at [ny // 2, nx // 2].
+
+    A pupil of numerical aperture NA passes nothing beyond the diffraction cutoff 2 NA / wavelength = 2 NA kf / n
+    (kf the references' n / wavelength): the pixels must be closer than half its period or the spectrum folds.  And
+    the window must hold the PSF's tails: an Airy pattern falls off only as r^-3, and what a window cuts off appears as
+    ripple and as a DC term that is too small, which lifts every other frequency.  Several Airy radii are the least
+    that means anything; the MTF of a NaN psf is NaN."""
+    psf = np.asarray(psf, dtype=np.float64)
+    ny, nx = psf.shape[-2:]
+    spec = np.abs(np.fft.fftshift(np.fft.fft2(psf), axes=(-2, -1)))
+    with np.errstate(invalid="ignore", divide="ignore"):
+        mtf = spec / spec[..., ny // 2, nx // 2][..., None, None]
+        fx = np.fft.fftshift(np.fft.fftfreq(nx, d=float(sx)))
+        fy = np.fft.fftshift(np.fft.fftfreq(ny, d=float(sy)))
+    return mtf, fx, fy
+
+
+def _psf_mode(refs, windows, nx, ny, weights):
+    """The Huygens PSF as the unfused driver sees it (:func:`_wave_mode`): :func:`huygens_psf_raw` on each batch's
+    final plane.  There is no fused entry point: the field is rays x pixels work on a plane that is read once.
+    ``refs`` is C-contiguous (n_fields, n_wavelengths, 8) and ``windows`` broadcasts to (n_fields, n_wavelengths, 4);
+    ``weights`` is None or (rays per group,) float64, uploaded once."""
+    ref = refs.reshape(-1, 8)
+    win = np.ascontiguousarray(np.broadcast_to(windows, refs.shape[:-1] + (4,))).reshape(-1, 4)
+    held = []
+
+    def plane(out, per, b0, nb):
+        if weights is not None and not held:
+            import torch
+            held.append(torch.from_numpy(weights).to(out.device))
+        return huygens_psf_raw(out, per, ref[b0:b0 + nb], win[b0:b0 + nb], nx, ny, held[0] if held else None)
+
+    return SimpleNamespace(
+        entry=None, ncols=None, plane=plane,
+        host=lambda G: (np.zeros((G, ny, nx), dtype=np.complex128), np.zeros(G)),
+        finish=lambda nf, nw, field, norm: summarize_psf(field.reshape(nf, nw, ny, nx), norm.reshape(nf, nw),
+                                                         win.reshape(nf, nw, 4)))
+
+
+def _psf_refuse(dtype, fused, devices):
+    """What the Huygens PSF calls refuse, before anything touches a device."""
+    if fused:
+        raise ValueError("the Huygens PSF has no fused variant: it runs generation -> trace -> rtpb_huygens_psf")
+    if devices is not None:
+        raise ValueError("the Huygens PSF runs on one device: devices= needs a fused sweep, and there is none")
+    if dtype not in ("float64", np.float64):
+        raise ValueError("the Huygens PSF is float64 only: a float32 phase of 1e4 ... 1e7 rad has an ulp of a "
+                         "milliradian to a radian")
+
+
+def _psf_weights(weights, area, per):
+    """(per,) float64 weights or None from ``weights``: "area" (``area()`` gives them), None, or an array."""
+    if weights is None:
+        return None
+    w = area() if isinstance(weights, str) and weights == "area" else weights
+    if isinstance(w, str):
+        raise ValueError('weights must be "area", None or an array of one weight per ray of a group')
+    w = np.ascontiguousarray(w, dtype=np.float64)
+    if w.shape != (per,):
+        raise ValueError(f"weights must have shape ({per},), one per ray of a group")
+    return w
+
+
+def _psf_sweep(system, initial_material, final_material, source, refs, half_width, n, weights, device,
+               groups_per_batch):
+    nx, ny = _psf_sides(n)
+    refs = _wave_refs(refs, (source.nf, source.nw, 8))
+    windows = psf_windows(half_width, nx, ny)
+    try:
+        np.broadcast_to(windows, refs.shape[:-1] + (4,))
+    except ValueError:
+        raise ValueError("half_width must be a scalar or shaped (n_fields, n_wavelengths)")
+    if groups_per_batch is None:
+        # the rays in flight as for the other unfused sweeps, and the batch's field (16 bytes a pixel) under 1 GiB
+        groups_per_batch = max(1, min(source.nf * source.nw, (1 << 27) // source.per, (1 << 30) // (nx * ny * 16)))
+    if not 1 <= groups_per_batch <= 65535:
+        raise ValueError("groups_per_batch must be in 1 ... 65535")
+    return _sweep(_psf_mode(refs, windows, nx, ny, weights), system, initial_material, final_material, source,
+                  device, "float64", int(groups_per_batch), False, None)
+
+
+def huygens_psf(system, initial_material, final_material, field_points, wavelengths, theta_max, n_thetas, nphis,
+                half_width, n=65, refs=None, weights="area", center_ray=(0, 0, 1), device="cuda:0",
+                groups_per_batch=None, dtype="float64", fused=False, devices=None):
+    """The DIFFRACTION spot for every (field point, wavelength): :func:`spot_sweep`'s fans, traced (final plane only),
+    and each group's Huygens field summed on ``n`` x ``n`` pixels reaching ``half_width`` (a scalar, or shaped
+    (n_fields, n_wavelengths)) about its reference point (fan generation -> trace planes='final' ->
+    ``rtpb_huygens_psf``).  Where the geometric sweeps say where rays land and :func:`wavefront_sweep` gives moments
+    of the wavefront, this is the spot a detector sees: its shape, the true Strehl ratio, and through
+    :func:`psf_mtf` the MTF.  Nothing is interpolated, and a vignetted pupil is just fewer rays.
+
+    ``refs`` (n_fields, n_wavelengths, 8) are :func:`wavefront_sweep`'s references, built as it builds them when
+    None (a :func:`spot_sweep` of the same fans for the centroids and one chief ray per group).  The PSF is taken
+    about each reference's C0 in the image plane; pass ``reference_best`` of a wavefront summary in C0's place for the
+    diffraction focus.  ``weights``: "area" (default) gives each ray the pupil area its sample stands for
+    (:func:`fan_area_weights`: the fans are dense on the axis), ``None`` weighs all rays alike, an array of
+    n_thetas * nphis doubles is used as given.  The pupil's sampling must resolve the window: rays ``dq`` apart in
+    kf e alias the spot with period 1 / dq.
+
+    Returns (:func:`summarize_psf` summary with arrays shaped (n_fields, n_wavelengths, ...), timing dict as
+    :func:`spot_sweep`'s unfused).  ``groups_per_batch`` bounds the rays and the field in flight (by default the
+    batch's field stays under 1 GiB); any value gives the same bits.  There is no fused variant and no multi-device
+    split: ``fused=True`` or ``devices=`` raises ``ValueError``, and so does a ``dtype`` other than float64."""
+    _psf_refuse(dtype, fused, devices)
+    field_points, wavelengths = _grid(field_points, wavelengths)
+    source = _fan_source(field_points, wavelengths, theta_max, n_thetas, nphis, center_ray)
+    weights = _psf_weights(weights, lambda: fan_area_weights(theta_max, n_thetas, nphis), source.per)
+    if refs is None:
+        refs = wavefront_refs(system, initial_material, final_material, field_points, wavelengths,
+                              center_ray=center_ray, device=device, theta_max=theta_max, n_thetas=n_thetas,
+                              nphis=nphis)
+    return _psf_sweep(system, initial_material, final_material, source, refs, half_width, n, weights, device,
+                      groups_per_batch)
+
+
+def collimated_huygens_psf(system, initial_material, final_material, normals, wavelengths, displacement_max, n_disps,
+                           nphis, half_width, n=65, phi_start=0., pt=(0, 0, 0), refs=None, weights="area",
+                           device="cuda:0", groups_per_batch=None, dtype="float64", fused=False, devices=None):
+    """The diffraction spot of :func:`collimated_spot_sweep`'s beams: :func:`huygens_psf` with that source
+    (``rtpb_collimated_rays_tables`` -> trace planes='final' -> ``rtpb_huygens_psf``).  With ``refs=None``
+    :func:`collimated_wavefront_refs` builds the references; ``weights="area"`` is :func:`beam_area_weights`."""
+    _psf_refuse(dtype, fused, devices)
+    source = _beam_source(normals, wavelengths, displacement_max, n_disps, nphis, phi_start, pt)
+    weights = _psf_weights(weights, lambda: beam_area_weights(displacement_max, n_disps, nphis), source.per)
+    if refs is None:
+        refs = collimated_wavefront_refs(system, initial_material, final_material, source.normals,
+                                         source.wavelengths, pt=source.pts, device=device,
+                                         displacement_max=displacement_max, n_disps=n_disps, nphis=nphis,
+                                         phi_start=phi_start)
+    return _psf_sweep(system, initial_material, final_material, source, refs, half_width, n, weights, device,
+                      groups_per_batch)
 
 
 FOOT_STAT_NAMES = ("arrive", "pass", "max_rho2_arrive", "max_rho2_pass", "min_u", "max_u", "min_v", "max_v")

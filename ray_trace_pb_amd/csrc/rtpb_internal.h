@@ -9,6 +9,7 @@
 //   rtpb_generators.hip    device ray fans and collimated bundles (RT:45-161)
 //   rtpb_analysis.hip      intersect_rays, the plane statistics (spot and focus), grid interpolation
 //   rtpb_image.hip         the spot image of a plane (binned ray counts per group)
+//   rtpb_psf.hip           the Huygens PSF of a plane (the coherent sum of the rays' wavelets per pixel)
 //   rtpb_sweep.hip         the fused spot / focus / image / wavefront sweeps of point-source fans, and
 //   rtpb_sweep_beam.hip    of collimated beams: two instantiation sets of rtpb_sweep_kernel.h (rtpb_stats.h: what
 //                          the sweep shares with the plane kernels; rtpb_sweep_host.h: its row planning, media table

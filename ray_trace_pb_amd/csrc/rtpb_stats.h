@@ -1,6 +1,6 @@
-// rtpb_stats.h -- what the plane kernels (rtpb_analysis.hip, rtpb_image.hip, rtpb_energy.hip) and the fused sweep
-// (rtpb_sweep.hip) share: the statistics sets, the one definition of a ray's contribution to the focus statistics, to
-// the wavefront statistics, to a spot image and to the energy curves, the footprint statistics' term (rtpb_foot.h, plain C++ so that the host can run it)
+// rtpb_stats.h -- what the plane kernels (rtpb_analysis.hip, rtpb_image.hip, rtpb_energy.hip, rtpb_psf.hip) and the
+// fused sweep (rtpb_sweep.hip) share: the statistics sets, the one definition of a ray's contribution to the focus
+// statistics, to the wavefront statistics, to the Huygens PSF, to a spot image and to the energy curves, the footprint statistics' term (rtpb_foot.h, plain C++ so that the host can run it)
 // and its wave and block reductions,
 // the wave's aggregated image adds, the reduction's argument block and its block-wide tree.  Everything here has
 // internal linkage, as it had inside the one unit: each unit's kernels take its own SpotArgs.
@@ -108,6 +108,32 @@ RTPB_HD double wave_term(const WaveRay& f, int k) {
     case 14: return f.ey * f.ez;
     default: return 0.0;
     }
+}
+
+// Huygens PSF (rtpb_huygens_psf): the field at the image-plane point C0 + (X, Y, 0) is the coherent sum of the rays'
+// plane wavelets, E = sum a exp(2 pi i (w + kf (ex X + ey Y))), with w and e wave_ray's OPD and direction offset
+// against the group's reference: nothing new is asked of a ray, and the counting rule is wave_ray's.  The one
+// definition of a ray's contribution, every operation one rounded IEEE operation in this order (no FMA):
+//   a = n * weight, qx = ex * kf, qy = ey * kf                     per ray (psf_ray; n is wave_ray's 1 or 0)
+//   t = (w + qx * X) + qy * Y,  fr = t - rint(t)                   per (ray, pixel) (psf_frac)
+// and the pixel adds a cospi(2 fr) and a sinpi(2 fr).  fr is exact (t and rint(t) are within a factor two of each
+// other, or t is below 1/2), |fr| <= 1/2, and removing whole waves before the sine keeps its argument small whatever
+// the OPD.  A ray that does not count adds nothing and is skipped, not multiplied by zero: its a is 0 * weight, NaN
+// for a NaN weight, and its t NaN in a NaN window.  A counting ray has a finite w, so psf_ray marks the others with a
+// NaN w (psf_counts) and the tile needs no fifth value.
+struct PsfRay {
+    double a, w, qx, qy;
+};
+RTPB_HD PsfRay psf_ray(double x, double y, double z, double dx, double dy, double dz, double ph,
+                       const double (&ref)[kWaveRef], double weight) {
+    const WaveRay f = wave_ray(x, y, z, dx, dy, dz, ph, ref);
+    if (f.n == 0.0) return PsfRay{0.0, __builtin_nan(""), 0.0, 0.0};
+    return PsfRay{f.n * weight, f.w, f.ex * ref[7], f.ey * ref[7]};
+}
+RTPB_HD bool psf_counts(const PsfRay& f) { return f.w == f.w; }
+RTPB_HD double psf_frac(const PsfRay& f, double X, double Y) {
+    const double t = (f.w + f.qx * X) + f.qy * Y;
+    return t - __builtin_rint(t);
 }
 
 // Spot images (rtpb_spot_image / rtpb_image_sweep): a 2-D histogram of the final positions per group, int32 counts,
