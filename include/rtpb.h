@@ -64,8 +64,9 @@ extern "C" {
                                     rtpb_footprint_sweep / rtpb_footprint_sweep_collimated (per-surface beam
                                     footprints and vignetting), then rtpb_spot_energy / rtpb_energy_sweep /
                                     rtpb_energy_sweep_collimated (encircled and ensquared energy), then
-                                    rtpb_huygens_psf (the diffraction PSF of a plane) joined within 10:
-                                    new symbols only, nothing existing changed */
+                                    rtpb_huygens_psf (the diffraction PSF of a plane), then rtpb_wavefront_map /
+                                    rtpb_wavefront_map_sweep / rtpb_wavefront_map_sweep_collimated (pupil OPD
+                                    maps) joined within 10: new symbols only, nothing existing changed */
 
 /* ---- error codes ---------------------------------------------------------------------------- */
 #define RTPB_OK 0
@@ -549,6 +550,59 @@ int rtpb_energy_sweep_collimated(const rtpb_plan* plan, int32_t device, int64_t 
                                  const double* group_frames, int64_t n_disps, int64_t nphis, const double* offsets,
                                  const double* phi_cos_sin, const double* params, int32_t nr, int32_t* hist_out,
                                  int32_t* outside_out, double* farthest_out, void* stream);
+
+/* WAVEFRONT MAP: per group, the optical path difference over the exit pupil -- the interferogram, and what Zernike
+   coefficients are fitted to on the host -- as a grid of nx x ny cells (each at most RTPB_MAX_IMAGE_SIDE) holding
+   INTEGERS: how many rays fell into the cell and the sum of their OPDs in units of 2^-q_bits waves.  Integer adds do
+   not depend on the order in which rays arrive, so the plane call, the fused sweeps and a host restatement agree bit
+   for bit.  A group's REFERENCE is the wavefront calls' eight doubles {C0, d0, p0, kf}.  A group's WINDOW is four
+   doubles {ex_lo, ey_lo, x_scale, y_scale} in the space of the direction offsets (ex, ey) = (dx - d0x, dy - d0y),
+   with rtpb_spot_image's semantics exactly.  A ray COUNTS exactly when it counts for rtpb_wavefront_stats; w, ex and
+   ey are that rule's values.  For a counting ray, every step one rounded IEEE operation in this order, no FMA:
+       far_e = max(|ex|, |ey|);  far_w = |w|            (both enter farthest[g], whatever the window and w_lim say)
+       tx = (ex - ex_lo) * x_scale;  ty = (ey - ey_lo) * y_scale
+       INSIDE iff 0 <= tx < nx and 0 <= ty < ny (compared in floating point: a NaN or infinite window is outside);
+           a ray that is not inside adds 1 to outside[g] and goes no further
+       a ray that is inside and fails |w| <= w_lim adds 1 to clipped[g] (a failed comparison: a NaN never passes)
+       otherwise tq = w * 2^q_bits (exact), q = (int64) rint(tq) (to nearest, ties to even), and with
+           b = (int)ty * nx + (int)tx:  count[g][b] += 1 (int32),  sum[g][b] += q (int64)
+   Two bounds follow: count[g].sum() + outside[g] + clipped[g] is the group's wavefront count n, exactly; and a cell's
+   mean OPD sum / 2^q_bits / count is within 2^-(q_bits + 1) waves of the true mean of its rays.  farthest[g] =
+   {max far_e, max far_w} over the counting rays (0.0 for a group with none; a NaN reference counts none): measured
+   from the chief ray (e = 0), not from the window, so a call with any window -- a 1 x 1 map, say -- tells the caller
+   which window and w_lim hold everything.  Unsigned 64-bit atomic maxima on the bit patterns, as rtpb_spot_energy's.
+   The calls refuse what could overflow before a device is touched: RTPB_E_INVALID unless 0 <= q_bits <= 52 and w_lim
+   is finite and >= 0; RTPB_E_LIMIT for more than 2^31 - 1 rays per group, and unless
+       ldexp(w_lim, q_bits) + 1 <= ldexp(1.0, 62) / rays per group
+   which keeps every cell's sum inside int64 by a factor of two (that covers the rounding of the check itself).
+   count_out (device, n_groups*ny*nx int32), sum_out (device, n_groups*ny*nx int64), outside_out and clipped_out
+   (device, n_groups int32), farthest_out (device, n_groups*2 doubles): each call zeroes its n_groups slices on
+   `stream` before counting; no workspace.  float64 ONLY, for rtpb_wavefront_stats' reason.
+   rtpb_wavefront_map: one (N, 8) AOS float64 plane split into groups as for rtpb_wavefront_stats; refs (n_groups x 8)
+   and windows (n_groups x 4) are HOST pointers, uploaded by the call. */
+int rtpb_wavefront_map(int32_t device, int32_t dtype, const void* plane, int64_t group_size, int64_t n_groups,
+                       const double* refs, const double* windows, int32_t nx, int32_t ny, int32_t q_bits,
+                       double w_lim, int32_t* count_out, int64_t* sum_out, int32_t* outside_out, int32_t* clipped_out,
+                       double* farthest_out, void* stream);
+
+/* Fused wavefront map sweeps: rtpb_wavefront_sweep / rtpb_wavefront_sweep_collimated with each counted ray added to
+   its group's map instead of the fifteen moments -- the same arguments up to the references, the same surface steps
+   (the phase is the one rtpb_trace stores), float64 plans only, every group a single row; no workspace.  refs and
+   windows: HOST (they ride in the sweep's one upload).  The results are identical to generating, tracing (final
+   plane) and rtpb_wavefront_map. */
+int rtpb_wavefront_map_sweep(const rtpb_plan* plan, int32_t device, int64_t n_groups, const double* group_params,
+                             int64_t n_thetas, int64_t nphis, const double center_ray[3], const double ex[3],
+                             const double ey[3], const double* theta_cos_sin, const double* phi_cos_sin,
+                             const double* refs, const double* windows, int32_t nx, int32_t ny, int32_t q_bits,
+                             double w_lim, int32_t* count_out, int64_t* sum_out, int32_t* outside_out,
+                             int32_t* clipped_out, double* farthest_out, void* stream);
+int rtpb_wavefront_map_sweep_collimated(const rtpb_plan* plan, int32_t device, int64_t n_groups,
+                                        const double* group_params, const double* group_frames, int64_t n_disps,
+                                        int64_t nphis, const double* offsets, const double* phi_cos_sin,
+                                        const double* refs, const double* windows, int32_t nx, int32_t ny,
+                                        int32_t q_bits, double w_lim, int32_t* count_out, int64_t* sum_out,
+                                        int32_t* outside_out, int32_t* clipped_out, double* farthest_out,
+                                        void* stream);
 
 /* HUYGENS PSF: per group, the complex field on a grid of image-plane pixels as the coherent sum of the rays' plane
    wavelets -- the diffraction spot itself, from which the true Strehl ratio and the MTF follow on the host.  No

@@ -153,6 +153,13 @@ SIGNATURES = {
                                                     _P]),
     # (the wavefront plane call's head; refs and windows on the host, weights on the device, the sides, two outputs)
     "rtpb_huygens_psf": (ctypes.c_int, [_i32, _i32, _P, _i64, _i64, _P, _P, _P, _i32, _i32, _P, _P, _P]),
+    # (refs, windows, nx, ny, q_bits, w_lim, then the five outputs and the stream)
+    "rtpb_wavefront_map": (ctypes.c_int, [_i32, _i32, _P, _i64, _i64, _P, _P, _i32, _i32, _i32, _dbl, _P, _P, _P, _P,
+                                          _P, _P]),
+    "rtpb_wavefront_map_sweep": (ctypes.c_int, [_P, _i32, _i64, _P, _i64, _i64, _P, _P, _P, _P, _P, _P, _P, _i32, _i32,
+                                                _i32, _dbl, _P, _P, _P, _P, _P, _P]),
+    "rtpb_wavefront_map_sweep_collimated": (ctypes.c_int, [_P, _i32, _i64, _P, _P, _i64, _i64, _P, _P, _P, _P, _i32,
+                                                           _i32, _i32, _dbl, _P, _P, _P, _P, _P, _P]),
     "rtpb_set_tuning":(ctypes.c_int, [ctypes.c_char_p, _i64]),
     "rtpb_timing_enable": (ctypes.c_int, [_i32]),
     "rtpb_timing_collect": (ctypes.c_int, [ctypes.POINTER(_dbl), ctypes.POINTER(_i64)]),

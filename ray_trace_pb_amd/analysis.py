@@ -20,6 +20,10 @@ curves of every group (``rtpb_energy_sweep[_collimated]``; ``rtpb_spot_energy`` 
 :func:`energy_radius` reads EE50 / EE80.  :func:`huygens_psf` and :func:`collimated_huygens_psf` give the diffraction spot
 itself -- each group's field as the coherent sum of its rays' wavelets on a grid of image-plane pixels
 (``rtpb_huygens_psf`` on the traced final plane), hence the true Strehl ratio and, through :func:`psf_mtf`, the MTF.
+:func:`wavefront_map_sweep` and :func:`collimated_wavefront_map_sweep` give the wavefront itself -- each group's map
+of optical path difference over the exit pupil, made of integers in the same fused pass
+(``rtpb_wavefront_map_sweep[_collimated]``; ``rtpb_wavefront_map`` for a stored plane) -- and :func:`zernike_fit` the
+Zernike coefficients fitted to it.
 """
 import contextlib
 import copy
@@ -1082,6 +1086,308 @@ def collimated_wavefront_sweep(system, initial_material, final_material, normals
     refs = _wave_refs(refs, (source.nf, source.nw, 8))
     return _sweep(_wave_mode(refs), system, initial_material, final_material, source, device, "float64",
                   groups_per_batch, fused, devices)
+
+
+def wavefront_map_windows(far_e, bins):
+    """The pupil windows (..., 4) = {ex_lo, ey_lo, x_scale, y_scale} the map sweeps choose from a first pass's
+    ``farthest[..., 0]`` (the largest max(|ex|, |ey|) of a group's counting rays): centred on the chief ray, e = 0,
+    with a half-width of ``far_e * (1 + 2^-20)`` -- just large enough that the farthest ray falls inside the last
+    cell -- or 1.0 where ``far_e`` is not a positive finite number (an empty group)."""
+    far = np.asarray(far_e, dtype=np.float64)
+    with np.errstate(invalid="ignore"):
+        half = np.where(np.isfinite(far) & (far > 0), far * (1.0 + 2.0 ** -20), 1.0)
+    return image_windows(np.zeros(far.shape + (2,)), half, bins)
+
+
+def wavefront_map_q_bits(group_size, w_lim):
+    """The ``q_bits`` the map sweeps choose: min(40, floor(62 - log2(group_size * w_lim))), lowered until the calls'
+    own bound holds (ldexp(w_lim, q_bits) + 1 <= 2^62 / group_size: no cell's sum can leave int64).  At 40 bits a
+    cell's mean is within 2^-41 waves of the true mean of its rays."""
+    w_lim = float(w_lim)
+    if not (np.isfinite(w_lim) and w_lim >= 0):
+        raise ValueError("w_lim must be finite and >= 0")
+    q = 40
+    if group_size * w_lim > 0:
+        q = min(40, int(np.floor(62 - np.log2(group_size * w_lim))))
+    while q >= 0 and not np.ldexp(w_lim, q) + 1.0 <= np.ldexp(1.0, 62) / group_size:
+        q -= 1
+    if q < 0:
+        raise ValueError("w_lim * group_size is too large for an int64 cell sum")
+    return q
+
+
+def wavefront_map_raw(plane, group_size, refs, windows, bins, q_bits, w_lim, stream=None):
+    """The wavefront map of a torch CUDA (N, 8) float64 plane, N = n_groups * group_size (``rtpb_wavefront_map``):
+    per group the optical path difference over the pupil window, as integers.  ``refs`` (n_groups, 8) as
+    :func:`wavefront_refs` gives them, ``windows`` (n_groups, 4) = {ex_lo, ey_lo, x_scale, y_scale} in the space of
+    the direction offsets e = d - d0 (:func:`image_windows`' layout), host values; ``bins`` an int or (nx, ny).
+    Returns (count (n_groups, ny, nx) int32, sum (n_groups, ny, nx) int64, outside (n_groups,) int32, clipped
+    (n_groups,) int32, farthest (n_groups, 2) float64), torch: a ray that counts for the wavefront statistics lands
+    in exactly one cell -- where ``sum`` gains rint(w * 2^q_bits), w its OPD in waves -- or in ``outside`` (not in
+    the window) or in ``clipped`` (inside, |w| > w_lim); ``farthest`` is the largest max(|ex|, |ey|) and the largest
+    |w| over all of them.  float64 only."""
+    import torch
+    if plane.dtype != torch.float64:
+        raise ValueError("wavefront maps need a float64 plane: a float32 phase of 1e4 ... 1e7 rad has an ulp of a "
+                         "milliradian to a radian")
+    nx, ny = _bins(bins)
+    n = plane.shape[0]
+    if n % group_size:
+        raise ValueError("plane length must be a multiple of group_size")
+    ngroups = n // group_size
+    refs = _wave_refs(refs, (ngroups, 8))
+    windows = np.ascontiguousarray(windows, dtype=np.float64)
+    if windows.shape != (ngroups, 4):
+        raise ValueError("windows must have shape (n_groups, 4)")
+    plane = plane.contiguous()
+    dev = plane.device
+    count = torch.empty((ngroups, ny, nx), dtype=torch.int32, device=dev)
+    total = torch.empty((ngroups, ny, nx), dtype=torch.int64, device=dev)
+    outside = torch.empty((ngroups,), dtype=torch.int32, device=dev)
+    clipped = torch.empty((ngroups,), dtype=torch.int32, device=dev)
+    farthest = torch.empty((ngroups, 2), dtype=torch.float64, device=dev)
+    if stream is None:
+        stream = torch.cuda.current_stream(dev).cuda_stream
+    C.check(C.lib().rtpb_wavefront_map(dev.index or 0, C.RTPB_F64, plane.data_ptr(), group_size, ngroups,
+                                       refs.ctypes.data, windows.ctypes.data, nx, ny, int(q_bits), float(w_lim),
+                                       count.data_ptr(), total.data_ptr(), outside.data_ptr(), clipped.data_ptr(),
+                                       farthest.data_ptr(), stream))
+    return count, total, outside, clipped, farthest
+
+
+def summarize_wavefront_map(count, sum, outside, clipped, farthest, windows, q_bits):
+    """The OPD map from the raw integers (host, NumPy): ``count`` and ``sum`` (..., ny, nx), ``outside`` and
+    ``clipped`` (...), ``farthest`` (..., 2), ``windows`` (..., 4).  Returns
+
+    - ``opd`` (..., ny, nx): sum / 2^q_bits / count, each cell's mean OPD in waves, NaN where ``count == 0``;
+    - ``count``, ``sum``, ``outside``, ``clipped`` and ``total`` = count.sum + outside + clipped, the group's wavefront
+      count (int64);
+    - ``ex_edges`` (..., nx + 1) / ``ey_edges`` (..., ny + 1), the cells' edges lo + i / scale in direction-offset
+      space, and ``ex_centers`` (..., nx) / ``ey_centers`` (..., ny);
+    - ``mean_opd``, the count-weighted mean: the mean over the rays in the map, within ``resolution`` of their true
+      mean;
+    - ``rms_opd_cells`` and ``pv_opd``: the standard deviation and the peak-to-valley of ``opd`` over the occupied
+      cells, every cell weighing the same;
+    - ``farthest``, ``windows``, ``q_bits`` and ``resolution`` = 2^-(q_bits + 1) waves, the bound on a cell's error.
+
+    A group with no ray in its map (a NaN reference counts none) has NaN for every float."""
+    count = np.asarray(count)
+    total_q = np.asarray(sum).astype(np.int64)
+    outside = np.asarray(outside).astype(np.int64)
+    clipped = np.asarray(clipped).astype(np.int64)
+    windows = np.asarray(windows, dtype=np.float64)
+    ny, nx = count.shape[-2:]
+    scale = 2.0 ** int(q_bits)
+    inside = count.sum(axis=(-2, -1), dtype=np.int64)
+    occupied = count > 0
+    xe, ye = image_edges(windows, (nx, ny))
+    with np.errstate(divide="ignore", invalid="ignore"):
+        opd = np.where(occupied, total_q / scale / count, np.nan)
+        mean = total_q.sum(axis=(-2, -1), dtype=np.int64) / scale / inside
+        cells = occupied.sum(axis=(-2, -1))
+        cell_mean = np.where(occupied, opd, 0.0).sum(axis=(-2, -1)) / cells
+        dev = np.where(occupied, opd - cell_mean[..., None, None], 0.0)
+        rms = np.sqrt((dev * dev).sum(axis=(-2, -1)) / cells)
+        pv = np.where(cells > 0, np.where(occupied, opd, -np.inf).max(axis=(-2, -1)) -
+                      np.where(occupied, opd, np.inf).min(axis=(-2, -1)), np.nan)
+    return {"opd": opd, "count": count, "sum": total_q, "outside": outside, "clipped": clipped,
+            "total": inside + outside + clipped, "ex_edges": xe, "ey_edges": ye,
+            "ex_centers": 0.5 * (xe[..., :-1] + xe[..., 1:]), "ey_centers": 0.5 * (ye[..., :-1] + ye[..., 1:]),
+            "mean_opd": mean, "rms_opd_cells": rms, "pv_opd": pv,
+            "farthest": np.asarray(farthest, dtype=np.float64), "windows": windows, "q_bits": int(q_bits),
+            "resolution": 2.0 ** -(int(q_bits) + 1)}
+
+
+def _noll(j):
+    """(n, m) of Noll's j-th Zernike term, j >= 1; m > 0 is the cosine term, m < 0 the sine term."""
+    n, k = 0, j - 1
+    while k > n:
+        n += 1
+        k -= n
+    m = (n % 2) + 2 * ((k + (n + 1) % 2) // 2)
+    return n, m if j % 2 == 0 else -m
+
+
+def zernike_basis(n_terms, x, y):
+    """The first ``n_terms`` Zernike polynomials in Noll's order at the points (x, y) of the unit disc, shaped
+    (n_terms,) + x.shape.  Orthonormal on the unit disc -- the mean of Z_j Z_k over it is 1 for j = k and 0 otherwise
+    -- so a fitted coefficient is that term's RMS contribution, in the map's unit (waves).  Z1 piston, Z2 / Z3 tilt,
+    Z4 defocus, Z5 / Z6 astigmatism, Z7 / Z8 coma, Z9 / Z10 trefoil, Z11 spherical aberration."""
+    from math import factorial
+    x, y = np.broadcast_arrays(np.asarray(x, dtype=np.float64), np.asarray(y, dtype=np.float64))
+    rho, phi = np.hypot(x, y), np.arctan2(y, x)
+    out = np.empty((int(n_terms),) + x.shape)
+    for j in range(1, int(n_terms) + 1):
+        n, m = _noll(j)
+        a = abs(m)
+        radial = np.zeros_like(rho)
+        for k in range((n - a) // 2 + 1):
+            c = (-1) ** k * factorial(n - k) // (factorial(k) * factorial((n + a) // 2 - k) *
+                                                 factorial((n - a) // 2 - k))
+            radial = radial + c * rho ** (n - 2 * k)
+        if m == 0:
+            out[j - 1] = np.sqrt(n + 1.0) * radial
+        else:
+            out[j - 1] = np.sqrt(2.0 * (n + 1.0)) * radial * (np.cos(a * phi) if m > 0 else np.sin(a * phi))
+    return out
+
+
+def zernike_fit(summary, n_terms=15, radius=None, center=(0, 0)):
+    """Zernike coefficients of the maps of a :func:`summarize_wavefront_map` summary: per group, an UNWEIGHTED
+    least-squares fit of :func:`zernike_basis` to ``opd`` over the occupied cells whose centres lie in the disc of
+    ``radius`` about ``center`` in direction-offset space, scaled to the unit disc.  ``radius`` defaults to the
+    group's ``farthest[..., 0]`` and may be a scalar or shaped as the groups.
+
+    Unweighted on purpose: a fan samples ``theta`` uniformly, so its rays crowd the centre of the pupil, and a fit
+    weighted by rays -- or moments summed over rays -- would describe the wavefront mostly where it is flattest.  A
+    cell's mean removes that density: every occupied cell is one sample of the wavefront at its place in the pupil.
+
+    Returns ``coefficients`` (..., n_terms) in waves, ``residual_rms`` (the RMS over the used cells of what the fit
+    leaves), ``cells`` (the number of cells used) and ``cond`` (the design matrix's condition number: near 1 when the
+    cells cover the disc evenly).  A group with fewer used cells than terms has NaN for all three floats."""
+    opd = np.asarray(summary["opd"])
+    lead = opd.shape[:-2]
+    ny, nx = opd.shape[-2:]
+    G = int(np.prod(lead, dtype=np.int64))
+    opd = opd.reshape(G, ny, nx)
+    xc = np.asarray(summary["ex_centers"]).reshape(G, nx)
+    yc = np.asarray(summary["ey_centers"]).reshape(G, ny)
+    rad = np.asarray(summary["farthest"])[..., 0] if radius is None else np.asarray(radius, dtype=np.float64)
+    rad = np.broadcast_to(rad, lead).reshape(G)
+    coef = np.full((G, int(n_terms)), np.nan)
+    res, cond = np.full(G, np.nan), np.full(G, np.nan)
+    cells = np.zeros(G, dtype=np.int64)
+    for g in range(G):
+        with np.errstate(divide="ignore", invalid="ignore"):
+            u = (xc[g][None, :] - center[0]) / rad[g]
+            v = (yc[g][:, None] - center[1]) / rad[g]
+            used = np.isfinite(opd[g]) & (u * u + v * v <= 1.0)
+        cells[g] = used.sum()
+        if cells[g] < n_terms or cells[g] == 0:
+            continue
+        uu, vv = np.broadcast_arrays(u, v)
+        A = zernike_basis(n_terms, uu[used], vv[used]).T
+        coef[g] = np.linalg.lstsq(A, opd[g][used], rcond=None)[0]
+        r = opd[g][used] - A @ coef[g]
+        res[g] = np.sqrt((r * r).mean())
+        cond[g] = np.linalg.cond(A)
+    return {"coefficients": coef.reshape(lead + (int(n_terms),)), "residual_rms": res.reshape(lead),
+            "cells": cells.reshape(lead), "cond": cond.reshape(lead)}
+
+
+def _wavemap_mode(refs, windows, nx, ny, q_bits, w_lim):
+    """The wavefront map sweep as the drivers see it: :func:`_image_mode` with :func:`_wave_mode`'s references --
+    ``rtpb_wavefront_map_sweep`` fused, ``wavefront_map_raw`` per plane, no workspace; per device the shard's five
+    outputs.  ``refs`` (n_fields, n_wavelengths, 8) and ``windows`` (n_fields, n_wavelengths, 4) are C-contiguous
+    float64, so those of groups [b0, b1) are contiguous in them."""
+    ref, win = refs.reshape(-1, 8), windows.reshape(-1, 4)
+
+    def shard(dev, per, g0, n, batch):
+        import torch
+        count = torch.empty((n, ny, nx), dtype=torch.int32, device=dev)
+        total = torch.empty((n, ny, nx), dtype=torch.int64, device=dev)
+        outside = torch.empty((n,), dtype=torch.int32, device=dev)
+        clipped = torch.empty((n,), dtype=torch.int32, device=dev)
+        farthest = torch.empty((n, 2), dtype=torch.float64, device=dev)
+        outputs = (count, total, outside, clipped, farthest)
+        return outputs, lambda b0, b1: (ref[b0:b1].ctypes.data, win[b0:b1].ctypes.data, nx, ny, q_bits, w_lim) + \
+            tuple(t[b0 - g0:b1 - g0].data_ptr() for t in outputs)
+
+    def finish(nf, nw, count, total, outside, clipped, farthest):
+        out = summarize_wavefront_map(count.reshape(nf, nw, ny, nx), total.reshape(nf, nw, ny, nx),
+                                      outside.reshape(nf, nw), clipped.reshape(nf, nw), farthest.reshape(nf, nw, 2),
+                                      windows, q_bits)
+        out["refs"], out["w_lim"] = refs, w_lim
+        return out
+
+    return SimpleNamespace(
+        entry="rtpb_wavefront_map_sweep", ncols=None, shard=shard, finish=finish,
+        # the cells, counters and maxima, cleared and then added to (the rays never leave the registers)
+        hbm_bytes=lambda per, n: n * (ny * nx * 12 + 2 * 4 + 2 * 8) * 2,
+        host=lambda G: (np.zeros((G, ny, nx), dtype=np.int32), np.zeros((G, ny, nx), dtype=np.int64),
+                        np.zeros(G, dtype=np.int32), np.zeros(G, dtype=np.int32), np.zeros((G, 2))),
+        plane=lambda out, per, b0, nb: wavefront_map_raw(out, per, ref[b0:b0 + nb], win[b0:b0 + nb], (nx, ny), q_bits,
+                                                         w_lim))
+
+
+def _wavemap_sweep(system, initial_material, final_material, source, refs, bins, windows, w_lim, q_bits, device,
+                   groups_per_batch, fused, devices, dtype):
+    """What the two map sweeps share once the source and the references exist: the first pass for the defaults, the
+    choice of q_bits, the sweep."""
+    if dtype not in ("float64", np.float64):
+        raise ValueError("wavefront_map_sweep is float64 only: a float32 phase of 1e4 ... 1e7 rad has an ulp of a "
+                         "milliradian to a radian")
+    nx, ny = _bins(bins)
+    shape = (source.nf, source.nw)
+    refs = _wave_refs(refs, shape + (8,))
+    run = lambda mode: _sweep(mode, system, initial_material, final_material, source, device, "float64",  # noqa: E731
+                              groups_per_batch, fused, devices)
+    if windows is None or w_lim is None:
+        # a 1 x 1 map whose limit clips everything: only its two maxima are read
+        unit = np.ascontiguousarray(np.broadcast_to(np.array([-1.0, -1.0, 0.5, 0.5]), shape + (4,)))
+        first, _ = run(_wavemap_mode(refs, unit, 1, 1, 0, 0.0))
+        if windows is None:
+            windows = wavefront_map_windows(first["farthest"][..., 0], (nx, ny))
+        if w_lim is None:
+            w_lim = max(1.0, float(first["farthest"][..., 1].max()))
+    windows = np.ascontiguousarray(windows, dtype=np.float64)
+    if windows.shape != shape + (4,):
+        raise ValueError("windows must have shape (n_fields, n_wavelengths, 4)")
+    w_lim = float(w_lim)
+    if q_bits is None:
+        q_bits = wavefront_map_q_bits(source.per, w_lim)
+    return run(_wavemap_mode(refs, windows, nx, ny, int(q_bits), w_lim))
+
+
+def wavefront_map_sweep(system, initial_material, final_material, field_points, wavelengths, theta_max, n_thetas,
+                        nphis=1, center_ray=(0, 0, 1), device="cuda:0", bins=33, refs=None, windows=None, w_lim=None,
+                        q_bits=None, fused=True, devices=None, groups_per_batch=None, dtype="float64"):
+    """Wavefront MAPS for every (field point, wavelength): :func:`wavefront_sweep`'s fans and surface steps, each
+    counted ray's OPD added to the cell of the group's pupil window that its direction offset e = d - d0 falls into,
+    in the same pass (``rtpb_wavefront_map_sweep``; with ``fused=False`` fan generation -> trace planes='final' ->
+    ``rtpb_wavefront_map``).  The map is made of integers -- per cell the rays' count and the sum of
+    rint(w * 2^q_bits) -- so fused, unfused and repeated calls give identical arrays, at sizes whose final plane
+    could not be stored.
+
+    ``refs`` (n_fields, n_wavelengths, 8) as for :func:`wavefront_sweep`; with ``refs=None`` :func:`wavefront_refs`
+    builds them, which traces the rays once.  ``windows`` (n_fields, n_wavelengths, 4), as :func:`image_windows` lays
+    them out, say which part of direction-offset space each map covers, and a ray whose |OPD| exceeds ``w_lim`` waves
+    is counted in ``clipped`` instead of a cell.  With ``windows=None`` or ``w_lim=None`` a first pass with a 1 x 1
+    map runs only for its ``farthest``: each window is then centred on the chief ray and just holds the group's
+    farthest ray (:func:`wavefront_map_windows`), and ``w_lim`` is the largest |OPD| of any group, at least 1 -- so
+    the rays are traced twice, and ``outside`` and ``clipped`` come out 0.  ``q_bits=None`` picks
+    :func:`wavefront_map_q_bits`.  ``bins`` is an int or (nx, ny); ``devices`` and ``groups_per_batch`` as for
+    :func:`spot_sweep`.  float64 only.
+
+    Returns (summary, timing): :func:`summarize_wavefront_map`'s dict with arrays shaped (n_fields, n_wavelengths,
+    ...), plus ``refs`` and ``w_lim``; :func:`zernike_fit` fits Zernike coefficients to it.  The timing dict has
+    :func:`spot_sweep`'s shape and covers the map pass alone."""
+    field_points, wavelengths = _grid(field_points, wavelengths)
+    if refs is None:
+        refs = wavefront_refs(system, initial_material, final_material, field_points, wavelengths,
+                              center_ray=center_ray, device=device, theta_max=theta_max, n_thetas=n_thetas,
+                              nphis=nphis, groups_per_batch=groups_per_batch, devices=devices)
+    return _wavemap_sweep(system, initial_material, final_material,
+                          _fan_source(field_points, wavelengths, theta_max, n_thetas, nphis, center_ray), refs, bins,
+                          windows, w_lim, q_bits, device, groups_per_batch, fused, devices, dtype)
+
+
+def collimated_wavefront_map_sweep(system, initial_material, final_material, normals, wavelengths, displacement_max,
+                                   n_disps, nphis=1, phi_start=0., pt=(0, 0, 0), device="cuda:0", bins=33, refs=None,
+                                   windows=None, w_lim=None, q_bits=None, fused=True, devices=None,
+                                   groups_per_batch=None, dtype="float64"):
+    """Wavefront maps of :func:`collimated_spot_sweep`'s beams: :func:`wavefront_map_sweep` with that source
+    (``rtpb_wavefront_map_sweep_collimated``, or unfused through ``rtpb_wavefront_map``; identical arrays).  With
+    ``refs=None`` :func:`collimated_wavefront_refs` builds the references; with ``windows=None`` or ``w_lim=None`` a
+    first pass chooses them, so the rays are traced twice."""
+    source = _beam_source(normals, wavelengths, displacement_max, n_disps, nphis, phi_start, pt)
+    if refs is None:
+        refs = collimated_wavefront_refs(system, initial_material, final_material, source.normals,
+                                         source.wavelengths, pt=source.pts, device=device,
+                                         displacement_max=displacement_max, n_disps=n_disps, nphis=nphis,
+                                         phi_start=phi_start, groups_per_batch=groups_per_batch, devices=devices)
+    return _wavemap_sweep(system, initial_material, final_material, source, refs, bins, windows, w_lim, q_bits, device,
+                          groups_per_batch, fused, devices, dtype)
 
 
 def _psf_sides(n, ny=None):

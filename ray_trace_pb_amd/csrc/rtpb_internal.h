@@ -478,6 +478,15 @@ int energy_check(const char* call, int32_t nr, int64_t group_size, int64_t n_gro
 int energy_clear(int32_t* hist_out, int32_t* outside_out, double* farthest_out, int64_t n_groups, int32_t nr,
                  hipStream_t st);
 
+// The same for the wavefront-map calls (rtpb_wavemap.hip; "wavefront-map", "wavefront-map-sweep"): the sides, q_bits
+// and w_lim -- with the bound that keeps a cell's sum inside int64 (rtpb_wavemap.h wavemap_bound) -- and the five
+// outputs.
+int wavemap_check(const char* call, int32_t nx, int32_t ny, int32_t q_bits, double w_lim, int64_t group_size,
+                  int64_t n_groups, const void* refs, const void* windows, const void* count_out, const void* sum_out,
+                  const void* outside_out, const void* clipped_out, const void* farthest_out);
+int wavemap_clear(int32_t* count_out, long long* sum_out, int32_t* outside_out, int32_t* clipped_out,
+                  double* farthest_out, int64_t n_groups, int32_t nx, int32_t ny, hipStream_t st);
+
 }  // namespace rtpbi
 
 // ---------------------------------------------------------------------------------- plans

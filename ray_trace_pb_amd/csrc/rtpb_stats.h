@@ -1,7 +1,8 @@
-// rtpb_stats.h -- what the plane kernels (rtpb_analysis.hip, rtpb_image.hip, rtpb_energy.hip, rtpb_psf.hip) and the
-// fused sweep (rtpb_sweep.hip) share: the statistics sets, the one definition of a ray's contribution to the focus
-// statistics, to the wavefront statistics, to the Huygens PSF, to a spot image and to the energy curves, the footprint statistics' term (rtpb_foot.h, plain C++ so that the host can run it)
-// and its wave and block reductions,
+// rtpb_stats.h -- what the plane kernels (rtpb_analysis.hip, rtpb_image.hip, rtpb_energy.hip, rtpb_psf.hip,
+// rtpb_wavemap.hip) and the fused sweep (rtpb_sweep.hip) share: the statistics sets, the one definition of a ray's
+// contribution to the focus statistics, to the wavefront statistics, to the Huygens PSF, to a spot image and to the
+// energy curves, the footprint statistics' term (rtpb_foot.h, plain C++ so that the host can run it) and its wave and
+// block reductions, the wavefront map's rule (rtpb_wavemap.h, plain C++ likewise) and its wave-level adds,
 // the wave's aggregated image adds, the reduction's argument block and its block-wide tree.  Everything here has
 // internal linkage, as it had inside the one unit: each unit's kernels take its own SpotArgs.
 #pragma once
@@ -9,6 +10,7 @@
 #include "rtpb_internal.h"
 
 #include "rtpb_foot.h"
+#include "rtpb_wavemap.h"
 
 namespace {
 
@@ -58,37 +60,16 @@ RTPB_HD double focus_term(const FocusRay& f, int k) {
     }
 }
 
-// Wavefront statistics (rtpb_wavefront_stats / rtpb_wavefront_sweep): the moments of the optical path difference.
-// A group's reference is kWaveRef doubles (C0x, C0y, C0z, d0x, d0y, d0z, p0, kf): the reference point, the pivot
-// direction and the pivot phase (radians) of the group's chief ray, and kf = n_final / wavelength.  The optical path
-// of a ray to the foot of the perpendicular from C0 is linear in C0, so the variance of the OPD about a displaced
-// reference C0 + delta is an exact quadratic in delta whose coefficients are the first and second moments of
-// (w, e) below (analysis.summarize_wavefront).  The pivots are subtracted per ray before anything is squared: the
-// phase is 1e4 ... 1e7 rad and the OPD a fraction of a wave, and un-pivoted sums cancel to a few per cent.
-// The one definition of a ray's contribution, for the plane kernel and the fused sweep alike, float64 only, every
-// operation one rounded IEEE operation in this order (no FMA):
-//   ex = dx - d0x, ey = dy - d0y, ez = dz - d0z
-//   s  = ((C0x - x) * dx + (C0y - y) * dy) + (C0z - z) * dz
-//   w  = (ph - p0) * kInv2Pi + s * kf                              (the OPD in waves)
-// A ray counts when x and y are finite (the spot statistics' rule) and w, ex, ey and ez are all finite.  wave_ray
-// gives the counted ray as (n, w, ex, ey, ez) with n = 1, or all +0 for a ray that does not count, and wave_term
-// its k-th statistic, each product one rounded multiply: n, w, w w, ex, ey, ez, w ex, w ey, w ez, ex ex, ey ey,
-// ez ez, ex ey, ex ez, ey ez (k past the set: +0, the padding of the last chunk of eight).
+// Wavefront statistics (rtpb_wavefront_stats / rtpb_wavefront_sweep): the moments of the optical path difference
+// against the group's reference.  The one definition of a ray's contribution is wave_ray (rtpb_wavemap.h, plain C++
+// so that the host can run it): the counted ray as (n, w, ex, ey, ez) with n = 1, or all +0 for a ray that does not
+// count.  wave_term is its k-th statistic, each product one rounded multiply: n, w, w w, ex, ey, ez, w ex, w ey, w ez,
+// ex ex, ey ey, ez ez, ex ey, ex ez, ey ez (k past the set: +0, the padding of the last chunk of eight).
 constexpr int kWaveStats = 15;
-constexpr int kWaveRef = 8;
-constexpr double kInv2Pi = 0.15915494309189535;
-struct WaveRay {
-    double n, w, ex, ey, ez;
-};
-RTPB_HD WaveRay wave_ray(double x, double y, double z, double dx, double dy, double dz, double ph,
-                         const double (&ref)[kWaveRef]) {
-    const double ex = dx - ref[3], ey = dy - ref[4], ez = dz - ref[5];
-    const double s = ((ref[0] - x) * dx + (ref[1] - y) * dy) + (ref[2] - z) * dz;
-    const double w = (ph - ref[6]) * kInv2Pi + s * ref[7];
-    if (x - x == 0.0 && y - y == 0.0 && w - w == 0.0 && ex - ex == 0.0 && ey - ey == 0.0 && ez - ez == 0.0)
-        return WaveRay{1.0, w, ex, ey, ez};
-    return WaveRay{0.0, 0.0, 0.0, 0.0, 0.0};
-}
+using rtpb::kWaveRef;
+using rtpb::kInv2Pi;
+using rtpb::WaveRay;
+using rtpb::wave_ray;
 RTPB_HD double wave_term(const WaveRay& f, int k) {
     switch (k) {
     case 0: return f.n;
@@ -137,22 +118,12 @@ RTPB_HD double psf_frac(const PsfRay& f, double X, double Y) {
 }
 
 // Spot images (rtpb_spot_image / rtpb_image_sweep): a 2-D histogram of the final positions per group, int32 counts,
-// so the result is exact and independent of the order of arrival.  The one definition of a ray's contribution, for
-// the plane kernel and the fused sweep alike: x and y are the ray's final position rounded to the storage type, w the
-// group's window {x_lo, y_lo, x_scale, y_scale}.  A ray counts when the spot statistics count it (x and y finite; the
-// sweep adds its own dead-row rule before calling).  tx = (x - x_lo) * x_scale and ty likewise, each one rounded
-// subtract and one rounded multiply; the ray is inside iff 0 <= tx < nx and 0 <= ty < ny, compared in floating point
-// (a NaN or infinite window, or an overflowing tx, is outside), and only then are tx and ty converted to integers:
-// no index exists for a ray that failed the test.  Returns the bin iy * nx + ix, kImageOutside for a counting ray
-// that is not inside, kImageSkip for a ray that does not count.  nx, ny <= RTPB_MAX_IMAGE_SIDE, so a bin fits an int.
-constexpr int kImageSkip = -1, kImageOutside = -2;
-RTPB_HD int image_bin(double x, double y, const double (&w)[4], int nx, int ny) {
-    if (!(x - x == 0.0 && y - y == 0.0)) return kImageSkip;
-    const double tx = (x - w[0]) * w[2], ty = (y - w[1]) * w[3];
-    if (tx >= 0.0 && tx < double(nx) && ty >= 0.0 && ty < double(ny))
-        return static_cast<int>(ty) * nx + static_cast<int>(tx);
-    return kImageOutside;
-}
+// so the result is exact and independent of the order of arrival.  The one definition of a ray's contribution is
+// image_bin (rtpb_wavemap.h, beside the map rule that bins the pupil with it): the bin iy * nx + ix, kImageOutside for
+// a counting ray that is not inside, kImageSkip for a ray that does not count.
+using rtpb::kImageSkip;
+using rtpb::kImageOutside;
+using rtpb::image_bin;
 
 // One wave's contributions to one group's image (image: the group's ny * nx counters, outside: its one; both
 // wave-uniform), bin from image_bin.  Every lane of the wave must call it.  Per-ray atomics would serialise on the
@@ -229,6 +200,51 @@ __device__ __forceinline__ void wave_energy_add(const EnergyRay& e, int nr, int3
     wave_image_add(e.bin[1], hist + nr, outside + 1);
     wave_max_bits(e.far[0], farthest);
     wave_max_bits(e.far[1], farthest + 1);
+}
+
+// Wavefront map (rtpb_wavefront_map / rtpb_wavefront_map_sweep; the rule: rtpb_wavemap.h wavemap_ray).  One wave's
+// contributions to one group's map (count and sum: the group's ny * nx cells; outside and clipped: its one of each;
+// farthest: its two maxima; all wave-uniform).  Every lane of the wave must call it.  wave_image_add extended by the
+// 64-bit sum: per distinct cell in the wave the leader issues one no-return add of the lane count and one 64-bit
+// integer add of the sum of q over the lanes that share the cell -- a masked butterfly over the wave, which every lane
+// runs (the loop is wave-uniform); a cell held by a single lane needs no reduction.  (Two adds per lane instead
+// take 1.7 to 3.5 times as long on the C5 workload: DESIGN.md, profiles/r16/per_lane_adds.patch.)  Integer adds and
+// maxima: any order, the same map.
+using rtpb::MapRay;
+using rtpb::kMapClipped;
+using rtpb::kMapWin;
+using rtpb::wavemap_ray;
+__device__ __forceinline__ void wave_map_add(const MapRay& m, int32_t* __restrict__ count,
+                                             long long* __restrict__ sum, int32_t* __restrict__ outside,
+                                             int32_t* __restrict__ clipped, double* __restrict__ farthest) {
+    const int lane = static_cast<int>(__lane_id());
+    const unsigned long long out = __ballot(m.bin == kImageOutside);
+    if (out != 0 && lane == __ffsll(out) - 1) atomicAdd(outside, __popcll(out));
+    const unsigned long long clip = __ballot(m.bin == kMapClipped);
+    if (clip != 0 && lane == __ffsll(clip) - 1) atomicAdd(clipped, __popcll(clip));
+    unsigned long long* const usum = reinterpret_cast<unsigned long long*>(sum);
+    unsigned long long pending = __ballot(m.bin >= 0);
+    while (pending != 0) {
+        const int leader = __ffsll(pending) - 1;
+        const int b = __builtin_amdgcn_readlane(m.bin, leader);
+        // (a retired lane's bin differs from b: every lane that shares a bin retires with it)
+        const unsigned long long same = __ballot(m.bin == b);
+        const int n = __popcll(same);
+        // two's complement: the unsigned sum of the lanes' q is the signed one
+        unsigned long long s = static_cast<unsigned long long>(m.q);
+        if (n > 1) {
+            s = m.bin == b ? s : 0ull;
+#pragma unroll
+            for (int w = 32; w > 0; w >>= 1) s += __shfl_xor(s, w, 64);
+        }
+        if (lane == leader) {
+            atomicAdd(count + b, n);
+            atomicAdd(usum + b, s);
+        }
+        pending &= ~same;
+    }
+    wave_max_bits(m.far_e, farthest);
+    wave_max_bits(m.far_w, farthest + 1);
 }
 
 struct SpotArgs {

@@ -7,7 +7,9 @@
 // rtpb_sweep_wave_variants.hip and rtpb_sweep_wave_variants_beam.hip the wavefront sweep over many systems and the
 // final rays of small groups (rtpb_wavefront_sweep_variants[_collimated], rtpb_final_rays_variants[_collimated]);
 // rtpb_sweep_foot.hip and rtpb_sweep_foot_beam.hip the footprint sweep (rtpb_footprint_sweep[_collimated]);
-// rtpb_sweep_energy.hip and rtpb_sweep_energy_beam.hip the energy sweep (rtpb_energy_sweep[_collimated]).
+// rtpb_sweep_energy.hip and rtpb_sweep_energy_beam.hip the energy sweep (rtpb_energy_sweep[_collimated]);
+// rtpb_sweep_wavemap.hip and rtpb_sweep_wavemap_beam.hip the wavefront map sweep
+// (rtpb_wavefront_map_sweep[_collimated]).
 // What the sweep shares with the plane kernels (the statistics, the image's contribution rule) is rtpb_stats.h, the
 // host arithmetic of a call (row planning, media table, upload layout) rtpb_sweep_host.h.
 #pragma once
@@ -44,6 +46,7 @@ struct SweepImage;
 struct SweepWave;
 struct SweepFoot;
 struct SweepEnergy;
+struct SweepMap;
 struct SweepArgs {
     const DevSurface<double>* __restrict__ surf;     // the plan's surfaces; variant sweeps: desc [n_variants][nsurf]
     union {
@@ -66,6 +69,7 @@ struct SweepArgs {
         const SweepWave* __restrict__ wave;         // wavefront mode
         const SweepFoot* __restrict__ foot;         // footprint mode
         const SweepEnergy* __restrict__ energy;     // energy mode
+        const SweepMap* __restrict__ map;           // wavefront map mode
     };
     // ray j of a group: j % n_thetas indexes the first table, j / n_thetas the second (the beam's n_thetas is its
     // nphis, its nphis its n_disps)
@@ -116,6 +120,20 @@ struct SweepEnergy {
 };
 static_assert(sizeof(SweepEnergy) % sizeof(double) == 0, "the parameters follow it");
 
+// The wavefront map mode's block of the upload, in the same place: the outputs and the call's sides, scale and limit,
+// followed by the groups' references and windows (kWaveRef + kMapWin doubles each; rtpb_wavemap.h wavemap_ray)
+struct SweepMap {
+    int32_t* count;      // [n_groups][ny][nx]
+    long long* sum;      // [n_groups][ny][nx]
+    int32_t* outside;    // [n_groups]
+    int32_t* clipped;    // [n_groups]
+    double* farthest;    // [n_groups][2]
+    double scale, w_lim; // scale = 2^q_bits
+    int32_t nx, ny;
+};
+static_assert(sizeof(SweepMap) % sizeof(double) == 0, "the references and windows follow it");
+constexpr int kMapPar = kWaveRef + kMapWin;
+
 template <typename TS>
 __device__ __forceinline__ double stored(double v) { return static_cast<double>(static_cast<TS>(v)); }
 
@@ -154,7 +172,9 @@ constexpr int kStateRows = 11;                     // bundle state per lane: x y
 #endif
 #define RTPB_SWEEP_ATTR(NS)                                                                                      \
     __attribute__((amdgpu_waves_per_eu(                                                                          \
-        (NS) == kWaveStats || (NS) == kFinalRays || (NS) == kFootStats ? RTPB_WAVE_WPE : RTPB_SWEEP_WPE, 8)))
+        (NS) == kWaveStats || (NS) == kFinalRays || (NS) == kFootStats || (NS) == kMapStats ? RTPB_WAVE_WPE      \
+                                                                                             : RTPB_SWEEP_WPE,   \
+        8)))
 // An optimisation fence on three per-lane values: the compiler moves no computation on them across it
 #if defined(__HIP_DEVICE_COMPILE__)
 #define RTPB_PIN3(a, b, c) asm volatile("" : "+v"(a), "+v"(b), "+v"(c))
@@ -178,6 +198,11 @@ constexpr int kImageStats = 0;
 // (energy_bins, wave_energy_add).  Everything else is the image mode's: which rays count, the kPosOnly steps, single
 // and bundle rows, both storage types, the occupancy class, no red tiles.
 constexpr int kEnergyStats = 2;
+// NS = kMapStats (rtpb_wavefront_map_sweep; float64, single rows only, no variants; the value is the mode's tag): the
+// wavefront mode's steps -- kPhase, the kNoAt full semantics, its occupancy class -- with the counter modes' ending:
+// no red tiles and no workspace, each ray's final state goes through wave_ray and wavemap_ray into its group's map
+// (wave_map_add), the dead-row and past-the-group lanes as to_image / to_energy handle them.
+constexpr int kMapStats = 4;
 // NS = kFinalRays (rtpb_final_rays_variants; variants, float64, single rows, groups of at most one tile): no
 // reduction, each ray's final state goes to rays_out[group][ray] as the row rtpb_trace stores for the final plane (a
 // killed ray's NaN pattern included), so the steps are the wavefront mode's.  Lanes past the group's size store nothing.
@@ -204,16 +229,19 @@ __global__ __launch_bounds__(kBlock) RTPB_SWEEP_ATTR(NS) void sweep_kernel(Sweep
                   "variants: the focus or wavefront statistics or the final rays, host-evaluated media");
     static_assert(!BUNDLE || (FEAT & 16) != 0, "bundles: host-evaluated media");
     static_assert(NS == kStats || NS == kFocusStats || NS == kImageStats || NS == kWaveStats || NS == kFinalRays ||
-                      NS == kFootStats || NS == kEnergyStats,
-                  "spot, focus, wavefront or footprint statistics, the image, the energy curves, or the final rays");
+                      NS == kFootStats || NS == kEnergyStats || NS == kMapStats,
+                  "spot, focus, wavefront or footprint statistics, the image, the energy curves, the wavefront map, or "
+                  "the final rays");
     constexpr bool kFoot = NS == kFootStats;
     static_assert(!kFoot || (!kVar && !BUNDLE && sizeof(TS) == 8), "footprints: float64, single rows, no variants");
     constexpr bool kWave = NS == kWaveStats;
     static_assert(!kWave || (!BUNDLE && sizeof(TS) == 8), "wavefront: float64, single rows");
     constexpr bool kRays = NS == kFinalRays;
     static_assert(!kRays || (kVar && !BUNDLE && sizeof(TS) == 8), "final rays: variants, float64, single rows");
-    constexpr bool kPhase = kWave || kRays;          // the trace kernel's full steps, the phase kept
-    constexpr bool kCounts = NS == kImageStats || NS == kEnergyStats;     // integer counters, no statistics
+    constexpr bool kMap = NS == kMapStats;
+    static_assert(!kMap || (!kVar && !BUNDLE && sizeof(TS) == 8), "wavefront map: float64, single rows, no variants");
+    constexpr bool kPhase = kWave || kRays || kMap;  // the trace kernel's full steps, the phase kept
+    constexpr bool kCounts = NS == kImageStats || NS == kEnergyStats || kMap;     // integer counters, no statistics
     constexpr int kRedRows = kCounts || kRays || kFoot ? 1 : BUNDLE ? 2 : NS == kStats ? kStats : 8;
     __shared__ double red[kRedRows][kBlock];
     __shared__ double state[BUNDLE ? kStateRows : 1][kBlock];
@@ -436,6 +464,22 @@ __global__ __launch_bounds__(kBlock) RTPB_SWEEP_ATTR(NS) void sweep_kernel(Sweep
         }
         wave_energy_add(e, nr, en->hist + g * 2 * nr, en->outside + 2 * g, en->farthest + 2 * g);
     };
+    // ... and the wavefront map mode's: reduce's rule of which final states reach wave_ray, then the map's own
+    auto to_map = [&](const Ray<double>& rr, bool ok, int64_t g) {
+        const cptr<SweepMap> mp = (cptr<SweepMap>)(a.map);
+        const cptr<double> q = (cptr<double>)(a.map + 1) + kMapPar * g;
+        const int nx = mp->nx, ny = mp->ny;
+        MapRay m{kImageSkip, 0, 0.0, 0.0};
+        if (ok && !is_nan(rr.dx)) {
+            const double ref[kWaveRef] = {q[0], q[1], q[2], q[3], q[4], q[5], q[6], q[7]};
+            const double win[kMapWin] = {q[8], q[9], q[10], q[11]};
+            m = wavemap_ray(wave_ray(rr.x, rr.y, rr.z, rr.dx, rr.dy, rr.dz, rr.ph, ref), win, nx, ny, mp->scale,
+                            mp->w_lim);
+        }
+        const int64_t cells = int64_t(ny) * nx;
+        wave_map_add(m, mp->count + g * cells, mp->sum + g * cells, mp->outside + g, mp->clipped + g,
+                     mp->farthest + 2 * g);
+    };
     if constexpr (!BUNDLE) {
 #pragma unroll
         for (int q = 0; q < kSweepRays; ++q) {
@@ -479,6 +523,8 @@ __global__ __launch_bounds__(kBlock) RTPB_SWEEP_ATTR(NS) void sweep_kernel(Sweep
                 to_image(r[q], tile[q] * kBlock + tid < a.gsize, grp[q]);
             } else if constexpr (NS == kEnergyStats) {
                 to_energy(r[q], tile[q] * kBlock + tid < a.gsize, grp[q]);
+            } else if constexpr (kMap) {
+                to_map(r[q], tile[q] * kBlock + tid < a.gsize, grp[q]);
             } else if constexpr (kRays) {
                 // a plain per-lane store of the row (four 16-byte stores), inside the group's own rows only
                 const int64_t j = tile[q] * kBlock + tid;
@@ -735,6 +781,41 @@ struct EnergyCall {
     double* farthest_out;
 };
 
+// ... those of the wavefront map sweeps (float64 plans; no workspace, no statistics) ...
+template <int SRC = kSrcFan>
+int map_sweep_check(const rtpb_plan* plan, int64_t n_groups, const double* group_params, const SweepSource& s,
+                    const double* refs, const double* windows, int32_t nx, int32_t ny, int32_t q_bits, double w_lim,
+                    const void* count_out, const void* sum_out, const void* outside_out, const void* clipped_out,
+                    const void* farthest_out) {
+    const char* const what = SRC == kSrcBeam ? "wavefront-map-sweep-collimated" : "wavefront-map-sweep";
+    if (!plan) return fail(RTPB_E_INVALID, "plan is NULL");
+    if (plan->dtype != RTPB_F64)
+        return fail(RTPB_E_INVALID, std::string(what) + ": float64 plans only (a float32 phase of 1e4 ... 1e7 rad has "
+                                                        "an ulp of a milliradian to a radian: its wavefront is noise)");
+    if (n_groups <= 0 || !s.complete(SRC) || !group_params)
+        return fail(RTPB_E_INVALID, std::string("bad ") + what + " arguments");
+    // (n_a * n_b: a product past int64 is past the limit too)
+    const int64_t gsize = s.n_a > 0x7fffffffll / s.n_b ? 0x80000000ll : s.n_a * s.n_b;
+    int rc = wavemap_check(what, nx, ny, q_bits, w_lim, gsize, n_groups, refs, windows, count_out, sum_out,
+                           outside_out, clipped_out, farthest_out);
+    if (rc) return rc;
+    if (n_groups > 65535) return fail(RTPB_E_LIMIT, std::string(what) + ": too many groups");
+    return RTPB_OK;
+}
+
+// rtpb_wavefront_map_sweep's own arguments (NS = kMapStats: no workspace, no statistics)
+struct MapCall {
+    const double* refs;         // host, n_groups x kWaveRef
+    const double* windows;      // host, n_groups x kMapWin
+    int32_t nx, ny, q_bits;
+    double w_lim;
+    int32_t* count_out;
+    long long* sum_out;
+    int32_t* outside_out;
+    int32_t* clipped_out;
+    double* farthest_out;
+};
+
 // A variant sweep's systems (SRC | kSrcVariant), lowered on the host (lower_variants): no plan and no device blob, the
 // descriptors ride in the call's upload.  All variants have nsurf surfaces and nsurf + 1 materials.
 struct VariantCall {
@@ -757,13 +838,15 @@ struct VariantCall {
 // NS = kFootStats: refs is the surfaces' frames (host, nsurf x kFootFrame), the workspace holds the blocks' partials
 // (n_groups x ceil(tiles / kSweepRays) x nsurf x kFootCols) and stats_out is n_groups x nsurf x kFootCols.
 // NS = kEnergyStats: en holds the call's parameters and outputs, as im does the image's; no workspace, no statistics.
+// NS = kMapStats: mp likewise; the references and the windows join the upload group by group.
 template <int NS, int SRC = kSrcFan>
 int sweep_impl(const rtpb_plan* plan_c, int32_t device, int64_t n_groups, const double* group_params,
                const SweepSource& src, double* workspace, double* stats_out, void* stream,
                const ImageCall* im = nullptr, const double* refs = nullptr, const VariantCall* vc = nullptr,
-               const EnergyCall* en = nullptr) {
-    constexpr bool kEnergy = NS == kEnergyStats;
+               const EnergyCall* en = nullptr, const MapCall* mp = nullptr) {
+    constexpr bool kEnergy = NS == kEnergyStats, kMap = NS == kMapStats;
     static_assert(!kEnergy || (SRC & kSrcVariant) == 0, "energy curves: no variants");
+    static_assert(!kMap || (SRC & kSrcVariant) == 0, "wavefront map: no variants");
     constexpr bool kImage = NS == kImageStats, kWave = NS == kWaveStats, kBeam = (SRC & ~kSrcVariant) == kSrcBeam;
     constexpr bool kVar = (SRC & kSrcVariant) != 0, kRays = NS == kFinalRays, kFoot = NS == kFootStats;
     static_assert(!kFoot || !kVar, "footprints: no variants");
@@ -784,7 +867,7 @@ int sweep_impl(const rtpb_plan* plan_c, int32_t device, int64_t n_groups, const 
     const int32_t dtype = kVar ? vc->dtype : plan->dtype;
     const int feat = kVar ? vc->feat : plan->feat;
     const size_t M = size_t(nsurf) + 1;
-    const SweepRows pr = plan_sweep_rows(group_params, n_groups, pre_n && !kWave && !kRays && !kFoot, kSweepRays,
+    const SweepRows pr = plan_sweep_rows(group_params, n_groups, pre_n && !kWave && !kRays && !kFoot && !kMap, kSweepRays,
                                          kMaxBundle, kBeam ? src.frames : nullptr,
                                          kVar ? vc->group_variant : nullptr);
     // (a beam's second table is its offsets, plain doubles: half as many pair slots; the footprint mode's block is
@@ -793,10 +876,11 @@ int sweep_impl(const rtpb_plan* plan_c, int32_t device, int64_t n_groups, const 
                           pr.bundles.size() + pr.singles.size() + pr.rows.size() + (kVar ? size_t(n_groups) : 0),
                           kImage    ? sizeof(SweepImage) / sizeof(double)
                           : kEnergy ? sizeof(SweepEnergy) / sizeof(double)
+                          : kMap    ? sizeof(SweepMap) / sizeof(double)
                           : kWave   ? sizeof(SweepWave) / sizeof(double)
                           : kFoot ? sizeof(SweepFoot) / sizeof(double) + size_t(nsurf) * kFootFrame
                                   : 0,
-                          kWave ? kWaveRef : kFoot ? 0 : 4, kBeam ? kFrame : 0,
+                          kWave ? kWaveRef : kMap ? kMapPar : kFoot ? 0 : 4, kBeam ? kFrame : 0,
                           kVar ? vc->desc.size() * sizeof(DevSurface<double>) : 0);
     StreamScratch dbuf;
     rc = dbuf.alloc(lay.bytes, st);
@@ -838,6 +922,19 @@ int sweep_impl(const rtpb_plan* plan_c, int32_t device, int64_t n_groups, const 
         rc = energy_clear(en->hist_out, en->outside_out, en->farthest_out, n_groups, en->nr, st);
         if (rc) return rc;
     }
+    if constexpr (kMap) {
+        const SweepMap head{mp->count_out, mp->sum_out, mp->outside_out, mp->clipped_out, mp->farthest_out,
+                            std::ldexp(1.0, mp->q_bits), mp->w_lim, mp->nx, mp->ny};
+        std::memcpy(h + lay.img, &head, sizeof(head));
+        double* const par = reinterpret_cast<double*>(h + lay.win);
+        for (int64_t gi = 0; gi < n_groups; ++gi) {
+            std::memcpy(par + kMapPar * gi, mp->refs + kWaveRef * gi, kWaveRef * sizeof(double));
+            std::memcpy(par + kMapPar * gi + kWaveRef, mp->windows + kMapWin * gi, kMapWin * sizeof(double));
+        }
+        rc = wavemap_clear(mp->count_out, mp->sum_out, mp->outside_out, mp->clipped_out, mp->farthest_out, n_groups,
+                           mp->nx, mp->ny, st);
+        if (rc) return rc;
+    }
     if constexpr (kWave) {
         const SweepWave head{workspace};
         std::memcpy(h + lay.img, &head, sizeof(head));
@@ -872,6 +969,7 @@ int sweep_impl(const rtpb_plan* plan_c, int32_t device, int64_t n_groups, const 
     a.gn = reinterpret_cast<const double*>(d + lay.gn);
     if constexpr (kImage) a.image = reinterpret_cast<const SweepImage*>(d + lay.img);
     else if constexpr (kEnergy) a.energy = reinterpret_cast<const SweepEnergy*>(d + lay.img);
+    else if constexpr (kMap) a.map = reinterpret_cast<const SweepMap*>(d + lay.img);
     else if constexpr (kWave) a.wave = reinterpret_cast<const SweepWave*>(d + lay.img);
     else if constexpr (kFoot) a.foot = reinterpret_cast<const SweepFoot*>(d + lay.img);
     else if constexpr (kRays) a.partials = stats_out;
@@ -892,7 +990,8 @@ int sweep_impl(const rtpb_plan* plan_c, int32_t device, int64_t n_groups, const 
     auto go = [&](auto tag) {
         using TS = decltype(tag);
         const int f = feat & 3;                       // lens / POLY6 code (no pre_n: POLY6); tables always compiled in
-        if constexpr (!kWave && !kRays && !kFoot) {   // (the wavefront, final-rays and footprint modes plan no bundle rows)
+        // (the wavefront, final-rays, footprint and map modes plan no bundle rows)
+        if constexpr (!kWave && !kRays && !kFoot && !kMap) {
             if (!pr.rows.empty()) {
                 SweepArgs ap = a;
                 ap.gidx = didx;
@@ -913,7 +1012,7 @@ int sweep_impl(const rtpb_plan* plan_c, int32_t device, int64_t n_groups, const 
                 hipLaunchKernelGGL((sweep_kernel<TS, 3, false, NS, SRC>), grid, dim3(kBlock), 0, st, as);
         }
     };
-    if constexpr (kWave || kRays || kFoot) {
+    if constexpr (kWave || kRays || kFoot || kMap) {
         go(double{});
     } else {
         if (dtype == RTPB_F64) go(double{});
@@ -923,7 +1022,7 @@ int sweep_impl(const rtpb_plan* plan_c, int32_t device, int64_t n_groups, const 
     if constexpr (kFoot) {
         rc = launch_foot_final(workspace, stats_out, n_groups, (tiles + kSweepRays - 1) / kSweepRays, nsurf, st);
         if (rc) return rc;
-    } else if constexpr (!kImage && !kEnergy && !kRays) {
+    } else if constexpr (!kImage && !kEnergy && !kMap && !kRays) {
         rc = launch_stats_final(NS, workspace, stats_out, n_groups, tiles, st);
         if (rc) return rc;
     }
