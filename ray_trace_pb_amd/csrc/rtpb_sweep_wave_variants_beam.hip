@@ -1,9 +1,5 @@
-// rtpb_sweep_wave_variants_beam.hip -- the wavefront sweep of collimated beams over many systems,
-// rtpb_wavefront_sweep_variants_collimated, and the final rays of small beams through each group's variant,
-// rtpb_final_rays_variants_collimated; with them the beam instantiations of the sweep kernel's variant form with the
-// trace kernel's full steps (rtpb_sweep_kernel.h).  A unit of its own, so that it compiles beside
-// rtpb_sweep_wave_variants.hip and not after it.
-#include "rtpb_sweep_kernel.h"
+// rtpb_sweep_wave_variants_beam.hip -- collimated beams: the wavefront and final-rays modes over variants.
+#include "rtpb_sweep_call.h"
 
 extern "C" {
 
@@ -14,9 +10,10 @@ int rtpb_wavefront_sweep_variants_collimated(const rtpb_surface* surfaces, int32
                                              int64_t n_disps, int64_t nphis, const double* offsets,
                                              const double* phi_cos_sin, const double* refs, double* workspace,
                                              int64_t workspace_len, double* stats_out, void* stream) {
-    const SweepSource src = beam_source(group_frames, n_disps, nphis, offsets, phi_cos_sin);
-    return wavefront_sweep_variants<kSrcBeam>(surfaces, nsurf, materials, n_variants, device, n_groups, group_params,
-                                              group_variant, src, refs, workspace, workspace_len, stats_out, stream);
+    return sweep_variants_entry<kWaveStats, kSrcBeam>(
+        surfaces, nsurf, materials, n_variants, RTPB_F64, device, n_groups, group_params, group_variant,
+        beam_source(group_frames, n_disps, nphis, offsets, phi_cos_sin),
+        {{workspace, workspace_len, stats_out}, refs}, stream);
 }
 
 int rtpb_final_rays_variants_collimated(const rtpb_surface* surfaces, int32_t nsurf, const rtpb_material* materials,
@@ -25,9 +22,9 @@ int rtpb_final_rays_variants_collimated(const rtpb_surface* surfaces, int32_t ns
                                         const double* group_frames, int64_t n_disps, int64_t nphis,
                                         const double* offsets, const double* phi_cos_sin, double* rays_out,
                                         void* stream) {
-    const SweepSource src = beam_source(group_frames, n_disps, nphis, offsets, phi_cos_sin);
-    return final_rays_variants<kSrcBeam>(surfaces, nsurf, materials, n_variants, device, n_groups, group_params,
-                                         group_variant, src, rays_out, stream);
+    return sweep_variants_entry<kFinalRays, kSrcBeam>(
+        surfaces, nsurf, materials, n_variants, RTPB_F64, device, n_groups, group_params, group_variant,
+        beam_source(group_frames, n_disps, nphis, offsets, phi_cos_sin), {rays_out}, stream);
 }
 
 }  // extern "C"
