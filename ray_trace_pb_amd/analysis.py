@@ -50,34 +50,15 @@ WAVE_STAT_NAMES = ("count", "sum_w", "sum_ww", "sum_ex", "sum_ey", "sum_ez", "su
 WAVE_RCOND = 1e-10
 
 
-def _plane_stats_raw(entry, ncols, plane, group_size, stream):
-    import torch
-    n = plane.shape[0]
-    if n % group_size:
-        raise ValueError("plane length must be a multiple of group_size")
-    ngroups = n // group_size
-    plane = plane.contiguous()
-    tiles = -(-group_size // 256)
-    ws = torch.empty(ngroups * tiles * ncols, dtype=torch.float64, device=plane.device)
-    stats = torch.empty((ngroups, ncols), dtype=torch.float64, device=plane.device)
-    if stream is None:
-        stream = torch.cuda.current_stream(plane.device).cuda_stream
-    C.check(getattr(C.lib(), entry)(plane.device.index or 0,
-                                    C.RTPB_F64 if plane.dtype == torch.float64 else C.RTPB_F32,
-                                    plane.data_ptr(), group_size, ngroups, ws.data_ptr(), ws.numel(),
-                                    stats.data_ptr(), stream))
-    return stats
-
-
 def spot_stats_raw(plane, group_size, stream=None):
     """Per-group sums (n_groups, 7) of a torch CUDA (N, 8) plane, N = n_groups * group_size."""
-    return _plane_stats_raw("rtpb_spot_stats", 7, plane, group_size, stream)
+    return _plane(_SPOT, plane, group_size, stream=stream)[0]
 
 
 def focus_stats_raw(plane, group_size, stream=None):
     """Per-group focus sums (n_groups, 16; ``FOCUS_STAT_NAMES``) of a torch CUDA (N, 8) plane -- any history
     plane, e.g. ``h[-1]``.  A ray counts when x, y and both slopes dx/dz, dy/dz are finite."""
-    return _plane_stats_raw("rtpb_focus_stats", 16, plane, group_size, stream)
+    return _plane(_FOCUS, plane, group_size, stream=stream)[0]
 
 
 def summarize(raw):
@@ -154,30 +135,22 @@ def _wave_refs(refs, shape):
     return refs
 
 
+def _phase_needs_float64(what, dtype=None, plane=None):
+    """``ValueError`` unless a sweep's ``dtype`` keyword, or a torch ``plane``, is float64; ``what`` opens the message.
+    Everything that reads a ray's phase is float64 only: a float32 phase of 1e4 ... 1e7 rad is noise at the scale of
+    a wave."""
+    if not (dtype in ("float64", np.float64) if plane is None else str(plane.dtype) == "torch.float64"):
+        raise ValueError(what + ": a float32 phase of 1e4 ... 1e7 rad has an ulp of a milliradian to a radian")
+
+
 def wavefront_stats_raw(plane, group_size, refs, stream=None):
     """Per-group wavefront sums (n_groups, 15; ``WAVE_STAT_NAMES``) of a torch CUDA (N, 8) float64 plane against
     ``refs`` (n_groups, 8) = (C0, d0, p0, kf) per group, host values (:func:`wavefront_refs`).  Per ray
     e = d - d0 and the OPD in waves w = (phase - p0) / (2 pi) + kf (C0 - r) . d; a ray counts when x, y, w and e are
     finite.  float64 only: a float32 phase of 1e4 ... 1e7 rad is noise at the scale of a wave, so a float32 plane
     raises ``ValueError``."""
-    import torch
-    if plane.dtype != torch.float64:
-        raise ValueError("wavefront statistics need a float64 plane: a float32 phase of 1e4 ... 1e7 rad has an ulp of "
-                         "a milliradian to a radian")
-    n = plane.shape[0]
-    if n % group_size:
-        raise ValueError("plane length must be a multiple of group_size")
-    ngroups = n // group_size
-    refs = _wave_refs(refs, (ngroups, 8))
-    plane = plane.contiguous()
-    tiles = -(-group_size // 256)
-    ws = torch.empty(ngroups * tiles * 15, dtype=torch.float64, device=plane.device)
-    stats = torch.empty((ngroups, 15), dtype=torch.float64, device=plane.device)
-    if stream is None:
-        stream = torch.cuda.current_stream(plane.device).cuda_stream
-    C.check(C.lib().rtpb_wavefront_stats(plane.device.index or 0, C.RTPB_F64, plane.data_ptr(), group_size, ngroups,
-                                         refs.ctypes.data, ws.data_ptr(), ws.numel(), stats.data_ptr(), stream))
-    return stats
+    _phase_needs_float64("wavefront statistics need a float64 plane", plane=plane)
+    return _plane(_wave_mode(_wave_refs(refs, (plane.shape[0] // group_size, 8))), plane, group_size, stream=stream)[0]
 
 
 def _wave_var(var, cov_we, cov_ee, kf, delta):
@@ -260,35 +233,115 @@ def focus_stats(plane, group_size):
     return summarize_focus(focus_stats_raw(plane, group_size).cpu().numpy())
 
 
-# A sweep mode is what differs between the spot, focus and image sweeps, as the drivers below read it:
-#   entry, ncols    the fused C entry point; its statistics per group (None: no workspace to size a batch by)
-#   shard(dev, per, g0, n, batch) -> (outputs, tail): the device tensors that receive groups [g0, g0 + n), one row per
-#                   group, and tail(b0, b1), entry's arguments between the fan tables and the stream for groups
-#                   [b0, b1) of them; ``per`` rays a group, at most ``batch`` groups a call
-#   hbm_bytes(per, n)   what the fused sweep of n groups moves through HBM
-#   host(G), plane(out, per, b0, nb)   unfused: zeroed host arrays for G groups, and the device reduction of the
-#                   final plane ``out`` of groups [b0, b0 + nb), one tensor per host array
-#   finish(nf, nw, *arrays)   the summary from the host arrays, in outputs' / host's order
-def _stats_mode(entry, plane_raw, ncols, summary):
-    """The mode of a statistics sweep: ``plane_raw`` is the unfused plane reduction, ``summary`` the host summary of
-    the raw sums.  Per device: a batch's workspace (the per-tile partial sums) and the shard's statistics."""
-    def shard(dev, per, g0, n, batch):
-        import torch
-        ws = torch.empty(batch * -(-per // 256) * ncols, dtype=torch.float64, device=dev)
-        stats = torch.empty((n, ncols), dtype=torch.float64, device=dev)
-        return (stats,), lambda b0, b1: (ws.data_ptr(), ws.numel(), stats[b0 - g0:b1 - g0].data_ptr())
+# A sweep mode states once what differs between the analyses; the drivers below derive the rest from it:
+#   entry, plane_entry   the fused C entry point (None: the Huygens PSF has none) and the one that reduces a stored
+#                   plane (None: the final rays are their own result)
+#   outputs         per output (the shape that follows the group index, the NumPy dtype).  The shard's device tensors
+#                   of the fused sweep, the zeroed host arrays host(G) of the unfused one and the allocation inside a
+#                   plane call all come from this list, one row per group
+#   tables          the per-group host tables, C-contiguous float64, one row per group: refs (G, 8), windows (G, 4),
+#                   params (G, 4); groups [b0, b1) are rows [b0, b1) of each.  ``device_tables``: the plane call reads
+#                   them on the device
+#   consts, plane_consts   the per-call constants of the fused and of the plane call (the same unless stated: the
+#                   footprint calls take ``frames, S`` and ``S, frames``).  An array or a tensor passes its address; a
+#                   function is called with the plane's device first (the PSF's weights, uploaded once)
+#   ws              (doubles per partial, tiles of 256 rays per partial of the fused call) where a group's partial sums
+#                   go through a workspace, else None; a plane call keeps one partial per tile
+#   cleared         the outputs are cleared and then added to (counters and maxima): they cross HBM twice
+#   planes          what the unfused path stores: "final", or "all" (the footprints read a batch's whole history)
+#   finish(shape, *arrays)   the summary from the host arrays, in outputs' order, reshaped to the source's ``shape``
+#   ncols, group_doubles   what :func:`_sweep_plan` sizes a batch by: the statistics of a tile partial, or what the mode
+#                   itself says a group adds to a batch's device memory
+# Every call's arguments therefore end: tables[b0:b1], constants, [workspace, its length], outputs[b0:b1], stream.
+# hbm_bytes(per, n) is what the fused sweep of n groups moves through HBM: the outputs (twice where cleared) and the
+# partials written and read back; the rays never leave the registers.
+def _mode(entry, plane_entry, outputs, finish, tables=(), consts=(), plane_consts=None, ws=None, cleared=False,
+          planes="final", device_tables=False, group_doubles=None):
+    out_bytes = sum(int(np.prod(shape, dtype=np.int64)) * np.dtype(dt).itemsize for shape, dt in outputs)
+
+    def ws_doubles(per, tiles_per_partial=None):
+        """The doubles of one group's partials: of the fused call, or with the given number of tiles a partial."""
+        return 0 if ws is None else -(-(-(-per // 256)) // (tiles_per_partial or ws[1])) * ws[0]
 
     return SimpleNamespace(
-        entry=entry, ncols=ncols, shard=shard,
-        # the per-tile partial sums written and read back, and the statistics (the rays never leave the registers)
-        hbm_bytes=lambda per, n: n * -(-per // 256) * ncols * 8 * 2 + n * ncols * 8,
-        host=lambda G: (np.zeros((G, ncols)),),
-        plane=lambda out, per, b0, nb: (plane_raw(out, per),),
-        finish=lambda nf, nw, raw: summary(raw.reshape(nf, nw, ncols)))
+        entry=entry, plane_entry=plane_entry, outputs=outputs, finish=finish, tables=tables, consts=consts,
+        plane_consts=consts if plane_consts is None else plane_consts, ws=ws, ws_doubles=ws_doubles, planes=planes,
+        device_tables=device_tables, group_doubles=group_doubles,
+        ncols=ws[0] if ws is not None and group_doubles is None else None,
+        hbm_bytes=lambda per, n: n * (out_bytes * (2 if cleared else 1) + 2 * 8 * ws_doubles(per)),
+        host=lambda G: tuple(np.zeros((G,) + shape, dtype=dt) for shape, dt in outputs))
 
 
-_SPOT = _stats_mode("rtpb_spot_sweep", spot_stats_raw, 7, summarize)
-_FOCUS = _stats_mode("rtpb_focus_sweep", focus_stats_raw, 16, summarize_focus)
+def _address(x):
+    """What a C call takes for a table or a constant: the address of an array or a tensor, anything else as it is."""
+    if isinstance(x, np.ndarray):
+        return x.ctypes.data
+    return x.data_ptr() if hasattr(x, "data_ptr") else x
+
+
+def _device_outputs(mode, n, dev):
+    import torch
+    return tuple(torch.empty((n,) + shape, dtype=getattr(torch, np.dtype(dt).name), device=dev)
+                 for shape, dt in mode.outputs)
+
+
+def _shard(mode, dev, per, g0, n, batch):
+    """(outputs, tail) of one device of the fused sweep: the tensors that receive groups [g0, g0 + n), one row per
+    group, and tail(b0, b1), the entry point's arguments between the source's and the stream for groups [b0, b1) of
+    them; ``per`` rays a group, at most ``batch`` groups a call, whose partials share one workspace."""
+    import torch
+    ws = None if mode.ws is None else torch.empty(batch * mode.ws_doubles(per), dtype=torch.float64, device=dev)
+    outputs = _device_outputs(mode, n, dev)
+    consts = tuple(_address(c) for c in mode.consts)
+
+    def tail(b0, b1):
+        return (*(t[b0:b1].ctypes.data for t in mode.tables), *consts,
+                *(() if ws is None else (ws.data_ptr(), ws.numel())),
+                *(t[b0 - g0:b1 - g0].data_ptr() for t in outputs))
+    return outputs, tail
+
+
+def _plane(mode, plane, group_size, b0=0, stream=None):
+    """``mode.plane_entry`` on a stored torch CUDA plane (N, 8) -- or history (1 + 2 S, N, 8) -- of N = n_groups *
+    ``group_size`` rays, the groups being [b0, b0 + n_groups) of the mode's tables: the one place that checks the
+    length, picks the dtype code and the stream, puts the tables where the call reads them, allocates the workspace
+    and the outputs, and calls.  Returns the outputs, torch tensors with one row per group."""
+    import torch
+    n, dev = plane.shape[-2], plane.device
+    if n % group_size:
+        raise ValueError(("plane" if plane.dim() == 2 else "history") + " length must be a multiple of group_size")
+    ngroups = n // group_size
+    plane = plane.contiguous()
+    tables = [t[b0:b0 + ngroups] for t in mode.tables]
+    if mode.device_tables:
+        tables = [t.to(device=dev, dtype=torch.float64).contiguous() if torch.is_tensor(t) else
+                  torch.from_numpy(np.array(t, dtype=np.float64)).to(dev) for t in tables]
+    consts = [c(dev) if callable(c) else c for c in mode.plane_consts]
+    ws = []
+    if mode.ws is not None:
+        ws = [torch.empty(ngroups * mode.ws_doubles(group_size, 1), dtype=torch.float64, device=dev)]
+    outputs = _device_outputs(mode, ngroups, dev)
+    if stream is None:
+        stream = torch.cuda.current_stream(dev).cuda_stream
+    C.check(getattr(C.lib(), mode.plane_entry)(
+        dev.index or 0, C.RTPB_F64 if plane.dtype == torch.float64 else C.RTPB_F32, plane.data_ptr(), group_size,
+        ngroups, *(_address(t) for t in tables), *(_address(c) for c in consts),
+        *(a for w in ws for a in (w.data_ptr(), w.numel())), *(t.data_ptr() for t in outputs), stream))
+    return outputs
+
+
+def _stats_mode(entry, plane_entry, ncols, summary, refs=None):
+    """The mode of a statistics sweep: ``ncols`` sums per group through per-tile partials, ``summary`` their host
+    summary.  ``refs`` (..., 8), C-contiguous float64, are the wavefront statistics' references: a table of the calls
+    and the summary's second argument."""
+    refs = () if refs is None else (refs,)
+    return _mode(entry, plane_entry, (((ncols,), np.float64),),
+                 lambda shape, raw: summary(raw.reshape(shape + (ncols,)), *(r.reshape(shape + (8,)) for r in refs)),
+                 tables=tuple(r.reshape(-1, 8) for r in refs), ws=(ncols, 1))
+
+
+_SPOT = _stats_mode("rtpb_spot_sweep", "rtpb_spot_stats", 7, summarize)
+_FOCUS = _stats_mode("rtpb_focus_sweep", "rtpb_focus_stats", 16, summarize_focus)
 
 
 def spot_sweep(system, initial_material, final_material, field_points, wavelengths, theta_max, n_thetas, nphis=1,
@@ -354,26 +407,41 @@ def wavefront_refs(system, initial_material, final_material, field_points, wavel
     ray -- the field point along ``center_ray``, ``get_ray_fan(field, 0, 1, wavelength)`` -- traced through the
     ordinary ``planes='final'`` path, and kf = final_material.n(wavelength) / wavelength.  A group whose chief ray
     dies gets a reference of NaN: every ray's OPD is then NaN, the group counts 0 and its summary is NaN."""
-    from .raytrace import get_ray_fan
     field_points, wavelengths = _grid(field_points, wavelengths)
-    nf = field_points.shape[0]
-    if spot_summary is None:
-        spot_summary, _ = spot_sweep(system, initial_material, final_material, field_points, wavelengths,
-                                     center_ray=center_ray, device=device, **fan_kw)
-    chief = np.concatenate([get_ray_fan(f, 0.0, 1, w, center_ray=center_ray) for f in field_points
-                            for w in wavelengths])
-    return _refs_from(system, initial_material, final_material, nf, wavelengths, spot_summary, chief, device)
+    sweep_kw = _sweep_kw(fan_kw)
+    source = None if spot_summary is not None else _fan_source(field_points, wavelengths, center_ray=center_ray,
+                                                               **{"nphis": 1, **fan_kw})
+    return _refs(system, initial_material, final_material, source,
+                 _fan_source(field_points, wavelengths, 0.0, 1, 1, center_ray), spot_summary, device, *sweep_kw)
 
 
-def _refs_from(system, initial_material, final_material, nf, wavelengths, spot_summary, chief, device):
-    """(nf, n_wavelengths, 8) references: the summary's centroids, the chief rays (host, one per group, field-major)
-    traced through the ordinary planes='final' path, and kf."""
+def _sweep_kw(kw):
+    """The sweep's own keywords taken out of a refs call's ``**kw`` -- :func:`_sweep`'s last four arguments, with the
+    public sweeps' defaults; what stays in ``kw`` describes the source."""
+    return [kw.pop(k, default) for k, default in (("dtype", "float64"), ("groups_per_batch", None), ("fused", True),
+                                                  ("devices", None))]
+
+
+def _refs(system, initial_material, final_material, source, chief, spot_summary, device, dtype="float64",
+          groups_per_batch=None, fused=True, devices=None):
+    """(n_fields, n_wavelengths, 8) references of a source's groups: the centroids of ``spot_summary`` -- None: of the
+    spot sweep of ``source``, which the last four arguments describe --, the rays of ``chief`` (the source of one chief
+    ray per group: the fan of half-angle 0 with one ray, the beam with one zero offset) traced through the ordinary
+    planes='final' path, and kf."""
     import torch
-    nw = wavelengths.size
-    refs = np.empty((nf, nw, 8))
-    refs[..., 0:3] = np.asarray(spot_summary["centroid"], dtype=np.float64).reshape(nf, nw, 3)
-    fin = system.ray_trace(torch.from_numpy(chief).to(torch.device(device)), initial_material, final_material,
-                           planes="final")[-1].cpu().numpy().reshape(nf, nw, 8)
+    if spot_summary is None:
+        spot_summary, _ = _sweep(_SPOT, system, initial_material, final_material, source, device, dtype,
+                                 groups_per_batch, fused, devices)
+    fin = system.ray_trace(torch.from_numpy(chief.rays()).to(torch.device(device)), initial_material, final_material,
+                           planes="final")[-1].cpu().numpy().reshape(chief.shape + (8,))
+    return _refs_from(spot_summary["centroid"], fin, final_material, chief.wavelengths)
+
+
+def _refs_from(centroids, fin, final_material, wavelengths):
+    """The references (..., n_wavelengths, 8) = (C0, d0, p0, kf) from the groups' centroids and their chief rays' final
+    rows ``fin`` (..., n_wavelengths, 8); NaN where the chief ray died."""
+    refs = np.empty(fin.shape)
+    refs[..., 0:3] = np.asarray(centroids, dtype=np.float64).reshape(fin.shape[:-1] + (3,))
     refs[..., 3:7] = fin[..., 3:7]
     refs[..., 7] = [float(final_material.n(w)) / w for w in wavelengths]
     refs[~np.isfinite(fin[..., :7]).all(axis=-1)] = np.nan
@@ -381,21 +449,20 @@ def _refs_from(system, initial_material, final_material, nf, wavelengths, spot_s
 
 
 def _wave_mode(refs):
-    """The wavefront sweep as the drivers see it (:func:`_stats_mode`, with the groups' references as
-    :func:`_image_mode` carries the windows): ``refs`` is C-contiguous (n_fields, n_wavelengths, 8) float64, so
-    the references of groups [b0, b1) are contiguous in it."""
-    ref = refs.reshape(-1, 8)
-    base = _stats_mode("rtpb_wavefront_sweep", None, 15, None)
-    stats_shard = base.shard
+    """The wavefront sweep as the drivers see it: the statistics mode with the groups' references.  ``refs`` is
+    C-contiguous (..., 8) float64, so the references of groups [b0, b1) are contiguous in it."""
+    return _stats_mode("rtpb_wavefront_sweep", "rtpb_wavefront_stats", 15, summarize_wavefront, refs)
 
-    def shard(dev, per, g0, n, batch):
-        outputs, tail = stats_shard(dev, per, g0, n, batch)
-        return outputs, lambda b0, b1: (ref[b0:b1].ctypes.data,) + tail(b0, b1)
 
-    base.shard = shard
-    base.plane = lambda out, per, b0, nb: (wavefront_stats_raw(out, per, ref[b0:b0 + nb]),)
-    base.finish = lambda nf, nw, raw: summarize_wavefront(raw.reshape(nf, nw, 15), refs)
-    return base
+def _wave_sweep(system, initial_material, final_material, source, device, refs, groups_per_batch, fused, devices,
+                dtype):
+    """What the two wavefront sweeps share once the source exists."""
+    _phase_needs_float64("wavefront_sweep is float64 only", dtype)
+    if refs is None:
+        refs = _refs(system, initial_material, final_material, source, source.chief(), None, device,
+                     groups_per_batch=groups_per_batch, devices=devices)
+    return _sweep(_wave_mode(_wave_refs(refs, source.shape + (8,))), system, initial_material, final_material, source,
+                  device, "float64", groups_per_batch, fused, devices)
 
 
 def wavefront_sweep(system, initial_material, final_material, field_points, wavelengths, theta_max, n_thetas,
@@ -414,18 +481,9 @@ def wavefront_sweep(system, initial_material, final_material, field_points, wave
     ``reference_best`` locates; :func:`rms_opd_at` gives the figure about any other point.
 
     float64 only (``dtype`` is there to say so: anything else raises ``ValueError``)."""
-    if dtype not in ("float64", np.float64):
-        raise ValueError("wavefront_sweep is float64 only: a float32 phase of 1e4 ... 1e7 rad has an ulp of a "
-                         "milliradian to a radian")
-    field_points, wavelengths = _grid(field_points, wavelengths)
-    if refs is None:
-        refs = wavefront_refs(system, initial_material, final_material, field_points, wavelengths,
-                              center_ray=center_ray, device=device, theta_max=theta_max, n_thetas=n_thetas,
-                              nphis=nphis, groups_per_batch=groups_per_batch, devices=devices)
-    refs = _wave_refs(refs, (field_points.shape[0], wavelengths.size, 8))
-    return _sweep(_wave_mode(refs), system, initial_material, final_material,
-                  _fan_source(field_points, wavelengths, theta_max, n_thetas, nphis, center_ray), device, "float64",
-                  groups_per_batch, fused, devices)
+    return _wave_sweep(system, initial_material, final_material,
+                       _fan_source(field_points, wavelengths, theta_max, n_thetas, nphis, center_ray), device, refs,
+                       groups_per_batch, fused, devices, dtype)
 
 
 def _grid(field_points, wavelengths):
@@ -435,7 +493,12 @@ def _grid(field_points, wavelengths):
 
 # A sweep source is what differs between the fans and the collimated beams, as the drivers read it:
 #   nf, nw, per     fields (field points, or beams), wavelengths and rays per group; group = field * nw + wavelength
+#   shape           what a summary's arrays lead with, one entry per group: (nf, nw); a variant source's
+#                   (n_variants, n_fields, nw)
 #   wavelengths     (nw,) float64
+#   chief()         the source of one chief ray per group: the fan of half-angle 0 with one ray, the beam with one
+#                   zero offset (the references' d0 and p0 come from these rays)
+#   rays()          every group's rays on the host, (nf * nw * per, 8), from the reference's generator
 #   suffix          of the fused C entry point's name after the mode's
 #   head(copies=1)  -> head(b0, b1): the entry's arguments from group_params up to the mode's tail, for groups
 #                   [b0, b1), and the host arrays they point into (to be kept until the call returns); with ``copies``
@@ -469,8 +532,14 @@ def _fan_source(field_points, wavelengths, theta_max, n_thetas, nphis, center_ra
         from .raytrace import fan_into
         fan_into(buf, field_points[g // nw], theta_max, n_thetas, wavelengths[g % nw], nphis, center_ray)
 
-    return SimpleNamespace(nf=nf, nw=nw, per=n_thetas * nphis, wavelengths=wavelengths, suffix="", head=head,
-                           into=into)
+    def rays():
+        from .raytrace import get_ray_fan
+        return np.concatenate([get_ray_fan(f, theta_max, n_thetas, w, nphis, center_ray) for f in field_points
+                               for w in wavelengths])
+
+    return SimpleNamespace(nf=nf, nw=nw, shape=(nf, nw), per=n_thetas * nphis, wavelengths=wavelengths, suffix="",
+                           head=head, into=into, rays=rays,
+                           chief=lambda: _fan_source(field_points, wavelengths, 0.0, 1, 1, center_ray))
 
 
 def _beams(normals, pt):
@@ -519,8 +588,14 @@ def _beam_source(normals, wavelengths, displacement_max, n_disps, nphis, phi_sta
         collimated_into(buf, pts[g // nw], displacement_max, n_disps, wavelengths[g % nw], nphis, phi_start,
                         normals[g // nw])
 
-    return SimpleNamespace(nf=nf, nw=nw, per=n_disps * nphis, wavelengths=wavelengths, suffix="_collimated",
-                           head=head, into=into, normals=normals, pts=pts)
+    def rays():
+        from .raytrace import get_collimated_rays
+        return np.concatenate([get_collimated_rays(p, displacement_max, n_disps, w, nphis, phi_start, n)
+                               for p, n in zip(pts, normals) for w in wavelengths])
+
+    return SimpleNamespace(nf=nf, nw=nw, shape=(nf, nw), per=n_disps * nphis, wavelengths=wavelengths,
+                           suffix="_collimated", head=head, into=into, rays=rays, normals=normals, pts=pts,
+                           chief=lambda: _beam_source(normals, wavelengths, 0, 1, 1, 0., pts))
 
 
 def _sweep(mode, system, initial_material, final_material, source, device, dtype, groups_per_batch, fused, devices):
@@ -547,17 +622,18 @@ def _sweep(mode, system, initial_material, final_material, source, device, dtype
         arrays, dt, extra = _sweep_fused(mode, low, S, source, devs, groups_per_batch)
     else:
         arrays, dt, extra = _sweep_unfused(mode, low, S, source, dev, tdt, groups_per_batch)
-    nf, nw = source.nf, source.nw
-    rays = nf * nw * source.per
-    return mode.finish(nf, nw, *arrays), {"seconds": dt, "rays": rays, "ray_surface_per_s": rays * S / dt, **extra}
+    rays = source.nf * source.nw * source.per
+    return mode.finish(source.shape, *arrays), {"seconds": dt, "rays": rays, "ray_surface_per_s": rays * S / dt,
+                                                **extra}
 
 
 def _sweep_unfused(mode, low, S, source, dev, tdt, groups_per_batch):
-    """Ray generation -> trace planes='final' -> ``mode.plane`` per batch of groups, through HBM buffers.  A mode
-    with ``planes = "all"`` (the footprints) gets the batch's whole history, (1 + 2 S, rays, 8) contiguous."""
+    """Ray generation -> trace planes='final' -> the mode's plane call (:func:`_plane`) per batch of groups, through
+    HBM buffers.  A mode with ``planes = "all"`` (the footprints) gets the batch's whole history, (1 + 2 S, rays, 8)
+    contiguous."""
     import torch
     G, per = source.nf * source.nw, source.per
-    sel = E.resolve_planes(getattr(mode, "planes", "final"), S)
+    sel = E.resolve_planes(mode.planes, S)
     P = len(sel)
     if groups_per_batch is None:
         groups_per_batch = max(1, min(G, (1 << 27) // (per * P)))     # ~128M ray records in flight
@@ -573,7 +649,7 @@ def _sweep_unfused(mode, low, S, source, dev, tdt, groups_per_batch):
         m = nb * per
         out = store[:P * m * 8].view(P, m, 8)                  # (the planes of a short last batch stay contiguous)
         E.trace_device(low, rays[:m], sel, out=out)
-        for a, t in zip(arrays, mode.plane(out[0] if P == 1 else out, per, b0, nb)):
+        for a, t in zip(arrays, _plane(mode, out[0] if P == 1 else out, per, b0)):
             a[b0:b0 + nb] = t.cpu().numpy()
     torch.cuda.synchronize(dev)
     return arrays, time.perf_counter() - t0, {}
@@ -620,10 +696,10 @@ def _sweep_fused(mode, low, S, source, devs, groups_per_batch):
     head = source.head()
     nf, nw, per = source.nf, source.nw, source.per
     groups_per_batch, bounds, launches = _sweep_plan(nf, nw, per, len(devs), groups_per_batch, mode.ncols,
-                                                     getattr(mode, "group_doubles", None))
+                                                     mode.group_doubles)
     work = []          # per device: its groups, the mode's outputs and argument tail, an event pair, its stream
     for (g0, g1), dev in zip(bounds, devs):
-        outputs, tail = mode.shard(dev, per, g0, max(g1 - g0, 1), groups_per_batch)
+        outputs, tail = _shard(mode, dev, per, g0, max(g1 - g0, 1), groups_per_batch)
         ev = (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
         work.append((dev, g1 - g0, outputs, tail, ev, torch.cuda.current_stream(dev)))
     for dev in devs:
@@ -667,6 +743,25 @@ def _bins(bins):
     return int(nx), int(ny)
 
 
+def _four(name, value, lead, text="(n_fields, n_wavelengths, 4)"):
+    """``value`` as the C-contiguous float64 table ``name`` (windows, params) of shape lead + (4,), which the refusal
+    calls ``text``."""
+    value = np.ascontiguousarray(value, dtype=np.float64)
+    if value.shape != tuple(lead) + (4,):
+        raise ValueError(f"{name} must have shape {text}")
+    return value
+
+
+def _plane_table(name, value, ngroups):
+    """The ``windows`` or ``params`` (n_groups, 4) of a plane call that reads them on the device: a torch tensor as it
+    is, anything else as a float64 array."""
+    if not hasattr(value, "data_ptr"):
+        value = np.array(value, dtype=np.float64)
+    if tuple(value.shape) != (ngroups, 4):
+        raise ValueError(name + " must have shape (n_groups, 4)")
+    return value
+
+
 def image_windows(centers, half_widths, bins):
     """Windows (..., 4) float64 {x_lo, y_lo, x_scale, y_scale} of spot images with ``bins`` (an int, or (nx, ny))
     bins: ``centers`` (..., 2) -- or (..., 3), the z ignored, as ``summary["centroid"]`` -- and ``half_widths``,
@@ -708,28 +803,9 @@ def spot_image_raw(plane, group_size, windows, bins, stream=None):
     counts of the rays' (x, y) in ``bins`` (an int, or (nx, ny)) bins of its window, ``windows`` (n_groups, 4) as
     :func:`image_windows` gives them.  Returns (image (n_groups, ny, nx), outside (n_groups,)), torch int32: a ray
     with finite x and y lands in exactly one bin or in ``outside``; the others are not counted."""
-    import torch
     nx, ny = _bins(bins)
-    n = plane.shape[0]
-    if n % group_size:
-        raise ValueError("plane length must be a multiple of group_size")
-    ngroups = n // group_size
-    if torch.is_tensor(windows):
-        w = windows.to(device=plane.device, dtype=torch.float64).contiguous()
-    else:
-        w = torch.from_numpy(np.array(windows, dtype=np.float64)).to(plane.device)
-    if tuple(w.shape) != (ngroups, 4):
-        raise ValueError("windows must have shape (n_groups, 4)")
-    plane = plane.contiguous()
-    image = torch.empty((ngroups, ny, nx), dtype=torch.int32, device=plane.device)
-    outside = torch.empty((ngroups,), dtype=torch.int32, device=plane.device)
-    if stream is None:
-        stream = torch.cuda.current_stream(plane.device).cuda_stream
-    C.check(C.lib().rtpb_spot_image(plane.device.index or 0,
-                                    C.RTPB_F64 if plane.dtype == torch.float64 else C.RTPB_F32, plane.data_ptr(),
-                                    group_size, ngroups, w.data_ptr(), nx, ny, image.data_ptr(), outside.data_ptr(),
-                                    stream))
-    return image, outside
+    windows = _plane_table("windows", windows, plane.shape[0] // group_size)
+    return _plane(_image_mode(windows, nx, ny), plane, group_size, stream=stream)
 
 
 def auto_image_windows(summary, bins, sigmas=4.0):
@@ -759,47 +835,34 @@ def image_sweep(system, initial_material, final_material, field_points, waveleng
     count for the spot statistics but fall outside the window -- and ``count`` = image.sum + outside, both
     (n_fields, n_wavelengths) int64, ``windows``, and ``x_edges`` (..., nx + 1) / ``y_edges`` (..., ny + 1), the bin
     edges lo + i / scale; the timing dict has :func:`spot_sweep`'s shape and covers the image pass alone."""
+    return _image_sweep(system, initial_material, final_material,
+                        _fan_source(field_points, wavelengths, theta_max, n_thetas, nphis, center_ray), bins, windows,
+                        sigmas, device, dtype, groups_per_batch, fused, devices)
+
+
+def _image_sweep(system, initial_material, final_material, source, bins, windows, sigmas, *sweep_args):
+    """What the two image sweeps share once the source exists; ``sweep_args`` are :func:`_sweep`'s after the source,
+    for the spot pass that chooses the windows as for the image pass."""
     nx, ny = _bins(bins)
     if windows is None:
-        spot, _ = spot_sweep(system, initial_material, final_material, field_points, wavelengths, theta_max,
-                             n_thetas, nphis, center_ray=center_ray, device=device, dtype=dtype,
-                             groups_per_batch=groups_per_batch, fused=fused, devices=devices)
+        spot, _ = _sweep(_SPOT, system, initial_material, final_material, source, *sweep_args)
         windows = auto_image_windows(spot, (nx, ny), sigmas)
-    windows = np.ascontiguousarray(windows, dtype=np.float64)
-    field_points, wavelengths = _grid(field_points, wavelengths)
-    if windows.shape != (field_points.shape[0], wavelengths.size, 4):
-        raise ValueError("windows must have shape (n_fields, n_wavelengths, 4)")
-    return _sweep(_image_mode(windows, nx, ny), system, initial_material, final_material,
-                  _fan_source(field_points, wavelengths, theta_max, n_thetas, nphis, center_ray), device, dtype,
-                  groups_per_batch, fused, devices)
+    return _sweep(_image_mode(_four("windows", windows, source.shape), nx, ny), system, initial_material,
+                  final_material, source, *sweep_args)
 
 
 def _image_mode(windows, nx, ny):
-    """The image sweep as the drivers see it (:func:`_stats_mode`): ``rtpb_image_sweep`` fused, ``spot_image_raw``
-    per plane, no workspace; per device the shard's images and outside counts.  ``windows`` is C-contiguous
-    (n_fields, n_wavelengths, 4) float64, so the windows of groups [b0, b1) are contiguous in it."""
-    win = windows.reshape(-1, 4)
-
-    def shard(dev, per, g0, n, batch):
-        import torch
-        image = torch.empty((n, ny, nx), dtype=torch.int32, device=dev)
-        outside = torch.empty((n,), dtype=torch.int32, device=dev)
-        return (image, outside), lambda b0, b1: (win[b0:b1].ctypes.data, nx, ny, image[b0 - g0:b1 - g0].data_ptr(),
-                                                 outside[b0 - g0:b1 - g0].data_ptr())
-
-    def finish(nf, nw, image, outside):
-        image = image.reshape(nf, nw, ny, nx)
-        outside = outside.reshape(nf, nw).astype(np.int64)
+    """The image sweep as the drivers see it: counters, no workspace, the windows read on the device by the plane
+    call.  ``windows`` is C-contiguous (..., 4) float64, so the windows of groups [b0, b1) are contiguous in it."""
+    def finish(shape, image, outside):
+        image = image.reshape(shape + (ny, nx))
+        outside = outside.reshape(shape).astype(np.int64)
         xe, ye = image_edges(windows, (nx, ny))
         return {"image": image, "outside": outside, "count": image.sum(axis=(-2, -1), dtype=np.int64) + outside,
                 "windows": windows, "x_edges": xe, "y_edges": ye}
 
-    return SimpleNamespace(
-        entry="rtpb_image_sweep", ncols=None, shard=shard, finish=finish,
-        # the counters, cleared and then added to (the rays never leave the registers)
-        hbm_bytes=lambda per, n: n * (ny * nx + 1) * 4 * 2,
-        host=lambda G: (np.zeros((G, ny, nx), dtype=np.int32), np.zeros(G, dtype=np.int32)),
-        plane=lambda out, per, b0, nb: spot_image_raw(out, per, win[b0:b0 + nb], (nx, ny)))
+    return _mode("rtpb_image_sweep", "rtpb_spot_image", (((ny, nx), np.int32), ((), np.int32)), finish,
+                 tables=(windows.reshape(-1, 4),), consts=(nx, ny), cleared=True, device_tables=True)
 
 
 def _energy_bins(bins):
@@ -852,29 +915,9 @@ def spot_energy_raw(plane, group_size, params, bins, stream=None):
     (hist (n_groups, 2, bins) int32, outside (n_groups, 2) int32, farthest (n_groups, 2) float64), torch: a ray with
     finite x and y lands in exactly one bin of each curve or in its ``outside``; ``farthest`` is the largest distance
     of each kind over those rays."""
-    import torch
     nr = _energy_bins(bins)
-    n = plane.shape[0]
-    if n % group_size:
-        raise ValueError("plane length must be a multiple of group_size")
-    ngroups = n // group_size
-    if torch.is_tensor(params):
-        p = params.to(device=plane.device, dtype=torch.float64).contiguous()
-    else:
-        p = torch.from_numpy(np.array(params, dtype=np.float64)).to(plane.device)
-    if tuple(p.shape) != (ngroups, 4):
-        raise ValueError("params must have shape (n_groups, 4)")
-    plane = plane.contiguous()
-    hist = torch.empty((ngroups, 2, nr), dtype=torch.int32, device=plane.device)
-    outside = torch.empty((ngroups, 2), dtype=torch.int32, device=plane.device)
-    farthest = torch.empty((ngroups, 2), dtype=torch.float64, device=plane.device)
-    if stream is None:
-        stream = torch.cuda.current_stream(plane.device).cuda_stream
-    C.check(C.lib().rtpb_spot_energy(plane.device.index or 0,
-                                     C.RTPB_F64 if plane.dtype == torch.float64 else C.RTPB_F32, plane.data_ptr(),
-                                     group_size, ngroups, p.data_ptr(), nr, hist.data_ptr(), outside.data_ptr(),
-                                     farthest.data_ptr(), stream))
-    return hist, outside, farthest
+    params = _plane_table("params", params, plane.shape[0] // group_size)
+    return _plane(_energy_mode(params, nr), plane, group_size, stream=stream)
 
 
 def summarize_energy(hist, outside, farthest, params):
@@ -934,48 +977,30 @@ def energy_sweep(system, initial_material, final_material, field_points, wavelen
     ``encircled`` / ``ensquared`` against ``radii``, ``count``, ``outside``, ``farthest`` (the largest radius and
     half-side of a counted ray: an r_max that holds everything), ``hist``, ``params``; :func:`energy_radius` reads
     EE50 / EE80 off it.  The timing dict has :func:`spot_sweep`'s shape and covers the energy pass alone."""
+    return _energy_sweep(system, initial_material, final_material,
+                         _fan_source(field_points, wavelengths, theta_max, n_thetas, nphis, center_ray), bins, params,
+                         sigmas, device, dtype, groups_per_batch, fused, devices)
+
+
+def _energy_sweep(system, initial_material, final_material, source, bins, params, sigmas, *sweep_args):
+    """What the two energy sweeps share once the source exists (:func:`_image_sweep`)."""
     nr = _energy_bins(bins)
     if params is None:
-        spot, _ = spot_sweep(system, initial_material, final_material, field_points, wavelengths, theta_max,
-                             n_thetas, nphis, center_ray=center_ray, device=device, dtype=dtype,
-                             groups_per_batch=groups_per_batch, fused=fused, devices=devices)
+        spot, _ = _sweep(_SPOT, system, initial_material, final_material, source, *sweep_args)
         params = auto_energy_params(spot, nr, sigmas)
-    params = np.ascontiguousarray(params, dtype=np.float64)
-    field_points, wavelengths = _grid(field_points, wavelengths)
-    if params.shape != (field_points.shape[0], wavelengths.size, 4):
-        raise ValueError("params must have shape (n_fields, n_wavelengths, 4)")
-    return _sweep(_energy_mode(params, nr), system, initial_material, final_material,
-                  _fan_source(field_points, wavelengths, theta_max, n_thetas, nphis, center_ray), device, dtype,
-                  groups_per_batch, fused, devices)
+    return _sweep(_energy_mode(_four("params", params, source.shape), nr), system, initial_material, final_material,
+                  source, *sweep_args)
 
 
 def _energy_mode(params, nr):
-    """The energy sweep as the drivers see it (:func:`_image_mode`): ``rtpb_energy_sweep`` fused,
-    ``spot_energy_raw`` per plane, no workspace; per device the shard's histograms, outside counts and maxima.
-    ``params`` is C-contiguous (n_fields, n_wavelengths, 4) float64, so the parameters of groups [b0, b1) are
-    contiguous in it."""
-    par = params.reshape(-1, 4)
+    """The energy sweep as the drivers see it (:func:`_image_mode`): counters and maxima, no workspace.  ``params``
+    is C-contiguous (..., 4) float64, so the parameters of groups [b0, b1) are contiguous in it."""
+    def finish(shape, hist, outside, farthest):
+        return summarize_energy(hist.reshape(shape + (2, nr)), outside.reshape(shape + (2,)),
+                                farthest.reshape(shape + (2,)), params)
 
-    def shard(dev, per, g0, n, batch):
-        import torch
-        hist = torch.empty((n, 2, nr), dtype=torch.int32, device=dev)
-        outside = torch.empty((n, 2), dtype=torch.int32, device=dev)
-        farthest = torch.empty((n, 2), dtype=torch.float64, device=dev)
-        return (hist, outside, farthest), lambda b0, b1: (par[b0:b1].ctypes.data, nr,
-                                                          hist[b0 - g0:b1 - g0].data_ptr(),
-                                                          outside[b0 - g0:b1 - g0].data_ptr(),
-                                                          farthest[b0 - g0:b1 - g0].data_ptr())
-
-    def finish(nf, nw, hist, outside, farthest):
-        return summarize_energy(hist.reshape(nf, nw, 2, nr), outside.reshape(nf, nw, 2),
-                                farthest.reshape(nf, nw, 2), params)
-
-    return SimpleNamespace(
-        entry="rtpb_energy_sweep", ncols=None, shard=shard, finish=finish,
-        # the counters and maxima, cleared and then added to (the rays never leave the registers)
-        hbm_bytes=lambda per, n: n * ((2 * nr + 2) * 4 + 2 * 8) * 2,
-        host=lambda G: (np.zeros((G, 2, nr), dtype=np.int32), np.zeros((G, 2), dtype=np.int32), np.zeros((G, 2))),
-        plane=lambda out, per, b0, nb: spot_energy_raw(out, per, par[b0:b0 + nb], nr))
+    return _mode("rtpb_energy_sweep", "rtpb_spot_energy", (((2, nr), np.int32), ((2,), np.int32), ((2,), np.float64)),
+                 finish, tables=(params.reshape(-1, 4),), consts=(nr,), cleared=True, device_tables=True)
 
 
 def collimated_spot_sweep(system, initial_material, final_material, normals, wavelengths, displacement_max, n_disps,
@@ -1014,18 +1039,9 @@ def collimated_image_sweep(system, initial_material, final_material, normals, wa
     """Spot-diagram images of :func:`collimated_spot_sweep`'s beams: :func:`image_sweep` with that source
     (``rtpb_image_sweep_collimated``, or unfused through ``rtpb_spot_image``; identical counts).  With
     ``windows=None`` a :func:`collimated_spot_sweep` of the same beams chooses them."""
-    nx, ny = _bins(bins)
-    beam = (normals, wavelengths, displacement_max, n_disps, nphis, phi_start, pt)
-    if windows is None:
-        spot, _ = collimated_spot_sweep(system, initial_material, final_material, *beam, device=device, dtype=dtype,
-                                        groups_per_batch=groups_per_batch, fused=fused, devices=devices)
-        windows = auto_image_windows(spot, (nx, ny), sigmas)
-    windows = np.ascontiguousarray(windows, dtype=np.float64)
-    source = _beam_source(*beam)
-    if windows.shape != (source.nf, source.nw, 4):
-        raise ValueError("windows must have shape (n_fields, n_wavelengths, 4)")
-    return _sweep(_image_mode(windows, nx, ny), system, initial_material, final_material, source, device, dtype,
-                  groups_per_batch, fused, devices)
+    return _image_sweep(system, initial_material, final_material,
+                        _beam_source(normals, wavelengths, displacement_max, n_disps, nphis, phi_start, pt), bins,
+                        windows, sigmas, device, dtype, groups_per_batch, fused, devices)
 
 
 def collimated_energy_sweep(system, initial_material, final_material, normals, wavelengths, displacement_max, n_disps,
@@ -1034,18 +1050,9 @@ def collimated_energy_sweep(system, initial_material, final_material, normals, w
     """Encircled and ensquared energy of :func:`collimated_spot_sweep`'s beams: :func:`energy_sweep` with that source
     (``rtpb_energy_sweep_collimated``, or unfused through ``rtpb_spot_energy``; identical results).  With
     ``params=None`` a :func:`collimated_spot_sweep` of the same beams chooses them."""
-    nr = _energy_bins(bins)
-    beam = (normals, wavelengths, displacement_max, n_disps, nphis, phi_start, pt)
-    if params is None:
-        spot, _ = collimated_spot_sweep(system, initial_material, final_material, *beam, device=device, dtype=dtype,
-                                        groups_per_batch=groups_per_batch, fused=fused, devices=devices)
-        params = auto_energy_params(spot, nr, sigmas)
-    params = np.ascontiguousarray(params, dtype=np.float64)
-    source = _beam_source(*beam)
-    if params.shape != (source.nf, source.nw, 4):
-        raise ValueError("params must have shape (n_fields, n_wavelengths, 4)")
-    return _sweep(_energy_mode(params, nr), system, initial_material, final_material, source, device, dtype,
-                  groups_per_batch, fused, devices)
+    return _energy_sweep(system, initial_material, final_material,
+                         _beam_source(normals, wavelengths, displacement_max, n_disps, nphis, phi_start, pt), bins,
+                         params, sigmas, device, dtype, groups_per_batch, fused, devices)
 
 
 def collimated_wavefront_refs(system, initial_material, final_material, normals, wavelengths, pt=(0, 0, 0),
@@ -1056,16 +1063,11 @@ def collimated_wavefront_refs(system, initial_material, final_material, normals,
     also ``groups_per_batch``, ``devices``) describes; d0 and p0 the final direction and phase of the beam's chief
     ray, ``get_collimated_rays(pt, 0, 1, wavelength, normal=normal)``, traced through the ordinary
     ``planes='final'`` path; kf = final_material.n(wavelength) / wavelength."""
-    from .raytrace import get_collimated_rays
-    normals, pts = _beams(normals, pt)
-    wavelengths = np.atleast_1d(np.asarray(wavelengths, dtype=float))
-    if spot_summary is None:
-        spot_summary, _ = collimated_spot_sweep(system, initial_material, final_material, normals, wavelengths,
-                                                pt=pts, device=device, **beam_kw)
-    chief = np.concatenate([get_collimated_rays(p, 0, 1, w, normal=n) for p, n in zip(pts, normals)
-                            for w in wavelengths])
-    return _refs_from(system, initial_material, final_material, normals.shape[0], wavelengths, spot_summary, chief,
-                      device)
+    sweep_kw = _sweep_kw(beam_kw)
+    source = None if spot_summary is not None else _beam_source(normals, wavelengths, pt=pt,
+                                                               **{"nphis": 1, "phi_start": 0., **beam_kw})
+    return _refs(system, initial_material, final_material, source, _beam_source(normals, wavelengths, 0, 1, 1, 0., pt),
+                 spot_summary, device, *sweep_kw)
 
 
 def collimated_wavefront_sweep(system, initial_material, final_material, normals, wavelengths, displacement_max,
@@ -1074,18 +1076,9 @@ def collimated_wavefront_sweep(system, initial_material, final_material, normals
     """Wavefront analysis of :func:`collimated_spot_sweep`'s beams: :func:`wavefront_sweep` with that source
     (``rtpb_wavefront_sweep_collimated``, or unfused through ``rtpb_wavefront_stats``; bit-identical).  With
     ``refs=None`` :func:`collimated_wavefront_refs` builds the references.  float64 only."""
-    if dtype not in ("float64", np.float64):
-        raise ValueError("wavefront_sweep is float64 only: a float32 phase of 1e4 ... 1e7 rad has an ulp of a "
-                         "milliradian to a radian")
-    source = _beam_source(normals, wavelengths, displacement_max, n_disps, nphis, phi_start, pt)
-    if refs is None:
-        refs = collimated_wavefront_refs(system, initial_material, final_material, source.normals,
-                                         source.wavelengths, pt=source.pts, device=device,
-                                         displacement_max=displacement_max, n_disps=n_disps, nphis=nphis,
-                                         phi_start=phi_start, groups_per_batch=groups_per_batch, devices=devices)
-    refs = _wave_refs(refs, (source.nf, source.nw, 8))
-    return _sweep(_wave_mode(refs), system, initial_material, final_material, source, device, "float64",
-                  groups_per_batch, fused, devices)
+    return _wave_sweep(system, initial_material, final_material,
+                       _beam_source(normals, wavelengths, displacement_max, n_disps, nphis, phi_start, pt), device,
+                       refs, groups_per_batch, fused, devices, dtype)
 
 
 def wavefront_map_windows(far_e, bins):
@@ -1126,33 +1119,11 @@ def wavefront_map_raw(plane, group_size, refs, windows, bins, q_bits, w_lim, str
     in exactly one cell -- where ``sum`` gains rint(w * 2^q_bits), w its OPD in waves -- or in ``outside`` (not in
     the window) or in ``clipped`` (inside, |w| > w_lim); ``farthest`` is the largest max(|ex|, |ey|) and the largest
     |w| over all of them.  float64 only."""
-    import torch
-    if plane.dtype != torch.float64:
-        raise ValueError("wavefront maps need a float64 plane: a float32 phase of 1e4 ... 1e7 rad has an ulp of a "
-                         "milliradian to a radian")
+    _phase_needs_float64("wavefront maps need a float64 plane", plane=plane)
     nx, ny = _bins(bins)
-    n = plane.shape[0]
-    if n % group_size:
-        raise ValueError("plane length must be a multiple of group_size")
-    ngroups = n // group_size
-    refs = _wave_refs(refs, (ngroups, 8))
-    windows = np.ascontiguousarray(windows, dtype=np.float64)
-    if windows.shape != (ngroups, 4):
-        raise ValueError("windows must have shape (n_groups, 4)")
-    plane = plane.contiguous()
-    dev = plane.device
-    count = torch.empty((ngroups, ny, nx), dtype=torch.int32, device=dev)
-    total = torch.empty((ngroups, ny, nx), dtype=torch.int64, device=dev)
-    outside = torch.empty((ngroups,), dtype=torch.int32, device=dev)
-    clipped = torch.empty((ngroups,), dtype=torch.int32, device=dev)
-    farthest = torch.empty((ngroups, 2), dtype=torch.float64, device=dev)
-    if stream is None:
-        stream = torch.cuda.current_stream(dev).cuda_stream
-    C.check(C.lib().rtpb_wavefront_map(dev.index or 0, C.RTPB_F64, plane.data_ptr(), group_size, ngroups,
-                                       refs.ctypes.data, windows.ctypes.data, nx, ny, int(q_bits), float(w_lim),
-                                       count.data_ptr(), total.data_ptr(), outside.data_ptr(), clipped.data_ptr(),
-                                       farthest.data_ptr(), stream))
-    return count, total, outside, clipped, farthest
+    ngroups = plane.shape[0] // group_size
+    return _plane(_wavemap_mode(_wave_refs(refs, (ngroups, 8)), _four("windows", windows, (ngroups,), "(n_groups, 4)"),
+                                nx, ny, int(q_bits), float(w_lim)), plane, group_size, stream=stream)
 
 
 def summarize_wavefront_map(count, sum, outside, clipped, farthest, windows, q_bits):
@@ -1277,48 +1248,31 @@ def zernike_fit(summary, n_terms=15, radius=None, center=(0, 0)):
 
 def _wavemap_mode(refs, windows, nx, ny, q_bits, w_lim):
     """The wavefront map sweep as the drivers see it: :func:`_image_mode` with :func:`_wave_mode`'s references --
-    ``rtpb_wavefront_map_sweep`` fused, ``wavefront_map_raw`` per plane, no workspace; per device the shard's five
-    outputs.  ``refs`` (n_fields, n_wavelengths, 8) and ``windows`` (n_fields, n_wavelengths, 4) are C-contiguous
-    float64, so those of groups [b0, b1) are contiguous in them."""
-    ref, win = refs.reshape(-1, 8), windows.reshape(-1, 4)
-
-    def shard(dev, per, g0, n, batch):
-        import torch
-        count = torch.empty((n, ny, nx), dtype=torch.int32, device=dev)
-        total = torch.empty((n, ny, nx), dtype=torch.int64, device=dev)
-        outside = torch.empty((n,), dtype=torch.int32, device=dev)
-        clipped = torch.empty((n,), dtype=torch.int32, device=dev)
-        farthest = torch.empty((n, 2), dtype=torch.float64, device=dev)
-        outputs = (count, total, outside, clipped, farthest)
-        return outputs, lambda b0, b1: (ref[b0:b1].ctypes.data, win[b0:b1].ctypes.data, nx, ny, q_bits, w_lim) + \
-            tuple(t[b0 - g0:b1 - g0].data_ptr() for t in outputs)
-
-    def finish(nf, nw, count, total, outside, clipped, farthest):
-        out = summarize_wavefront_map(count.reshape(nf, nw, ny, nx), total.reshape(nf, nw, ny, nx),
-                                      outside.reshape(nf, nw), clipped.reshape(nf, nw), farthest.reshape(nf, nw, 2),
+    cells, counters and maxima, no workspace.  ``refs`` (..., 8) and ``windows`` (..., 4) are C-contiguous float64,
+    so those of groups [b0, b1) are contiguous in them."""
+    def finish(shape, count, total, outside, clipped, farthest):
+        out = summarize_wavefront_map(count.reshape(shape + (ny, nx)), total.reshape(shape + (ny, nx)),
+                                      outside.reshape(shape), clipped.reshape(shape), farthest.reshape(shape + (2,)),
                                       windows, q_bits)
         out["refs"], out["w_lim"] = refs, w_lim
         return out
 
-    return SimpleNamespace(
-        entry="rtpb_wavefront_map_sweep", ncols=None, shard=shard, finish=finish,
-        # the cells, counters and maxima, cleared and then added to (the rays never leave the registers)
-        hbm_bytes=lambda per, n: n * (ny * nx * 12 + 2 * 4 + 2 * 8) * 2,
-        host=lambda G: (np.zeros((G, ny, nx), dtype=np.int32), np.zeros((G, ny, nx), dtype=np.int64),
-                        np.zeros(G, dtype=np.int32), np.zeros(G, dtype=np.int32), np.zeros((G, 2))),
-        plane=lambda out, per, b0, nb: wavefront_map_raw(out, per, ref[b0:b0 + nb], win[b0:b0 + nb], (nx, ny), q_bits,
-                                                         w_lim))
+    return _mode("rtpb_wavefront_map_sweep", "rtpb_wavefront_map",
+                 (((ny, nx), np.int32), ((ny, nx), np.int64), ((), np.int32), ((), np.int32), ((2,), np.float64)),
+                 finish, tables=(refs.reshape(-1, 8), windows.reshape(-1, 4)), consts=(nx, ny, q_bits, w_lim),
+                 cleared=True)
 
 
 def _wavemap_sweep(system, initial_material, final_material, source, refs, bins, windows, w_lim, q_bits, device,
                    groups_per_batch, fused, devices, dtype):
-    """What the two map sweeps share once the source and the references exist: the first pass for the defaults, the
+    """What the two map sweeps share once the source exists: the references, the first pass for the defaults, the
     choice of q_bits, the sweep."""
-    if dtype not in ("float64", np.float64):
-        raise ValueError("wavefront_map_sweep is float64 only: a float32 phase of 1e4 ... 1e7 rad has an ulp of a "
-                         "milliradian to a radian")
+    _phase_needs_float64("wavefront_map_sweep is float64 only", dtype)
     nx, ny = _bins(bins)
-    shape = (source.nf, source.nw)
+    shape = source.shape
+    if refs is None:
+        refs = _refs(system, initial_material, final_material, source, source.chief(), None, device,
+                     groups_per_batch=groups_per_batch, devices=devices)
     refs = _wave_refs(refs, shape + (8,))
     run = lambda mode: _sweep(mode, system, initial_material, final_material, source, device, "float64",  # noqa: E731
                               groups_per_batch, fused, devices)
@@ -1330,9 +1284,7 @@ def _wavemap_sweep(system, initial_material, final_material, source, refs, bins,
             windows = wavefront_map_windows(first["farthest"][..., 0], (nx, ny))
         if w_lim is None:
             w_lim = max(1.0, float(first["farthest"][..., 1].max()))
-    windows = np.ascontiguousarray(windows, dtype=np.float64)
-    if windows.shape != shape + (4,):
-        raise ValueError("windows must have shape (n_fields, n_wavelengths, 4)")
+    windows = _four("windows", windows, shape)
     w_lim = float(w_lim)
     if q_bits is None:
         q_bits = wavefront_map_q_bits(source.per, w_lim)
@@ -1362,11 +1314,6 @@ def wavefront_map_sweep(system, initial_material, final_material, field_points, 
     Returns (summary, timing): :func:`summarize_wavefront_map`'s dict with arrays shaped (n_fields, n_wavelengths,
     ...), plus ``refs`` and ``w_lim``; :func:`zernike_fit` fits Zernike coefficients to it.  The timing dict has
     :func:`spot_sweep`'s shape and covers the map pass alone."""
-    field_points, wavelengths = _grid(field_points, wavelengths)
-    if refs is None:
-        refs = wavefront_refs(system, initial_material, final_material, field_points, wavelengths,
-                              center_ray=center_ray, device=device, theta_max=theta_max, n_thetas=n_thetas,
-                              nphis=nphis, groups_per_batch=groups_per_batch, devices=devices)
     return _wavemap_sweep(system, initial_material, final_material,
                           _fan_source(field_points, wavelengths, theta_max, n_thetas, nphis, center_ray), refs, bins,
                           windows, w_lim, q_bits, device, groups_per_batch, fused, devices, dtype)
@@ -1380,14 +1327,9 @@ def collimated_wavefront_map_sweep(system, initial_material, final_material, nor
     (``rtpb_wavefront_map_sweep_collimated``, or unfused through ``rtpb_wavefront_map``; identical arrays).  With
     ``refs=None`` :func:`collimated_wavefront_refs` builds the references; with ``windows=None`` or ``w_lim=None`` a
     first pass chooses them, so the rays are traced twice."""
-    source = _beam_source(normals, wavelengths, displacement_max, n_disps, nphis, phi_start, pt)
-    if refs is None:
-        refs = collimated_wavefront_refs(system, initial_material, final_material, source.normals,
-                                         source.wavelengths, pt=source.pts, device=device,
-                                         displacement_max=displacement_max, n_disps=n_disps, nphis=nphis,
-                                         phi_start=phi_start, groups_per_batch=groups_per_batch, devices=devices)
-    return _wavemap_sweep(system, initial_material, final_material, source, refs, bins, windows, w_lim, q_bits, device,
-                          groups_per_batch, fused, devices, dtype)
+    return _wavemap_sweep(system, initial_material, final_material,
+                          _beam_source(normals, wavelengths, displacement_max, n_disps, nphis, phi_start, pt), refs,
+                          bins, windows, w_lim, q_bits, device, groups_per_batch, fused, devices, dtype)
 
 
 def _psf_sides(n, ny=None):
@@ -1445,36 +1387,19 @@ def huygens_psf_raw(plane, group_size, refs, windows, nx, ny, weights=None, stre
     Each pixel is summed in an order fixed by (group_size, nx, ny): two calls give the same bits, and a group gives
     the same bits whichever groups share its call.  The cost is group_size * nx * ny
     complex exponentials per group.  float64 only, as the wavefront statistics."""
-    import torch
-    if plane.dtype != torch.float64:
-        raise ValueError("the Huygens PSF needs a float64 plane: a float32 phase of 1e4 ... 1e7 rad has an ulp of a "
-                         "milliradian to a radian")
+    _phase_needs_float64("the Huygens PSF needs a float64 plane", plane=plane)
     nx, ny = _psf_sides(nx, ny)
-    n = plane.shape[0]
-    if n % group_size:
-        raise ValueError("plane length must be a multiple of group_size")
-    ngroups = n // group_size
+    ngroups = plane.shape[0] // group_size
     refs = _wave_refs(refs, (ngroups, 8))
     win = np.asarray(windows, dtype=np.float64)
     if win.shape not in ((ngroups, 4), (1, 4)):
         raise ValueError("windows must have shape (n_groups, 4) or (1, 4)")
-    win = np.ascontiguousarray(np.broadcast_to(win, (ngroups, 4)))
     if weights is not None:
-        if not torch.is_tensor(weights):
-            weights = torch.from_numpy(np.ascontiguousarray(weights, dtype=np.float64))
-        weights = weights.to(device=plane.device, dtype=torch.float64).contiguous()
+        if not hasattr(weights, "data_ptr"):
+            weights = np.ascontiguousarray(weights, dtype=np.float64)
         if tuple(weights.shape) != (group_size,):
             raise ValueError("weights must have shape (group_size,)")
-    plane = plane.contiguous()
-    field = torch.empty((ngroups, ny, nx), dtype=torch.complex128, device=plane.device)
-    norm = torch.empty((ngroups,), dtype=torch.float64, device=plane.device)
-    if stream is None:
-        stream = torch.cuda.current_stream(plane.device).cuda_stream
-    C.check(C.lib().rtpb_huygens_psf(plane.device.index or 0, C.RTPB_F64, plane.data_ptr(), group_size, ngroups,
-                                     refs.ctypes.data, win.ctypes.data,
-                                     None if weights is None else weights.data_ptr(), nx, ny, field.data_ptr(),
-                                     norm.data_ptr(), stream))
-    return field, norm
+    return _plane(_psf_mode(refs, win, nx, ny, weights), plane, group_size, stream=stream)
 
 
 def summarize_psf(field, norm, windows):
@@ -1538,25 +1463,24 @@ def psf_mtf(psf, sx, sy):
 
 
 def _psf_mode(refs, windows, nx, ny, weights):
-    """The Huygens PSF as the unfused driver sees it (:func:`_wave_mode`): :func:`huygens_psf_raw` on each batch's
-    final plane.  There is no fused entry point: the field is rays x pixels work on a plane that is read once.
-    ``refs`` is C-contiguous (n_fields, n_wavelengths, 8) and ``windows`` broadcasts to (n_fields, n_wavelengths, 4);
-    ``weights`` is None or (rays per group,) float64, uploaded once."""
-    ref = refs.reshape(-1, 8)
-    win = np.ascontiguousarray(np.broadcast_to(windows, refs.shape[:-1] + (4,))).reshape(-1, 4)
-    held = []
+    """The Huygens PSF as the unfused driver sees it: ``rtpb_huygens_psf`` on each batch's final plane.  There is no
+    fused entry point: the field is rays x pixels work on a plane that is read once.  ``refs`` is C-contiguous
+    (..., 8) and ``windows`` broadcasts to (..., 4); ``weights`` is None or (rays per group,) float64, NumPy or torch:
+    a per-call constant on the plane's device, uploaded once."""
+    win = np.ascontiguousarray(np.broadcast_to(windows, refs.shape[:-1] + (4,)))
+    held = {}
 
-    def plane(out, per, b0, nb):
-        if weights is not None and not held:
+    def on_device(dev):
+        if weights is not None and dev not in held:
             import torch
-            held.append(torch.from_numpy(weights).to(out.device))
-        return huygens_psf_raw(out, per, ref[b0:b0 + nb], win[b0:b0 + nb], nx, ny, held[0] if held else None)
+            w = weights if torch.is_tensor(weights) else torch.from_numpy(weights)
+            held[dev] = w.to(device=dev, dtype=torch.float64).contiguous()
+        return held.get(dev)
 
-    return SimpleNamespace(
-        entry=None, ncols=None, plane=plane,
-        host=lambda G: (np.zeros((G, ny, nx), dtype=np.complex128), np.zeros(G)),
-        finish=lambda nf, nw, field, norm: summarize_psf(field.reshape(nf, nw, ny, nx), norm.reshape(nf, nw),
-                                                         win.reshape(nf, nw, 4)))
+    return _mode(None, "rtpb_huygens_psf", (((ny, nx), np.complex128), ((), np.float64)),
+                 lambda shape, field, norm: summarize_psf(field.reshape(shape + (ny, nx)), norm.reshape(shape),
+                                                          win.reshape(shape + (4,))),
+                 tables=(refs.reshape(-1, 8), win.reshape(-1, 4)), consts=(on_device, nx, ny))
 
 
 def _psf_refuse(dtype, fused, devices):
@@ -1565,9 +1489,7 @@ def _psf_refuse(dtype, fused, devices):
         raise ValueError("the Huygens PSF has no fused variant: it runs generation -> trace -> rtpb_huygens_psf")
     if devices is not None:
         raise ValueError("the Huygens PSF runs on one device: devices= needs a fused sweep, and there is none")
-    if dtype not in ("float64", np.float64):
-        raise ValueError("the Huygens PSF is float64 only: a float32 phase of 1e4 ... 1e7 rad has an ulp of a "
-                         "milliradian to a radian")
+    _phase_needs_float64("the Huygens PSF is float64 only", dtype)
 
 
 def _psf_weights(weights, area, per):
@@ -1586,7 +1508,9 @@ def _psf_weights(weights, area, per):
 def _psf_sweep(system, initial_material, final_material, source, refs, half_width, n, weights, device,
                groups_per_batch):
     nx, ny = _psf_sides(n)
-    refs = _wave_refs(refs, (source.nf, source.nw, 8))
+    if refs is None:
+        refs = _refs(system, initial_material, final_material, source, source.chief(), None, device)
+    refs = _wave_refs(refs, source.shape + (8,))
     windows = psf_windows(half_width, nx, ny)
     try:
         np.broadcast_to(windows, refs.shape[:-1] + (4,))
@@ -1624,13 +1548,8 @@ def huygens_psf(system, initial_material, final_material, field_points, waveleng
     batch's field stays under 1 GiB); any value gives the same bits.  There is no fused variant and no multi-device
     split: ``fused=True`` or ``devices=`` raises ``ValueError``, and so does a ``dtype`` other than float64."""
     _psf_refuse(dtype, fused, devices)
-    field_points, wavelengths = _grid(field_points, wavelengths)
     source = _fan_source(field_points, wavelengths, theta_max, n_thetas, nphis, center_ray)
     weights = _psf_weights(weights, lambda: fan_area_weights(theta_max, n_thetas, nphis), source.per)
-    if refs is None:
-        refs = wavefront_refs(system, initial_material, final_material, field_points, wavelengths,
-                              center_ray=center_ray, device=device, theta_max=theta_max, n_thetas=n_thetas,
-                              nphis=nphis)
     return _psf_sweep(system, initial_material, final_material, source, refs, half_width, n, weights, device,
                       groups_per_batch)
 
@@ -1644,11 +1563,6 @@ def collimated_huygens_psf(system, initial_material, final_material, normals, wa
     _psf_refuse(dtype, fused, devices)
     source = _beam_source(normals, wavelengths, displacement_max, n_disps, nphis, phi_start, pt)
     weights = _psf_weights(weights, lambda: beam_area_weights(displacement_max, n_disps, nphis), source.per)
-    if refs is None:
-        refs = collimated_wavefront_refs(system, initial_material, final_material, source.normals,
-                                         source.wavelengths, pt=source.pts, device=device,
-                                         displacement_max=displacement_max, n_disps=n_disps, nphis=nphis,
-                                         phi_start=phi_start)
     return _psf_sweep(system, initial_material, final_material, source, refs, half_width, n, weights, device,
                       groups_per_batch)
 
@@ -1700,24 +1614,11 @@ def footprint_stats_raw(history, group_size, frames, stream=None):
     ray's row in plane 2 s + 1 and B its row in plane 2 s + 2: the rays whose A position is finite (they arrive), those
     whose B position is finite too (they pass), the largest rho2 = u u + v v of either set and the extremes of u and v
     of the passing rays, (u, v) being A's position in the surface's frame.  A float32 history raises ``ValueError``."""
-    import torch
     _float64_only("footprint_stats_raw", history, frames)
     if history.dim() != 3 or history.shape[0] % 2 != 1 or history.shape[0] < 3 or history.shape[2] != 8:
         raise ValueError("history must have shape (1 + 2 S, N, 8)")
-    S, n = (history.shape[0] - 1) // 2, history.shape[1]
-    if n % group_size:
-        raise ValueError("history length must be a multiple of group_size")
-    ngroups = n // group_size
-    frames = _foot_frames(frames, S)
-    history = history.contiguous()
-    ws = torch.empty(ngroups * -(-group_size // 256) * S * 8, dtype=torch.float64, device=history.device)
-    stats = torch.empty((ngroups, S, 8), dtype=torch.float64, device=history.device)
-    if stream is None:
-        stream = torch.cuda.current_stream(history.device).cuda_stream
-    C.check(C.lib().rtpb_footprint_stats(history.device.index or 0, C.RTPB_F64, history.data_ptr(), group_size,
-                                         ngroups, S, frames.ctypes.data, ws.data_ptr(), ws.numel(), stats.data_ptr(),
-                                         stream))
-    return stats
+    frames = _foot_frames(frames, (history.shape[0] - 1) // 2)
+    return _plane(_foot_mode(frames, group_size, None), history, group_size, stream=stream)[0]
 
 
 def summarize_footprint(raw, rays_per_group, aperture_rads):
@@ -1768,29 +1669,16 @@ def footprint_stats(history, group_size, frames, aperture_rads):
 
 
 def _foot_mode(frames, per, aperture_rads):
-    """The footprint sweep as the drivers see it (:func:`_stats_mode`): ``rtpb_footprint_sweep`` fused; unfused the
-    whole history of a batch (``planes='all'``) reduced by ``rtpb_footprint_stats``.  ``frames`` is C-contiguous
-    (S, 9) float64.  Per device: a batch's workspace (one partial per block of two tiles, S x 8 doubles each) and the
-    shard's statistics."""
+    """The footprint sweep as the drivers see it: unfused, the whole history of a batch (``planes='all'``) is reduced.
+    ``frames``, C-contiguous (S, 9) float64, and S are constants of both calls, in either order; the fused call keeps
+    one partial per block of two tiles, S x 8 doubles each."""
     S = frames.shape[0]
     blocks = -(-(-(-per // 256)) // 2)
-
-    def shard(dev, per, g0, n, batch):
-        import torch
-        ws = torch.empty(batch * blocks * S * 8, dtype=torch.float64, device=dev)
-        stats = torch.empty((n, S, 8), dtype=torch.float64, device=dev)
-        return (stats,), lambda b0, b1: (frames.ctypes.data, S, ws.data_ptr(), ws.numel(),
-                                         stats[b0 - g0:b1 - g0].data_ptr())
-
-    return SimpleNamespace(
-        entry="rtpb_footprint_sweep", ncols=None, shard=shard, planes="all",
-        # what a group adds to a batch's device memory, in doubles: its partials and its statistics
-        group_doubles=(blocks + 1) * S * 8,
-        # the block partials written and read back, and the statistics (the rays never leave the registers)
-        hbm_bytes=lambda per, n: n * blocks * S * 8 * 8 * 2 + n * S * 8 * 8,
-        host=lambda G: (np.zeros((G, S, 8)),),
-        plane=lambda out, per, b0, nb: (footprint_stats_raw(out, per, frames),),
-        finish=lambda nf, nw, raw: summarize_footprint(raw.reshape(nf, nw, S, 8), per, aperture_rads))
+    return _mode("rtpb_footprint_sweep", "rtpb_footprint_stats", (((S, 8), np.float64),),
+                 lambda shape, raw: summarize_footprint(raw.reshape(shape + (S, 8)), per, aperture_rads),
+                 consts=(frames, S), plane_consts=(S, frames), ws=(S * 8, 2), planes="all",
+                 # what a group adds to a batch's device memory, in doubles: its partials and its statistics
+                 group_doubles=(blocks + 1) * S * 8)
 
 
 def footprint_sweep(system, initial_material, final_material, field_points, wavelengths, theta_max, n_thetas, nphis=1,
@@ -1810,11 +1698,17 @@ def footprint_sweep(system, initial_material, final_material, field_points, wave
 
     float64 only: there is no ``dtype``, and float32 field points, wavelengths or frames raise ``ValueError``."""
     _float64_only("footprint_sweep", field_points, wavelengths, frames)
-    S = len(system.surfaces)
-    frames = _foot_frames(footprint_frames(system) if frames is None else frames, S)
-    return _sweep(_foot_mode(frames, n_thetas * nphis, _aperture_rads(system)), system, initial_material,
-                  final_material, _fan_source(field_points, wavelengths, theta_max, n_thetas, nphis, center_ray),
-                  device, "float64", groups_per_batch, fused, devices)
+    return _foot_sweep(system, initial_material, final_material,
+                       _fan_source(field_points, wavelengths, theta_max, n_thetas, nphis, center_ray), frames, device,
+                       groups_per_batch, fused, devices)
+
+
+def _foot_sweep(system, initial_material, final_material, source, frames, device, *sweep_args):
+    """What the two footprint sweeps share once the source exists; ``sweep_args`` are :func:`_sweep`'s after the
+    dtype."""
+    frames = _foot_frames(footprint_frames(system) if frames is None else frames, len(system.surfaces))
+    return _sweep(_foot_mode(frames, source.per, _aperture_rads(system)), system, initial_material, final_material,
+                  source, device, "float64", *sweep_args)
 
 
 def collimated_footprint_sweep(system, initial_material, final_material, normals, wavelengths, displacement_max,
@@ -1824,11 +1718,9 @@ def collimated_footprint_sweep(system, initial_material, final_material, normals
     (``rtpb_footprint_sweep_collimated``, or unfused through ``rtpb_footprint_stats``; bit-identical).  float64
     only."""
     _float64_only("collimated_footprint_sweep", normals, wavelengths, pt, frames)
-    S = len(system.surfaces)
-    frames = _foot_frames(footprint_frames(system) if frames is None else frames, S)
-    return _sweep(_foot_mode(frames, n_disps * nphis, _aperture_rads(system)), system, initial_material,
-                  final_material, _beam_source(normals, wavelengths, displacement_max, n_disps, nphis, phi_start, pt),
-                  device, "float64", groups_per_batch, fused, devices)
+    return _foot_sweep(system, initial_material, final_material,
+                       _beam_source(normals, wavelengths, displacement_max, n_disps, nphis, phi_start, pt), frames,
+                       device, groups_per_batch, fused, devices)
 
 
 def rigid_move(system, surfaces, shift=(0, 0, 0), tilt=(0, 0), pivot=None):
@@ -1893,7 +1785,8 @@ def _variant_source(systems, initial_material, final_material, inner, shared=Non
     leaves the dtype out of ``lead``: the float64-only entry points (wavefront, final rays) have no such argument."""
     V, per_variant = len(systems), inner.nf * inner.nw
     S = len(systems[0].surfaces)
-    src = SimpleNamespace(nf=V * inner.nf, nw=inner.nw, per=inner.per, wavelengths=inner.wavelengths,
+    src = SimpleNamespace(nf=V * inner.nf, nw=inner.nw, shape=(V,) + inner.shape, per=inner.per,
+                          wavelengths=inner.wavelengths,
                           suffix="_variants" + inner.suffix, nsurf=S, systems=systems, lower_seconds=0.0, lowered={})
 
     def lower(keys, code):
@@ -1977,25 +1870,37 @@ def _variant_sweep(what, systems, initial_material, final_material, inner, devic
     systems, S = _variant_systems(what, systems, fused, devices)
     for s in systems:
         _require_image_plane(s, require_image_plane)
-    V, nf, nw = len(systems), inner.nf, inner.nw
-    if not fused:
+    if fused and groups_per_batch is None:
+        groups_per_batch = _variant_batch(len(systems), S, inner.nf, inner.nw, inner.per, 16)
+    source = _variant_source(systems, initial_material, final_material, inner)
+    summary, timing = _variant_run(systems, S, initial_material, final_material, inner, source, _FOCUS,
+                                   lambda v: _FOCUS, device, dtype, groups_per_batch, fused, devices)
+    if fused:
+        timing["lower_seconds"] = source.lower_seconds
+    return summary, timing
+
+
+def _variant_run(systems, S, initial_material, final_material, inner, source, mode, mode_of, device, dtype,
+                 groups_per_batch, fused, devices):
+    """A variant sweep once its checks are done: fused, ``mode`` over ``source`` (the variant source of ``inner``)
+    through the single driver; unfused, one ordinary unfused sweep of ``inner`` per system with ``mode_of(v)``, the
+    seconds added up.  Either way the summary is ``mode``'s, shaped (n_variants, ...), and the timing dict says
+    ``"variants"``."""
+    V = len(systems)
+    if fused:
+        summary, timing = _sweep(mode, None, initial_material, final_material, source, device, dtype,
+                                 groups_per_batch, True, devices)
+    else:
         raws, seconds = [], 0.0
-        for s in systems:
-            one, t = _sweep(_FOCUS, s, initial_material, final_material, inner, device, dtype, groups_per_batch,
+        for v, s in enumerate(systems):
+            one, t = _sweep(mode_of(v), s, initial_material, final_material, inner, device, dtype, groups_per_batch,
                             False, None)
             raws.append(one["raw"])
             seconds += t["seconds"]
-        rays = V * nf * nw * inner.per
-        return summarize_focus(np.stack(raws)), {"seconds": seconds, "rays": rays,
-                                                 "ray_surface_per_s": rays * S / seconds, "variants": V}
-    if groups_per_batch is None:
-        groups_per_batch = _variant_batch(V, S, nf, nw, inner.per, 16)
-    source = _variant_source(systems, initial_material, final_material, inner)
-    mode = SimpleNamespace(**vars(_FOCUS))
-    mode.finish = lambda nf_all, nw_, raw: summarize_focus(raw.reshape(V, nf, nw, 16))
-    summary, timing = _sweep(mode, None, initial_material, final_material, source, device, dtype, groups_per_batch,
-                             fused, devices)
-    timing.update(variants=V, lower_seconds=source.lower_seconds)
+        rays = V * inner.nf * inner.nw * inner.per
+        summary = mode.finish((V,) + inner.shape, np.stack(raws))
+        timing = {"seconds": seconds, "rays": rays, "ray_surface_per_s": rays * S / seconds}
+    timing["variants"] = V
     return summary, timing
 
 
@@ -2033,17 +1938,11 @@ def collimated_variant_focus_sweep(systems, initial_material, final_material, no
                           dtype, groups_per_batch, fused, devices, require_image_plane)
 
 
-def _rays_mode():
-    """The final-rays call as the single driver sees it (:func:`_stats_mode`): ``rtpb_final_rays`` with a variant
-    source's suffix, no workspace; per device the rows of the shard's groups, (n, rays per group, 8) float64."""
-    def shard(dev, per, g0, n, batch):
-        import torch
-        rays = torch.empty((n, per, 8), dtype=torch.float64, device=dev)
-        return (rays,), lambda b0, b1: (rays[b0 - g0:b1 - g0].data_ptr(),)
-
-    return SimpleNamespace(entry="rtpb_final_rays", ncols=None, shard=shard,
-                           hbm_bytes=lambda per, n: n * per * 64,
-                           finish=lambda nf, nw, rays: rays.reshape(nf, nw, -1, 8))
+def _rays_mode(per):
+    """The final-rays call as the single driver sees it: ``rtpb_final_rays`` with a variant source's suffix, fused
+    only, no workspace; a group's output is the rows of its ``per`` rays."""
+    return _mode("rtpb_final_rays", None, (((per, 8), np.float64),),
+                 lambda shape, rays: rays.reshape(shape + (per, 8)))
 
 
 def _variant_refs(what, systems, initial_material, final_material, inner, chief, spot_summary, device,
@@ -2061,32 +1960,21 @@ def _variant_refs(what, systems, initial_material, final_material, inner, chief,
     if shared is None:
         shared = _variant_source(systems, initial_material, final_material, chief if inner is None else inner)
     if spot_summary is None:
-        focus = SimpleNamespace(**vars(_FOCUS))
-        focus.finish = lambda nf_all, nw_, raw: summarize_focus(raw.reshape(V, nf, nw, 16))
         source = _variant_source(systems, initial_material, final_material, inner, shared=shared)
-        spot_summary, _ = _sweep(focus, None, initial_material, final_material, source, device, "float64",
+        spot_summary, _ = _sweep(_FOCUS, None, initial_material, final_material, source, device, "float64",
                                  groups_per_batch or _variant_batch(V, S, nf, nw, inner.per, 16), True, devices)
         c0 = spot_summary["centroid"]
     source = _variant_source(systems, initial_material, final_material, chief, shared=shared, typed=False)
-    fin, _ = _sweep(_rays_mode(), None, initial_material, final_material, source, device, "float64",
+    fin, _ = _sweep(_rays_mode(chief.per), None, initial_material, final_material, source, device, "float64",
                     groups_per_batch or _variant_batch(V, S, nf, nw, 1, None), True, devices)
-    fin = fin.reshape(V, nf, nw, 8)
-    refs = np.empty((V, nf, nw, 8))
-    refs[..., 0:3] = c0
-    refs[..., 3:7] = fin[..., 3:7]
-    refs[..., 7] = [float(final_material.n(w)) / w for w in chief.wavelengths]
-    refs[~np.isfinite(fin[..., :7]).all(axis=-1)] = np.nan
-    return refs
+    return _refs_from(c0, fin.reshape(V, nf, nw, 8), final_material, chief.wavelengths)
 
 
-def _variant_wave(what, systems, initial_material, final_material, inner, chief, device, refs, spot_summary,
+def _variant_wave(what, systems, initial_material, final_material, inner, device, refs, spot_summary,
                   groups_per_batch, fused, devices, dtype):
-    """What the two variant wavefront sweeps share: the checks (before any device call), the references, the fused
-    call through the single driver or, unfused, one ordinary unfused wavefront sweep per system, and the summary
-    shaped (n_variants, ...)."""
-    if dtype not in ("float64", np.float64):
-        raise ValueError("wavefront_sweep is float64 only: a float32 phase of 1e4 ... 1e7 rad has an ulp of a "
-                         "milliradian to a radian")
+    """What the two variant wavefront sweeps share: the checks (before any device call), the references, and the
+    sweep (:func:`_variant_run`: unfused, system v's sweep takes ``refs[v]``)."""
+    _phase_needs_float64("wavefront_sweep is float64 only", dtype)
     systems, S = _variant_systems(what, systems, fused, devices)
     V, nf, nw = len(systems), inner.nf, inner.nw
     if refs is not None:
@@ -2095,29 +1983,17 @@ def _variant_wave(what, systems, initial_material, final_material, inner, chief,
     refs_seconds = 0.0
     if refs is None:
         t0 = time.perf_counter()
-        refs = _variant_refs(what, systems, initial_material, final_material, inner, chief, spot_summary, device,
-                             groups_per_batch, devices if fused else None, shared)
+        refs = _variant_refs(what, systems, initial_material, final_material, inner, inner.chief(), spot_summary,
+                             device, groups_per_batch, devices if fused else None, shared)
         refs_seconds = time.perf_counter() - t0 - shared.lower_seconds        # (the lowering happens in there)
-    if not fused:
-        raws, seconds = [], 0.0
-        for v, s in enumerate(systems):
-            one, t = _sweep(_wave_mode(np.ascontiguousarray(refs[v])), s, initial_material, final_material, inner,
-                            device, "float64", groups_per_batch, False, None)
-            raws.append(one["raw"])
-            seconds += t["seconds"]
-        rays = V * nf * nw * inner.per
-        return summarize_wavefront(np.stack(raws), refs), {
-            "seconds": seconds, "rays": rays, "ray_surface_per_s": rays * S / seconds, "variants": V,
-            "lower_seconds": shared.lower_seconds, "refs_seconds": refs_seconds}
-    if groups_per_batch is None:
+    if fused and groups_per_batch is None:
         groups_per_batch = _variant_batch(V, S, nf, nw, inner.per, 15, 8 * 8)
     # the references of groups [b0, b1) are contiguous in refs, as _wave_mode slices them
-    mode = _wave_mode(refs.reshape(V * nf, nw, 8))
-    mode.finish = lambda nf_all, nw_, raw: summarize_wavefront(raw.reshape(V, nf, nw, 15), refs)
     source = _variant_source(systems, initial_material, final_material, inner, shared=shared, typed=False)
-    summary, timing = _sweep(mode, None, initial_material, final_material, source, device, "float64",
-                             groups_per_batch, True, devices)
-    timing.update(variants=V, lower_seconds=shared.lower_seconds, refs_seconds=refs_seconds)
+    summary, timing = _variant_run(systems, S, initial_material, final_material, inner, source, _wave_mode(refs),
+                                   lambda v: _wave_mode(np.ascontiguousarray(refs[v])), device, "float64",
+                                   groups_per_batch, fused, devices)
+    timing.update(lower_seconds=shared.lower_seconds, refs_seconds=refs_seconds)
     return summary, timing
 
 
@@ -2177,9 +2053,8 @@ def variant_wavefront_sweep(systems, initial_material, final_material, field_poi
     ``systems``, unequal numbers of surfaces, more than ``RTPB_MAX_SURFACES`` of them, ``devices=`` without
     ``fused``, a ``refs`` of the wrong shape."""
     return _variant_wave("variant_wavefront_sweep", systems, initial_material, final_material,
-                         _fan_source(field_points, wavelengths, theta_max, n_thetas, nphis, center_ray),
-                         _fan_source(field_points, wavelengths, 0.0, 1, 1, center_ray), device, refs, spot_summary,
-                         groups_per_batch, fused, devices, dtype)
+                         _fan_source(field_points, wavelengths, theta_max, n_thetas, nphis, center_ray), device, refs,
+                         spot_summary, groups_per_batch, fused, devices, dtype)
 
 
 def collimated_variant_wavefront_sweep(systems, initial_material, final_material, normals, wavelengths,
@@ -2191,9 +2066,8 @@ def collimated_variant_wavefront_sweep(systems, initial_material, final_material
     :func:`collimated_variant_wavefront_refs`; a group's sums are bit-identical to
     :func:`collimated_wavefront_sweep` of its system alone with the same reference."""
     return _variant_wave("collimated_variant_wavefront_sweep", systems, initial_material, final_material,
-                         _beam_source(normals, wavelengths, displacement_max, n_disps, nphis, phi_start, pt),
-                         _beam_source(normals, wavelengths, 0, 1, 1, 0., pt), device, refs, spot_summary,
-                         groups_per_batch, fused, devices, dtype)
+                         _beam_source(normals, wavelengths, displacement_max, n_disps, nphis, phi_start, pt), device,
+                         refs, spot_summary, groups_per_batch, fused, devices, dtype)
 
 
 class GridInterpolator:

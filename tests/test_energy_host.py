@@ -260,8 +260,8 @@ def test_bad_params_shapes_raise_before_any_device_work():
 
 
 def test_automatic_params_fall_back_to_one(monkeypatch):
-    """energy_sweep(params=None) asks spot_sweep with the same arguments, then centroid and sigmas * rms_radius; an
-    empty group, a zero, a NaN and an infinite RMS radius get r_max 1.0."""
+    """energy_sweep(params=None) runs the spot mode on the same source with the same arguments, then centroid and
+    sigmas * rms_radius; an empty group, a zero, a NaN and an infinite RMS radius get r_max 1.0."""
     nan = np.nan
     summ = {"count": np.array([[100.0, 0.0, 50.0, 9.0, 1.0]]),
             "centroid": np.array([[[1.0, 2.0, 0.0], [nan, nan, nan], [0.5, 0.25, 0.0], [3.0, 4.0, 0.0],
@@ -283,35 +283,39 @@ def test_automatic_params_fall_back_to_one(monkeypatch):
     class Stop(Exception):
         pass
 
-    def fake(which):
-        def sweep(*a, **kw):
-            seen[which] = (a, kw)
-            return summ, {}
-        return sweep
+    def sweep(*a):
+        seen["sweep"] = a
+        return summ, {}
 
     def stop(s, bins, sigmas):
         seen["auto"] = (s, bins, sigmas)
         raise Stop
 
-    monkeypatch.setattr(analysis, "spot_sweep", fake("fan"))
-    monkeypatch.setattr(analysis, "collimated_spot_sweep", fake("beam"))
+    monkeypatch.setattr(analysis, "_sweep", sweep)
     monkeypatch.setattr(analysis, "auto_energy_params", stop)
     with pytest.raises(Stop):
         analysis.energy_sweep("sys", "m0", "m1", [[0.0, 0.0, 0.0]], [0.4, 0.5, 0.6, 0.7, 0.8], 0.1, 5, 3,
                               center_ray=(0, 1, 0), device="cuda:1", dtype="float32", bins=8, sigmas=2.0,
                               groups_per_batch=3, fused=True, devices=[1, 2])
-    a, kw = seen["fan"]
-    assert a[:3] == ("sys", "m0", "m1") and a[5:] == (0.1, 5, 3)
-    assert kw == dict(center_ray=(0, 1, 0), device="cuda:1", dtype="float32", groups_per_batch=3, fused=True,
-                      devices=[1, 2])
+    mode, *a = seen["sweep"]
+    assert mode is analysis._SPOT and a[:3] == ["sys", "m0", "m1"] and a[4:] == ["cuda:1", "float32", 3, True, [1, 2]]
+    assert (a[3].suffix, a[3].shape, a[3].per, a[3].wavelengths.tolist()) == ("", (1, 5), 15, [0.4, 0.5, 0.6, 0.7, 0.8])
+    with np.errstate(all="ignore"):                  # (a center_ray along y has no basis: the directions are NaN)
+        rays = a[3].rays()
+    assert rays.shape == (75, 8) and not rays[:, :3].any() and rays[:, 7].tolist() == np.repeat(a[3].wavelengths,
+                                                                                                15).tolist()
     assert seen["auto"] == (summ, 8, 2.0)
     with pytest.raises(Stop):
         analysis.collimated_energy_sweep("sys", "m0", "m1", [[0.0, 0.0, 1.0]], [0.4, 0.5], 2.0, 7, 3, 0.25,
                                          pt=(1, 2, 3), device="cuda:1", dtype="float32", bins=16, sigmas=3.0,
                                          groups_per_batch=2, fused=False)
-    a, kw = seen["beam"]
-    assert a[:3] == ("sys", "m0", "m1") and a[4:] == ([0.4, 0.5], 2.0, 7, 3, 0.25, (1, 2, 3))
-    assert kw == dict(device="cuda:1", dtype="float32", groups_per_batch=2, fused=False, devices=None)
+    mode, *a = seen["sweep"]
+    assert mode is analysis._SPOT and a[:3] == ["sys", "m0", "m1"] and a[4:] == ["cuda:1", "float32", 2, False, None]
+    assert (a[3].suffix, a[3].shape, a[3].per, a[3].wavelengths.tolist()) == ("_collimated", (1, 2), 21, [0.4, 0.5])
+    rays = a[3].rays()
+    dx, dy = rays[:, 0] - 1, rays[:, 1] - 2
+    assert rays.shape == (42, 8) and np.isclose(np.hypot(dx, dy).max(), 2.0) and (rays[:, 2] == 3).all()
+    assert np.isclose(np.arctan2(-dy[0], -dx[0]), 0.25) and (rays[:, 3:6] == (0, 0, 1)).all()       # (offset -2)
     assert seen["auto"] == (summ, 16, 3.0)
 
 

@@ -133,8 +133,8 @@ def test_bad_window_shapes_raise():
 
 
 def test_automatic_windows_fall_back_to_one(monkeypatch):
-    """image_sweep(windows=None) asks spot_sweep with the same arguments, then centroid +- sigmas * rms_radius; an
-    empty group, a zero and a NaN RMS radius get half-width 1.0."""
+    """image_sweep(windows=None) runs the spot mode on the same source with the same arguments, then centroid +-
+    sigmas * rms_radius; an empty group, a zero and a NaN RMS radius get half-width 1.0."""
     nan = np.nan
     summ = {"count": np.array([[100.0, 0.0, 50.0, 9.0, 1.0]]),
             "centroid": np.array([[[1.0, 2.0, 0.0], [nan, nan, nan], [0.5, 0.25, 0.0], [3.0, 4.0, 0.0],
@@ -153,8 +153,8 @@ def test_automatic_windows_fall_back_to_one(monkeypatch):
 
     seen = {}
 
-    def fake_spot_sweep(*a, **kw):
-        seen["a"], seen["kw"] = a, kw
+    def fake_sweep(*a):
+        seen["a"] = a
         return summ, {}
 
     class Stop(Exception):
@@ -164,15 +164,19 @@ def test_automatic_windows_fall_back_to_one(monkeypatch):
         seen["auto"] = (s, bins, sigmas)
         raise Stop
 
-    monkeypatch.setattr(analysis, "spot_sweep", fake_spot_sweep)
+    monkeypatch.setattr(analysis, "_sweep", fake_sweep)
     monkeypatch.setattr(analysis, "auto_image_windows", stop)
     with pytest.raises(Stop):
         analysis.image_sweep("sys", "m0", "m1", [[0.0, 0.0, 0.0]], [0.4, 0.5, 0.6, 0.7, 0.8], 0.1, 5, 3,
                              center_ray=(0, 1, 0), device="cuda:1", dtype="float32", bins=(8, 4), sigmas=2.0,
                              groups_per_batch=3, fused=True, devices=[1, 2])
-    assert seen["a"][:3] == ("sys", "m0", "m1") and seen["a"][5:] == (0.1, 5, 3)
-    assert seen["kw"] == dict(center_ray=(0, 1, 0), device="cuda:1", dtype="float32", groups_per_batch=3,
-                              fused=True, devices=[1, 2])
+    mode, *a = seen["a"]
+    assert mode is analysis._SPOT and a[:3] == ["sys", "m0", "m1"] and a[4:] == ["cuda:1", "float32", 3, True, [1, 2]]
+    assert (a[3].suffix, a[3].shape, a[3].per, a[3].wavelengths.tolist()) == ("", (1, 5), 15, [0.4, 0.5, 0.6, 0.7, 0.8])
+    with np.errstate(all="ignore"):                  # (a center_ray along y has no basis: the directions are NaN)
+        rays = a[3].rays()
+    assert rays.shape == (75, 8) and not rays[:, :3].any() and rays[:, 7].tolist() == np.repeat(a[3].wavelengths,
+                                                                                                15).tolist()
     assert seen["auto"] == (summ, (8, 4), 2.0)
 
 
