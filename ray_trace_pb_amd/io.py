@@ -76,7 +76,8 @@ class HistoryWriter:
     chunk_rays: rays per chunk (default: all -- one chunk per configuration, the script's chunks=(1, planes,
     nrays, 8)); the last chunk of a configuration is stored at full chunk size, padded with the fill value (NaN),
     as zarr stores edge chunks.  workers: threads encoding and writing chunks; compressed configurations with fewer
-    chunks than workers are encoded up to ``depth`` at a time (raw ones one at a time)."""
+    chunks than workers are encoded up to ``depth`` at a time (raw ones one at a time; ``max_inflight`` is the
+    number this store admits)."""
 
     def __init__(self, path, n_configs, n_planes, n_rays, dtype="float64", attrs=None, depth=2, compressor=None,
                  chunk_rays=None, workers=None):
@@ -99,8 +100,9 @@ class HistoryWriter:
         # configurations whose chunks are encoded at once (each holds its host copy until written): raw chunks one
         # at a time, as the disk takes them; compressed ones up to `depth`, enough to keep the workers busy when a
         # configuration has fewer chunks than there are workers
-        inflight = 1 if self.codec is None else max(1, min(int(depth), -(-n_workers // max(self._n_chunks, 1))))
-        self._inflight = threading.BoundedSemaphore(inflight)
+        per_pool = -(-n_workers // max(self._n_chunks, 1))
+        self.max_inflight = 1 if self.codec is None else max(1, min(int(depth), per_pool))     # read-only
+        self._inflight = threading.BoundedSemaphore(self.max_inflight)
         self._q = queue.Queue(maxsize=depth)
         self._free = queue.Queue()
         self._err = None
@@ -152,21 +154,28 @@ class HistoryWriter:
             # the configuration's chunks go to the pool; its host copy returns to the free list when the last one
             # is written, and the semaphore bounds the configurations in flight (and so the host copies held)
             self._inflight.acquire()
-            left = [self._n_chunks]
-            lock = threading.Lock()
-
-            def done(fut, buf=buf):
-                if fut.exception() is not None:
-                    self._err = fut.exception()
-                with lock:
-                    left[0] -= 1
-                    last = left[0] == 0
-                if last:
-                    if buf is not None:
-                        self._free.put(buf)
-                    self._inflight.release()
+            done = self._completion(buf)
             for j in range(self._n_chunks):
                 self._pool.submit(self._write_chunk, index, j, arr).add_done_callback(done)
+
+    def _completion(self, buf):
+        """The done-callback of one configuration's chunks.  The count of chunks left, its lock and the host copy
+        are this configuration's own: with several configurations in flight, a chunk of an earlier one that
+        finishes after a later one was admitted counts down its own configuration."""
+        left = [self._n_chunks]
+        lock = threading.Lock()
+
+        def done(fut):
+            if fut.exception() is not None:
+                self._err = fut.exception()
+            with lock:
+                left[0] -= 1
+                last = left[0] == 0
+            if last:
+                if buf is not None:
+                    self._free.put(buf)
+                self._inflight.release()
+        return done
 
     def write(self, index, history):
         """Store ``history`` (n_planes, n_rays, 8) as configuration ``index`` (asynchronous)."""

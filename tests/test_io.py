@@ -1,6 +1,8 @@
 """Streaming history writer (zarr-v2 layout of the reference's lightsheet sweep): round trips."""
 import json
 import os
+import threading
+import time
 
 import numpy as np
 import pytest
@@ -185,3 +187,173 @@ def test_device_histories_to_zlib_chunks(tmp_path):
     got = read_array(p)
     for i in range(2):
         assert same_bits(got[i], ref[i])
+
+
+# ---------------------------------------------------------------- several configurations in flight
+WAIT = 60.0            # a watchdog, never waited out on a correct writer
+SETTLE = 0.2           # see _Gated.settle
+
+
+class _Gated:
+    """A writer whose `_write_chunk` is wrapped: chunk (configuration, j) waits for its gate, if it has one, and
+    start and finish of every chunk are events the test can wait for.  The wrapper counts the configurations that
+    have a started and unfinished chunk; the writer's semaphore bounds them, since a configuration keeps its permit
+    until its last chunk's callback has run."""
+
+    def __init__(self, writer, held):
+        self.w = writer
+        self.gate = {k: threading.Event() for k in held}
+        keys = [(i, j) for i in range(writer.shape[0]) for j in range(writer._n_chunks)]
+        self.started = {k: threading.Event() for k in keys}
+        self.finished = {k: threading.Event() for k in keys}
+        self.peak, self.timed_out = 0, []
+        self._mu = threading.Lock()
+        inner = writer._write_chunk
+
+        def write_chunk(index, j, arr):
+            k = (index, j)
+            with self._mu:
+                self.started[k].set()
+                busy = {a for a, b in keys if self.started[a, b].is_set() and not self.finished[a, b].is_set()}
+                self.peak = max(self.peak, len(busy))
+            if k in self.gate and not self.gate[k].wait(WAIT):
+                self.timed_out.append(k)
+            inner(index, j, arr)
+            with self._mu:
+                self.finished[k].set()
+        writer._write_chunk = write_chunk
+
+    def await_(self, what, *keys):
+        for k in keys:
+            assert getattr(self, what)[k].wait(WAIT), f"chunk {k} never {what}"
+
+    def release(self, *keys):
+        for k in keys:
+            self.gate[k].set()
+
+    def settle(self):
+        """A chunk's done-callback runs after the chunk function has returned and leaves nothing to observe on a
+        correct writer, so the one way to let it run first is to wait a moment.  Too short a wait only lets a broken
+        writer slip past the checks made while chunks are held (the permit count after close() needs no wait); it
+        fails nothing on a correct one."""
+        time.sleep(SETTLE)
+
+    def close(self):
+        """close() under a watchdog (a lost permit can leave the drain thread blocked for ever), then the checks
+        every order shares: no gate timed out, the bound held, every permit is back."""
+        self.release(*self.gate)
+        t = threading.Thread(target=self.w.close, daemon=True)
+        t.start()
+        t.join(WAIT)
+        assert not t.is_alive(), "close() hangs"
+        assert not self.timed_out, self.timed_out
+        assert self.peak <= self.w.max_inflight, (self.peak, self.w.max_inflight)
+        back = sum(self.w._inflight.acquire(blocking=False) for _ in range(self.w.max_inflight))
+        assert back == self.w.max_inflight, f"{back} of {self.w.max_inflight} permits back after close()"
+
+
+def _overlap_writer(path, n_configs, n_planes, n_rays, held):
+    """compressor zlib, two chunks per configuration, 4 workers, depth 2: two configurations in flight."""
+    w = HistoryWriter(path, n_configs, n_planes, n_rays, compressor="zlib", chunk_rays=-(-n_rays // 2), workers=4,
+                      depth=2)
+    assert w.max_inflight == 2 and w._n_chunks == 2
+    return _Gated(w, held)
+
+
+def _overlap_histories(n):
+    rng = np.random.default_rng(7)
+    hist = [rng.normal(size=(5, 600, 8)) for _ in range(n)]
+    hist[1][2, 301] = np.nan
+    return hist
+
+
+def test_overlap_earlier_configuration_finishes_last(tmp_path):
+    """Order 1: configuration 0's chunks are held until both of configuration 1's are written and configuration 2
+    has taken 1's place; then 0's chunks finish while 2 is the newest configuration.  Each configuration counts its
+    own chunks, so every permit comes back and every configuration reads back."""
+    hist = _overlap_histories(4)
+    p = tmp_path / "o1.zarr"
+    g = _overlap_writer(p, 4, 5, 600, held=[(0, 0), (0, 1)])
+    try:
+        g.w.write(0, hist[0])
+        g.w.write(1, hist[1])
+        g.await_("finished", (1, 0), (1, 1))
+        g.w.write(2, hist[2])
+        g.await_("started", (2, 0))          # admitted: configuration 1's last callback has run
+        g.release((0, 0), (0, 1))
+        g.w.write(3, hist[3])
+    finally:
+        g.close()
+    got = read_array(p)
+    for i in range(4):
+        assert same_bits(got[i], hist[i]), i
+
+
+def test_overlap_first_chunks_finish_then_a_third_configuration(tmp_path):
+    """Order 2: 0's chunk 0 finishes once 1 has been admitted, then 1's chunk 0; both chunk 1s are held while
+    configuration 2 is written.  Two chunks have finished, but neither configuration has: 2 must wait."""
+    hist = _overlap_histories(4)
+    p = tmp_path / "o2.zarr"
+    g = _overlap_writer(p, 4, 5, 600, held=[(0, 0), (0, 1), (1, 0), (1, 1)])
+    try:
+        g.w.write(0, hist[0])
+        g.w.write(1, hist[1])
+        g.await_("started", (1, 0))
+        g.release((0, 0))
+        g.await_("finished", (0, 0))
+        g.release((1, 0))
+        g.await_("finished", (1, 0))
+        g.settle()
+        g.w.write(2, hist[2])
+        assert not g.started[2, 0].wait(SETTLE), "configuration 2 admitted beside two unfinished ones"
+        g.release((0, 1), (1, 1))
+        g.w.write(3, hist[3])
+    finally:
+        g.close()
+    got = read_array(p)
+    for i in range(4):
+        assert same_bits(got[i], hist[i]), i
+
+
+@pytest.mark.gpu
+def test_overlap_device_histories_keep_their_pinned_buffers(tmp_path):
+    """Order 2 with device histories, whose host copies are recycled pinned buffers: configuration 1's chunk 1 is
+    held while configuration 2 is written and its copy has finished.  1's buffer is still being encoded, so 2 must
+    get another one; every configuration reads back bit for bit and every buffer ends on the free list."""
+    torch = pytest.importorskip("torch")
+    import ray_trace_pb_amd.materials as mat
+    import ray_trace_pb_amd.raytrace as rt
+    import systems
+    system, rays, m0, m1 = systems.c1_plano_convex(rt, mat)
+    x = torch.from_numpy(rays).cuda()
+    n = rays.shape[0]
+    hist = [system.ray_trace(x + torch.tensor([0, 0, -i, 0, 0, 0, 0, 0], dtype=x.dtype, device=x.device), m0, m1)
+            for i in range(4)]
+    ref = [h.cpu().numpy() for h in hist]
+    assert not any(same_bits(ref[i], ref[j]) for i in range(4) for j in range(i))
+    p = tmp_path / "gpu_o2.zarr"
+    g = _overlap_writer(p, 4, 7, n, held=[(0, 0), (0, 1), (1, 0), (1, 1)])
+    try:
+        g.w.write(0, hist[0])
+        g.w.write(1, hist[1])
+        g.await_("started", (1, 0))
+        g.release((0, 0))
+        g.await_("finished", (0, 0))
+        g.release((1, 0))
+        g.await_("finished", (1, 0))
+        g.settle()
+        g.w.write(2, hist[2])
+        torch.cuda.synchronize()
+        g.release((0, 1), (1, 1))
+        g.w.write(3, hist[3])
+    finally:
+        g.close()
+    got = read_array(p)
+    for i in range(4):
+        assert same_bits(got[i], ref[i]), i
+    w = g.w
+    assert len(w._pinned) <= 4
+    free = []
+    while not w._free.empty():
+        free.append(w._free.get_nowait())
+    assert sorted(b.data_ptr() for b in free) == sorted(b.data_ptr() for b in w._pinned)
