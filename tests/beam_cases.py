@@ -14,8 +14,10 @@ import numpy as np
 
 import ray_trace_pb_amd.materials as mat
 import ray_trace_pb_amd.raytrace as rt
+from ray_trace_pb_amd import _capi as C
 from oracle import rt_numpy as O
 from serialize import material_to_dict, surface_to_dict
+from sweep_cases import alive
 import systems
 
 ND, NPH = 65, 9                        # 585 rays per group: two tiles and a ragged third, so a block with an empty tile
@@ -34,6 +36,19 @@ NAMES = ("c2",) + CLIPPED + ("dead", "poly6", "same_pt", "same_normal")
 def unit(v):
     v = np.asarray(v, dtype=float)
     return v / np.linalg.norm(v)
+
+
+class Ebaf11Poly(mat.Ebaf11):
+    """Ebaf11 sent to the kernels as RTPB_POLY6 (device pow) instead of a host table."""
+
+    def _rtpb_lower(self):
+        return C.RTPB_POLY6, tuple(self.params)
+
+
+def poly_system(system):
+    mats = [Ebaf11Poly() if type(m) is mat.Ebaf11 else m for m in system.materials]
+    assert any(isinstance(m, Ebaf11Poly) for m in mats)
+    return rt.System(system.surfaces, mats)
 
 
 def _y_system():
@@ -74,9 +89,8 @@ def _build(name):
         return dict(c2, pts=[[200.0, 0.0, -5.0], [0.0, 0.0, -5.0]], dmax=1.0, normals=[[0, 0, 1], [0, 0, 1]],
                     prop="a beam that misses its system entirely beside one that does not")
     if name == "poly6":
-        from test_gpu_poly6 import _poly_system
         table = systems.c3_system(rt, mat)
-        return dict(system=_poly_system(table), m0=vac, m1=vac, pts=[0.0, 0.0, -5.0], dmax=4.0,
+        return dict(system=poly_system(table), m0=vac, m1=vac, pts=[0.0, 0.0, -5.0], dmax=4.0,
                     normals=[[0, 0, 1], unit([np.tan(1 * DEG), 0, 1])], wls=[0.532, 0.58, 0.635], bitwise=False,
                     S=[surface_to_dict(s) for s in table.surfaces],
                     M=[material_to_dict(m) for m in [vac] + list(table.materials) + [vac]],
@@ -159,11 +173,6 @@ def oracle_refs(name):
                 refs[i, j, 7] = float(c.m1.n(wl)) / wl
     refs.setflags(write=False)
     return refs
-
-
-def alive(plane):
-    """A ray is alive in a plane when its position is a number (the sweeps count finite x and y)."""
-    return np.isfinite(plane[..., 0]) & np.isfinite(plane[..., 1])
 
 
 def oracle_counts(name, dtype="float64"):

@@ -194,20 +194,6 @@ extern "C" void harness_sweep_divisor(int64_t d, int64_t g, uint32_t* mul, int32
     sweep_divisor(d, g, *mul, *shift);
 }
 
-// the sweep's block rows (rtpb_sweep_host.h plan_sweep_rows): bundles and singles hold up to n_groups entries, rows
-// up to n_groups (a row has at least two groups); counts = the three lengths
-extern "C" void harness_sweep_rows(const double* group_params, int64_t n_groups, int bundles_allowed, int rays_per_lane,
-                                   int max_bundle, int32_t* bundles, int32_t* rows, int32_t* singles, int64_t* counts) {
-    const rtpbi::SweepRows r = rtpbi::plan_sweep_rows(group_params, n_groups, bundles_allowed != 0, rays_per_lane,
-                                                      max_bundle);
-    std::copy(r.bundles.begin(), r.bundles.end(), bundles);
-    std::copy(r.rows.begin(), r.rows.end(), rows);
-    std::copy(r.singles.begin(), r.singles.end(), singles);
-    counts[0] = static_cast<int64_t>(r.bundles.size());
-    counts[1] = static_cast<int64_t>(r.rows.size());
-    counts[2] = static_cast<int64_t>(r.singles.size());
-}
-
 // the sweep's per-group media (rtpb_sweep_host.h fill_group_media) of nmat lowered materials:
 // out[n_groups][nmat + 3 (nmat - 1)]
 extern "C" void harness_sweep_media(const rtpb_material* materials, int32_t nmat, const double* group_params,

@@ -1,5 +1,5 @@
-"""Build + load the CPU harness of the kernel arithmetic (tests/native/math_harness.cpp).
-TEST INFRASTRUCTURE ONLY."""
+"""Build + load the CPU harnesses of the kernels' host-instantiable code (tests/native/*.cpp), and build the GPU
+checks beside them.  TEST INFRASTRUCTURE ONLY."""
 import ctypes
 import os
 import subprocess
@@ -7,31 +7,46 @@ import subprocess
 import numpy as np
 
 HERE = os.path.dirname(os.path.abspath(__file__))
-SRC = os.path.join(HERE, "native", "math_harness.cpp")
-OUT = os.path.join(HERE, "native", "_build", "libmath_harness.so")
-DEPS = [SRC, os.path.join(HERE, "..", "ray_trace_pb_amd", "csrc", "rtpb_math.h"),
-        os.path.join(HERE, "..", "ray_trace_pb_amd", "csrc", "rtpb_sweep_host.h"),
-        os.path.join(HERE, "..", "include", "rtpb.h")]
+CSRC = os.path.join(HERE, "..", "ray_trace_pb_amd", "csrc")
+# every CPU harness (tests/native/<name>.cpp) and the headers of csrc/ it instantiates
+HARNESSES = {
+    "math_harness": ("rtpb_math.h", "rtpb_sweep_host.h"),       # the kernel arithmetic (harness(), below)
+    "foot_harness": ("rtpb_foot.h", "rtpb_math.h"),             # the footprint term (foot_harness.py)
+    "wavemap_harness": ("rtpb_wavemap.h", "rtpb_math.h"),       # the wavefront map's rule (wavemap_harness.py)
+    "sweep_rows": ("rtpb_sweep_host.h", "rtpb_math.h"),         # the sweeps' block rows and layout (sweep_rows.py)
+}
+DEPS = [os.path.join(HERE, "native", "math_harness.cpp")] + \
+    [os.path.join(CSRC, h) for h in HARNESSES["math_harness"]] + [os.path.join(HERE, "..", "include", "rtpb.h")]
 
-_lib = None
+_loaded = {}
+
+
+def load(name, headers=None):
+    """The library of tests/native/<name>.cpp, loaded once per process; rebuilt first when it is older than its source,
+    one of its ``headers`` of csrc/ (HARNESSES[name] by default) or include/rtpb.h."""
+    if name not in _loaded:
+        src = os.path.join(HERE, "native", name + ".cpp")
+        out = os.path.join(HERE, "native", "_build", f"lib{name}.so")
+        deps = [src] + [os.path.join(CSRC, h) for h in (HARNESSES[name] if headers is None else headers)] + \
+            [os.path.join(HERE, "..", "include", "rtpb.h")]
+        os.makedirs(os.path.dirname(out), exist_ok=True)
+        import fcntl
+        with open(out + ".lock", "w") as lk:        # several test processes may race to (re)build
+            fcntl.flock(lk, fcntl.LOCK_EX)
+            if not os.path.exists(out) or any(os.path.getmtime(out) < os.path.getmtime(d) for d in deps):
+                tmp = f"{out}.{os.getpid()}.tmp"
+                subprocess.run(["g++", "-O2", "-std=c++17", "-ffp-contract=off", "-fPIC", "-shared",
+                                "-I", os.path.join(HERE, "..", "include"), "-o", tmp, src], check=True)
+                os.replace(tmp, out)
+        _loaded[name] = ctypes.CDLL(out)
+    return _loaded[name]
 
 
 def harness():
-    global _lib
-    if _lib is None:
-        os.makedirs(os.path.dirname(OUT), exist_ok=True)
-        import fcntl
-        with open(OUT + ".lock", "w") as lk:        # several test processes may race to (re)build
-            fcntl.flock(lk, fcntl.LOCK_EX)
-            if not os.path.exists(OUT) or any(os.path.getmtime(OUT) < os.path.getmtime(d) for d in DEPS):
-                tmp = f"{OUT}.{os.getpid()}.tmp"
-                subprocess.run(["g++", "-O2", "-std=c++17", "-ffp-contract=off", "-fPIC", "-shared",
-                                "-I", os.path.join(HERE, "..", "include"), "-o", tmp, SRC], check=True)
-                os.replace(tmp, OUT)
-        _lib = ctypes.CDLL(OUT)
-        _lib.harness_bounds.argtypes = [ctypes.c_double] * 3 + [ctypes.POINTER(ctypes.c_double)]
-        _lib.harness_bounds.restype = None
-    return _lib
+    lib = load("math_harness")
+    lib.harness_bounds.argtypes = [ctypes.c_double] * 3 + [ctypes.POINTER(ctypes.c_double)]
+    lib.harness_bounds.restype = None
+    return lib
 
 
 def surface_flags(low):

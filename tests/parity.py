@@ -5,6 +5,11 @@ import os
 
 import numpy as np
 
+import ray_trace_pb_amd.materials as mat
+import ray_trace_pb_amd.raytrace as rt
+from oracle import rt_numpy as O
+from serialize import material_to_dict, surface_to_dict, system_from_json
+
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
 ALL_CASES = sorted(os.path.basename(f)[:-4] for f in glob.glob(os.path.join(GOLDEN, "*.npz"))
                    if os.path.basename(f)[:-4] not in ("shapes", "generators"))
@@ -18,6 +23,26 @@ def load_case(name):
     d = np.load(os.path.join(GOLDEN, f"{name}.npz"))
     spec = json.loads(str(d["system_json"]))
     return spec, d["rays_in"], d["history"]
+
+
+def golden_case(name):
+    """(system, m0, m1, rays, history) of a golden case: the system rebuilt from the fixture's JSON, the reference's
+    input rays and its history."""
+    d = np.load(os.path.join(GOLDEN, f"{name}.npz"))
+    system, m0, m1 = system_from_json(rt, mat, str(d["system_json"]))
+    return system, m0, m1, d["rays_in"], d["history"]
+
+
+def oracle_dicts(system, m0, m1):
+    """The oracle's surface and material dicts of a system between m0 and m1."""
+    return ([surface_to_dict(s) for s in system.surfaces],
+            [material_to_dict(m) for m in [m0] + list(system.materials) + [m1]])
+
+
+def oracle_trace(system, m0, m1, rays):
+    """The NumPy oracle's history of rays through a system (its floating-point warnings silenced)."""
+    with np.errstate(all="ignore"):
+        return O.ray_trace(*oracle_dicts(system, m0, m1), rays)
 
 
 def same_bits(got, ref):
@@ -36,6 +61,27 @@ def same_bits(got, ref):
         return False
     u = {2: np.uint16, 4: np.uint32, 8: np.uint64}[t.itemsize]
     return bool(np.array_equal(np.ascontiguousarray(got[~nan]).view(u), np.ascontiguousarray(ref[~nan]).view(u)))
+
+
+def bits(a):
+    return np.ascontiguousarray(a, dtype=np.float64).view(np.int64)
+
+
+def same_int64(got, ref):
+    got, ref = np.ascontiguousarray(got, dtype=np.float64), np.ascontiguousarray(ref, dtype=np.float64)
+    return got.shape == ref.shape and np.array_equal(got.view(np.int64), ref.view(np.int64))
+
+
+def assert_same_summary(got, exp):
+    assert got.keys() == exp.keys()
+    for k in exp:
+        assert same_bits(got[k], exp[k]), k
+
+
+def plane_of(x, y):
+    p = np.zeros((len(x), 8))
+    p[:, 0], p[:, 1], p[:, 5] = x, y, 1.0
+    return p
 
 
 def compare(got, ref, rtol):

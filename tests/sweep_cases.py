@@ -38,6 +38,20 @@ TAIL_BEFORE = ("c5_tail2_before", "c5_tail5_before")
 TAIL_WLS = [0.405, 0.532, 0.785]
 
 
+def tilted_xz_system():
+    """Surfaces tilted in the x-z plane (kPlaneXZ): flats and PerfectLens steps with normals (-sin t, 0, cos t) and
+    centers off the axis in x, between Constant, Sellmeier and Vacuum media -- uniform-media lenses (F, B in the
+    plane: the focal planes' x-z center form) and a lens beside a Sellmeier glass (per-ray focal points)."""
+    def n(t):
+        return [-np.sin(t), 0.0, np.cos(t)]
+    return rt.System([rt.FlatSurface([0.3, 0, 0], n(0.2), 20),
+                      rt.PerfectLens(15, [0.5, 0, 10], n(0.3), 0.8),
+                      rt.FlatSurface([1.0, 0, 22], n(0.25), 40),
+                      rt.PerfectLens(-12, [-0.7, 0, 35], n(-0.4), 0.7),
+                      rt.FlatSurface([0.0, 0, 50], n(0.1), 60)],
+                     [mat.Constant(1.3), mat.Vacuum(), mat.Bk7(), mat.Constant(1.1)]), mat.Vacuum(), mat.Constant(1.0)
+
+
 def _golden(name):
     """Field points, wavelengths and fan axis from the golden bundle of the system, as in
     test_fused_sweep_bitwise_on_golden_systems."""
@@ -83,7 +97,6 @@ def _build(name):
         return dict(system=systems.c2_system(rt, mat), m0=vac, m1=vac, fields=[[0.0, 0.0, -5.0], [1.0, -2.0, -5.0]],
                     wls=list(systems.C2_WAVELENGTHS), theta=0.05, prop="the lens-free instantiation, all alive")
     if name == "xz":
-        from test_axial import tilted_xz_system
         system, m0, m1 = tilted_xz_system()
         return dict(system=system, m0=m0, m1=m1, fields=[[0.0, 0.0, -3.0], [0.4, -0.3, -3.0]], wls=[0.5, 0.55, 0.6],
                     theta=0.2, prop="tilted flats and PerfectLens steps in the x-z plane")
@@ -122,6 +135,39 @@ def case(name):
         kw["M"] = [material_to_dict(m) for m in [kw["m0"]] + list(kw["system"].materials) + [kw["m1"]]]
     kw["fields"] = np.asarray(kw["fields"], dtype=float)
     return Case(**kw)
+
+
+# (the positional arguments of analysis.spot_sweep / focus_sweep, groups_per_batch) of the fused == unfused tests'
+# systems, at NT x NPH rays per group
+def sweep_case(case):
+    gpb = 4
+    if case == "c5":
+        system, m0, m1 = systems.c5_system(rt, mat), mat.Constant(1), mat.Constant(1)
+        fields, wls, theta = systems.c5_field_points(2), [0.405, 0.532, 0.785], 0.5 * np.pi / 180
+    elif case == "c5_bundles":
+        # batches of 13 groups over 2 fields x 9 wavelengths: bundle rows of 8 and 4 groups and single rows
+        system, m0, m1 = systems.c5_system(rt, mat), mat.Constant(1), mat.Constant(1)
+        fields, wls, theta = systems.c5_field_points(2), list(np.linspace(0.4, 0.8, 9)), 0.5 * np.pi / 180
+        gpb = 13
+    elif case == "c2":
+        system, m0, m1 = systems.c2_system(rt, mat), mat.Vacuum(), mat.Vacuum()
+        fields, wls, theta = [[0.0, 0.0, -5.0], [1.0, -2.0, -5.0]], list(systems.C2_WAVELENGTHS), 0.05
+    elif case == "c4":
+        system, m0, m1 = systems.c4_system(rt, mat), mat.Constant(systems.OPM_N1), mat.Vacuum()
+        fields, wls, theta = [[1e-3, 1e-3, 1e-3 * np.tan(np.pi / 6)], [0.0, 0.0, 0.0]], \
+            [systems.OPM_WAVELENGTH, 0.9 * systems.OPM_WAVELENGTH], np.arcsin(1.35 / systems.OPM_N1)
+    elif case == "xz":
+        system, m0, m1 = tilted_xz_system()
+        fields, wls, theta = [[0.0, 0.0, -3.0], [0.4, -0.3, -3.0]], [0.5, 0.6], 0.2
+    elif case in ("tir", "tir_last"):
+        system, _, m0, m1 = systems.tir_prism(rt, mat)
+        if case == "tir_last":
+            system = rt.System(system.surfaces[:2], system.materials[:1])
+        fields, wls, theta = [[0.0, 0.0, -5.0], [2.0, -1.0, -5.0]], [0.45, 0.55, 0.7], 0.5
+    else:
+        system, m0, m1 = systems.stress_system(rt, mat), mat.Vacuum(), mat.Vacuum()
+        fields, wls, theta = [[0.0, 0.0, -10.0], [3.0, -2.0, -10.0], [-1.5, 2.5, -10.0]], [0.5, 0.6328], 0.3
+    return (system, m0, m1, fields, wls, theta, NT, NPH), gpb
 
 
 def sweep_args(c):

@@ -14,9 +14,8 @@ import ray_trace_pb_amd.raytrace as rt
 from ray_trace_pb_amd import _capi as C
 from ray_trace_pb_amd import _engine as E
 from native_harness import harness_trace, surface_flags
-from oracle import rt_numpy as O
-from parity import same_bits
-from serialize import material_to_dict, surface_to_dict
+from parity import oracle_trace, same_bits
+from sweep_cases import tilted_xz_system
 import systems
 
 K_AXIAL = 64
@@ -33,20 +32,6 @@ def axial_lens_system():
                       rt.PerfectLens(20, [0, 0, 40], [0, 0, 1], 0.9),
                       rt.FlatSurface([0, 0, 70], [0, 0, 1], 50)],
                      [mat.Bk7(), mat.Constant(1.2), mat.Constant(1.4), mat.Vacuum()]), mat.Vacuum(), mat.Constant(1.0)
-
-
-def tilted_xz_system():
-    """Surfaces tilted in the x-z plane (kPlaneXZ): flats and PerfectLens steps with normals (-sin t, 0, cos t) and
-    centers off the axis in x, between Constant, Sellmeier and Vacuum media -- uniform-media lenses (F, B in the
-    plane: the focal planes' x-z center form) and a lens beside a Sellmeier glass (per-ray focal points)."""
-    def n(t):
-        return [-np.sin(t), 0.0, np.cos(t)]
-    return rt.System([rt.FlatSurface([0.3, 0, 0], n(0.2), 20),
-                      rt.PerfectLens(15, [0.5, 0, 10], n(0.3), 0.8),
-                      rt.FlatSurface([1.0, 0, 22], n(0.25), 40),
-                      rt.PerfectLens(-12, [-0.7, 0, 35], n(-0.4), 0.7),
-                      rt.FlatSurface([0.0, 0, 50], n(0.1), 60)],
-                     [mat.Constant(1.3), mat.Vacuum(), mat.Bk7(), mat.Constant(1.1)]), mat.Vacuum(), mat.Constant(1.0)
 
 
 CASES = {
@@ -82,12 +67,6 @@ def adversarial_rays(n=6000, seed=7, wl=0.55):
     ax[:, 6] = -0.0
     ax[:, 7] = wl
     return np.concatenate((r, ax), axis=0)
-
-
-def oracle(system, m0, m1, rays):
-    with np.errstate(all="ignore"):
-        return O.ray_trace([surface_to_dict(s) for s in system.surfaces],
-                           [material_to_dict(m) for m in [m0] + list(system.materials) + [m1]], rays)
 
 
 def lowered(system, m0, m1, rays):
@@ -131,7 +110,7 @@ def test_plane_xz_flags_set_where_the_geometry_allows(name):
 def test_axial_steps_bitwise_vs_oracle_cpu(name):
     system, m0, m1 = CASES[name]()
     rays = adversarial_rays(wl=0.532 if name == "c4" else 0.55)
-    ref = oracle(system, m0, m1, rays)
+    ref = oracle_trace(system, m0, m1, rays)
     got = harness_trace(lowered(system, m0, m1, rays), rays)
     assert same_bits(got, ref)
 
@@ -142,7 +121,7 @@ def test_axial_steps_bitwise_vs_oracle_gpu(name):
     torch = pytest.importorskip("torch")
     system, m0, m1 = CASES[name]()
     rays = adversarial_rays(wl=0.532 if name == "c4" else 0.55)
-    ref = oracle(system, m0, m1, rays)
+    ref = oracle_trace(system, m0, m1, rays)
     got = system.ray_trace(torch.from_numpy(rays).to("cuda:0"), m0, m1)
     assert same_bits(got.cpu().numpy(), ref)
     assert same_bits(system.ray_trace(rays, m0, m1, planes="final")[0], ref[-1])

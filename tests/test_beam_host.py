@@ -1,10 +1,6 @@
 """The collimated-beam sweeps on the host: the argument checks of the four rtpb_*_sweep_collimated entry points (no GPU
 is touched), their ctypes signatures, the bundle-row key of point and frame together (csrc/rtpb_sweep_host.h
-plan_sweep_rows through tests/native/beam_rows.cpp), and what the Python wrappers refuse before any device call."""
-import ctypes
-import fcntl
-import os
-import subprocess
+plan_sweep_rows through tests/sweep_rows.py), and what the Python wrappers refuse before any device call."""
 
 import numpy as np
 import pytest
@@ -12,9 +8,9 @@ import pytest
 from ray_trace_pb_amd import _capi as C
 from ray_trace_pb_amd import analysis
 import ray_trace_pb_amd.raytrace as rt
-from test_wavefront_host import _flat_plan
+from flat_plans import flat_plan
+import sweep_rows
 
-HERE = os.path.dirname(os.path.abspath(__file__))
 STATS = {"rtpb_spot_sweep_collimated": (7, b"spot-sweep"), "rtpb_focus_sweep_collimated": (16, b"focus-sweep"),
          "rtpb_wavefront_sweep_collimated": (15, b"wavefront-sweep")}
 
@@ -28,7 +24,7 @@ def test_statistics_entry_points_validate_without_a_gpu():
     buf = np.zeros(4096)
     p = buf.ctypes.data
     G, tiles = 3, 2                     # 30 x 10 rays: two tiles
-    plan, plan32 = _flat_plan(C.RTPB_F64), _flat_plan(C.RTPB_F32)
+    plan, plan32 = flat_plan(C.RTPB_F64), flat_plan(C.RTPB_F32)
     try:
         for name, (ncols, word) in STATS.items():
             fn = getattr(lib, name)
@@ -65,7 +61,7 @@ def test_image_entry_point_validates_without_a_gpu():
     lib = C.lib()
     buf = np.zeros(4096)
     p = buf.ctypes.data
-    plan = _flat_plan(C.RTPB_F64)
+    plan = flat_plan(C.RTPB_F64)
     try:
         ok = dict(plan=plan, device=0, n_groups=2, group_params=p, group_frames=p, n_disps=30, nphis=10, offsets=p,
                   phi_cos_sin=p, windows=p, nx=16, ny=12, image_out=p, outside_out=p, stream=None)
@@ -147,36 +143,10 @@ def test_collimated_sweeps_with_devices_need_the_fused_path(monkeypatch):
         analysis.spot_sweep(None, None, None, [[0.0, 0.0, 0.0]], [0.5], 0.1, 5, 3, fused=False, devices=[0])
 
 
-ROWS_SRC = os.path.join(HERE, "native", "beam_rows.cpp")
-ROWS_OUT = os.path.join(HERE, "native", "_build", "libbeam_rows.so")
-RPL, MAX_BUNDLE = 2, 8                  # the shipped constants: two rays per lane, eight groups per bundle row
-
-
-def plan_rows(params, frames):
-    """(bundles, rows, singles) of plan_sweep_rows for (G, 4) group parameters and (G, 9) frames, or None."""
-    deps = [ROWS_SRC, os.path.join(HERE, "..", "ray_trace_pb_amd", "csrc", "rtpb_sweep_host.h")]
-    os.makedirs(os.path.dirname(ROWS_OUT), exist_ok=True)
-    with open(ROWS_OUT + ".lock", "w") as lk:           # several test processes may race to (re)build
-        fcntl.flock(lk, fcntl.LOCK_EX)
-        if not os.path.exists(ROWS_OUT) or any(os.path.getmtime(ROWS_OUT) < os.path.getmtime(d) for d in deps):
-            tmp = f"{ROWS_OUT}.{os.getpid()}.tmp"
-            subprocess.run(["g++", "-O2", "-std=c++17", "-ffp-contract=off", "-fPIC", "-shared",
-                            "-I", os.path.join(HERE, "..", "include"), "-o", tmp, ROWS_SRC], check=True)
-            os.replace(tmp, ROWS_OUT)
-    fn = ctypes.CDLL(ROWS_OUT).beam_sweep_rows
-    fn.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int, ctypes.c_int, ctypes.c_int] + \
-        [ctypes.c_void_p] * 4
-    fn.restype = None
-    params = np.ascontiguousarray(params, dtype=np.float64)
-    G = params.shape[0]
-    if frames is not None:
-        frames = np.ascontiguousarray(frames, dtype=np.float64)
-        assert frames.shape == (G, 9)
-    bundles, rows, singles = (np.full(G, -1, dtype=np.int32) for _ in range(3))
-    counts = np.zeros(3, dtype=np.int64)
-    fn(params.ctypes.data, None if frames is None else frames.ctypes.data, G, 1, RPL, MAX_BUNDLE,
-       bundles.ctypes.data, rows.ctypes.data, singles.ctypes.data, counts.ctypes.data)
-    return bundles[:counts[0]].tolist(), rows[:counts[1]].tolist(), singles[:counts[2]].tolist()
+def row_lists(params, frames):
+    """(bundles, rows, singles) of plan_sweep_rows as lists, for (G, 4) group parameters and (G, 9) frames, or None:
+    the collimated sweeps' call, which passes the frames and leaves the variants to their default."""
+    return tuple(a.tolist() for a in sweep_rows.plan_rows(params, frames, trailing=1))
 
 
 def _frames(normals):
@@ -195,26 +165,26 @@ def test_bundle_rows_key_on_point_and_frame_together():
     params[2 * nw:, :3] = [1.0, -2.0, -5.0]
     params[:, 3] = np.tile(0.5 + 0.05 * np.arange(nw), 3)
     frames = np.repeat(_frames([normals[0], normals[1], normals[0]]), nw, axis=0)
-    bundles, rows, singles = plan_rows(params, frames)
+    bundles, rows, singles = row_lists(params, frames)
     assert singles == [] and sorted(bundles) == list(range(12))
     assert rows[1::2] == [4, 4, 4] and rows[0::2] == [0, 4, 8]
     for o in rows[0::2]:
         assert len({g // nw for g in bundles[o:o + 4]}) == 1
     # the key the fan sweeps use, and what it would do here
-    b0, r0, s0 = plan_rows(params, None)
+    b0, r0, s0 = row_lists(params, None)
     assert r0[1::2] == [8, 4] and {g // nw for g in b0[:8]} == {0, 1}
     # -0.0 and +0.0 in a normal are two bit patterns, hence two beams (as two field points are for the fans)
     f2 = _frames([[0.0, 0.0, 1.0]] * 2)
     f2 = np.repeat(f2, 2, axis=0)
     p2 = np.zeros((4, 4))
     p2[:, 3] = [0.5, 0.6, 0.5, 0.6]
-    assert plan_rows(p2, f2)[1] == [0, 4]
+    assert row_lists(p2, f2)[1] == [0, 4]
     f2[2:, 0] = -0.0
-    assert plan_rows(p2, f2)[1] == [0, 2, 2, 2]
+    assert row_lists(p2, f2)[1] == [0, 2, 2, 2]
     # nine wavelengths of one beam: a full row of eight and a leftover single
     p9 = np.zeros((9, 4))
     p9[:, 3] = np.linspace(0.4, 0.8, 9)
-    bundles, rows, singles = plan_rows(p9, np.repeat(_frames([[0.0, 1.0, 0.0]]), 9, axis=0))
+    bundles, rows, singles = row_lists(p9, np.repeat(_frames([[0.0, 1.0, 0.0]]), 9, axis=0))
     assert rows == [0, 8] and bundles == list(range(8)) and singles == [8]
 
 

@@ -1,60 +1,22 @@
-"""Encircled / ensquared energy on the host: ``energy_of_plane``, the NumPy restatement of the contribution rule that
-tests/test_gpu_energy.py holds the kernels to, on values worked out by hand; the host summary and ``energy_radius``
-against a closed form; the parameter helpers of the Python front end; and the argument checks of rtpb_spot_energy /
-rtpb_energy_sweep / rtpb_energy_sweep_collimated (no GPU is touched).
+"""Encircled / ensquared energy on the host: ``energy_of_plane`` (tests/restatements.py), the NumPy restatement of
+the contribution rule that tests/test_gpu_energy.py holds the kernels to, on values worked out by hand; the host
+summary and ``energy_radius`` against a closed form; the parameter helpers of the Python front end; and the argument
+checks of rtpb_spot_energy / rtpb_energy_sweep / rtpb_energy_sweep_collimated (no GPU is touched).
 
 The rule (include/rtpb.h): a ray counts when x and y are finite; dx = x - cx, dy = y - cy, rho = sqrt(dx dx + dy dy),
 m = max(|dx|, |dy|), tc = rho * scale, ts = m * scale, each one rounded operation; inside the circle curve iff
 0 <= tc < nr in floating point, and only then hist[g, 0, int(tc)] += 1, otherwise outside[g, 0] += 1; the square
 curve the same with ts, hist[g, 1] and outside[g, 1]; farthest[g] = (max rho, max m) over the counting rays, 0.0 for
 none.  A centre that is not finite puts every counting ray outside both curves and leaves farthest untouched."""
-import ctypes
 
 import numpy as np
 import pytest
 
 from ray_trace_pb_amd import _capi as C
 from ray_trace_pb_amd import analysis
-
-
-def energy_of_plane(plane, group_size, params, nr):
-    """(hist (G, 2, nr) int32, outside (G, 2) int32, farthest (G, 2) float64) of an (N, 8) plane (float64 values: a
-    float32 plane widened), N = G * group_size, with params (G, 4) float64."""
-    plane = np.asarray(plane, dtype=np.float64)
-    p = np.asarray(params, dtype=np.float64).reshape(-1, 4)
-    G = plane.shape[0] // group_size
-    assert plane.shape[0] == G * group_size and p.shape[0] == G
-    x, y = plane[:, 0].reshape(G, group_size), plane[:, 1].reshape(G, group_size)
-    hist = np.zeros((G, 2, nr), dtype=np.int32)
-    outside = np.zeros((G, 2), dtype=np.int32)
-    farthest = np.zeros((G, 2))
-    with np.errstate(all="ignore"):
-        counts = np.isfinite(x) & np.isfinite(y)
-        centred = np.isfinite(p[:, 0:1]) & np.isfinite(p[:, 1:2])
-        dx, dy = x - p[:, 0:1], y - p[:, 1:2]
-        rho = np.sqrt(dx * dx + dy * dy)
-        m = np.maximum(np.abs(dx), np.abs(dy))
-        dist = np.stack((rho, m), axis=1)                               # (G, 2, group_size)
-        t = dist * p[:, 2].reshape(G, 1, 1)
-        inside = (counts & centred)[:, None, :] & (t >= 0) & (t < nr)
-    for g in range(G):
-        for k in range(2):
-            sel = inside[g, k]
-            np.add.at(hist[g, k], t[g, k, sel].astype(np.int64), 1)     # (truncation, as the C cast; in [0, nr))
-            outside[g, k] = np.count_nonzero(counts[g] & ~sel)
-            if centred[g, 0] and counts[g].any():
-                farthest[g, k] = dist[g, k, counts[g]].max()
-    return hist, outside, farthest
-
-
-def plane_of(x, y):
-    p = np.zeros((len(x), 8))
-    p[:, 0], p[:, 1], p[:, 5] = x, y, 1.0
-    return p
-
-
-def bits(a):
-    return np.ascontiguousarray(a, dtype=np.float64).view(np.int64)
+from flat_plans import flat_plan
+from parity import bits, plane_of
+from restatements import energy_of_plane
 
 
 # ------------------------------------------------------------------------------------------ the restatement
@@ -320,22 +282,6 @@ def test_automatic_params_fall_back_to_one(monkeypatch):
 
 
 # ------------------------------------------------------------------------------------------ the C ABI's checks
-def _flat_plan():
-    surf = (C.Surface * 1)()
-    surf[0].kind = C.RTPB_FLAT
-    surf[0].normal[:] = [0, 0, 1]
-    surf[0].input_axis[:] = [0, 0, 1]
-    surf[0].aperture = 1.0
-    surf[0].on_tol = 1e-12
-    mats = (C.Material * 2)()
-    for m in mats:
-        m.kind = C.RTPB_CONSTANT
-        m.c[0] = 1.0
-    plan = ctypes.c_void_p()
-    assert C.lib().rtpb_plan_create(surf, 1, mats, 2, C.RTPB_F64, ctypes.byref(plan)) == 0
-    return plan
-
-
 def test_energy_entry_points_validate_without_a_gpu():
     """rtpb_spot_energy / rtpb_energy_sweep / rtpb_energy_sweep_collimated: NULL pointers, non-positive sizes and a
     bad dtype are RTPB_E_INVALID with a message that names the call, nr past RTPB_MAX_ENERGY_BINS and groups past
@@ -356,7 +302,7 @@ def test_energy_entry_points_validate_without_a_gpu():
         assert lib.rtpb_spot_energy(*dict(ok, **bad).values()) == C.RTPB_E_LIMIT, bad
         assert b"spot-energy" in lib.rtpb_last_error(), bad
 
-    plan = _flat_plan()
+    plan = flat_plan()
     try:
         fan = dict(plan=plan, device=0, n_groups=2, group_params=p, n_thetas=30, nphis=10, center_ray=p, ex=p, ey=p,
                    theta_cos_sin=p, phi_cos_sin=p, params=p, nr=16, hist_out=p, outside_out=p, farthest_out=p,

@@ -7,7 +7,6 @@ rounded products: S_ab / n carries at most n * 2^-52 of sum|a b| / n <= sqrt(C_a
     |C_ab - exact| <= 16 * n * 2^-52 * (sqrt(C_aa * C_bb) + |mean_a * mean_b|),
 which for a variance is 16 * n * 2^-52 * (1 + mean^2 / variance) relative -- about 1e-11 for n = 4096 and zero
 means."""
-import ctypes
 
 import numpy as np
 import pytest
@@ -16,6 +15,7 @@ import ray_trace_pb_amd.materials as mat
 import ray_trace_pb_amd.raytrace as rt
 from ray_trace_pb_amd import _capi as C
 from ray_trace_pb_amd import analysis
+from flat_plans import flat_plan
 import systems
 
 EPS = 2.0 ** -52
@@ -146,22 +146,6 @@ def test_nan_paths_do_not_raise():
         assert np.isnan(e[k]).all(), k
 
 
-def _flat_plan():
-    surf = (C.Surface * 1)()
-    surf[0].kind = C.RTPB_FLAT
-    surf[0].normal[:] = [0, 0, 1]
-    surf[0].input_axis[:] = [0, 0, 1]
-    surf[0].aperture = 1.0
-    surf[0].on_tol = 1e-12
-    mats = (C.Material * 2)()
-    for m in mats:
-        m.kind = C.RTPB_CONSTANT
-        m.c[0] = 1.0
-    plan = ctypes.c_void_p()
-    assert C.lib().rtpb_plan_create(surf, 1, mats, 2, C.RTPB_F64, ctypes.byref(plan)) == 0
-    return plan
-
-
 def test_focus_entry_points_validate_without_a_gpu():
     """rtpb_focus_stats / rtpb_focus_sweep: NULL pointers, non-positive sizes and a workspace sized for the 7 spot
     columns are RTPB_E_INVALID before any device work (the pointers here are host memory, never read), and the
@@ -183,7 +167,7 @@ def test_focus_entry_points_validate_without_a_gpu():
     assert b"workspace too small" in lib.rtpb_last_error() and b"* 16 doubles" in lib.rtpb_last_error()
     assert lib.rtpb_focus_stats(*dict(ok, n_groups=65536, workspace_len=1 << 40).values()) == C.RTPB_E_LIMIT
 
-    plan = _flat_plan()
+    plan = flat_plan()
     try:
         nt, nph = 30, 10
         ok = dict(plan=plan, device=0, n_groups=G, group_params=p, n_thetas=nt, nphis=nph, center_ray=p, ex=p, ey=p,

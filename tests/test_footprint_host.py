@@ -2,7 +2,6 @@
 (no GPU is touched), the Python entry points' refusals, foot_ray / foot_merge (ray_trace_pb_amd/csrc/rtpb_foot.h) run
 on the CPU against the NumPy restatement (tests/foot_oracle.py), analysis.summarize_footprint against a direct per-ray
 calculation, and what tests/test_gpu_footprint.py assumes about the named sweep cases, checked with the oracle alone."""
-import functools
 import math
 
 import numpy as np
@@ -11,60 +10,13 @@ import pytest
 from ray_trace_pb_amd import _capi as C
 from ray_trace_pb_amd import _engine as E
 from ray_trace_pb_amd import analysis
-from oracle import rt_numpy as O
 import ray_trace_pb_amd.raytrace as rt
 import foot_harness as FH
 import foot_oracle as FO
-import sweep_cases as SC
 from native_harness import harness_trace
-from test_wavefront_host import _flat_plan
-
-CASES = ("c2", "tir", "stress", "c4", "c5_wide", "tangent", "xz")
-NT, NPH = 43, 7                        # 301 rays per group: two tiles, the second ragged
-
-
-@functools.lru_cache(maxsize=None)
-def case_fans(name, nt=NT, nph=NPH, theta=None):
-    """Each group's fan of a named sweep case at the given shape (and half-angle, the case's own by default), from
-    the reference generator, field-major."""
-    c = SC.case(name)
-    return tuple(rt.get_ray_fan(f, c.theta if theta is None else theta, nt, w, nphis=nph, center_ray=c.center_ray)
-                 for f in c.fields for w in c.wls)
-
-
-@functools.lru_cache(maxsize=None)
-def case_histories(name, nt=NT, nph=NPH, theta=None):
-    """The oracle's whole history per group at that shape: a tuple of (1 + 2 S, rays, 8) arrays (read-only)."""
-    c = SC.case(name)
-    hs = tuple(O.ray_trace(c.S, c.M, rays) for rays in case_fans(name, nt, nph, theta))
-    for h in hs:
-        h.setflags(write=False)
-    return hs
-
-
-@functools.lru_cache(maxsize=None)
-def case_columns(name, nt=NT, nph=NPH, tilted=False, theta=None):
-    """The restatement's (n_fields, n_wavelengths, S, 8) of a case on the oracle's histories, with the default frames
-    or with tilted_frames."""
-    c = SC.case(name)
-    fr = tilted_frames(c.system) if tilted else analysis.footprint_frames(c.system)
-    out = np.stack([FO.foot_columns(h, fr)[0] for h in case_histories(name, nt, nph, theta)])
-    out = out.reshape(len(c.fields), len(c.wls), len(c.S), 8)
-    out.setflags(write=False)
-    return out
-
-
-def tilted_frames(system):
-    """Frames with an off-axis origin and a tilted (orthonormal) basis, the same for every surface but the origin's z."""
-    fr = analysis.footprint_frames(system)
-    a, b = 0.3, -0.2
-    rx = np.array([[1, 0, 0], [0, math.cos(a), -math.sin(a)], [0, math.sin(a), math.cos(a)]])
-    ry = np.array([[math.cos(b), 0, math.sin(b)], [0, 1, 0], [-math.sin(b), 0, math.cos(b)]])
-    rot = ry @ rx
-    fr[:, 0:3] += (0.37, -0.21, 0.05)
-    fr[:, 3:6] = rot @ np.array([1.0, 0.0, 0.0])
-    fr[:, 6:9] = rot @ np.array([0.0, 1.0, 0.0])
-    return fr
+import sweep_cases as SC
+from flat_plans import flat_plan
+from foot_cases import CASES, NT, NPH, case_columns, case_fans, case_histories, tilted_frames
 
 
 def test_footprint_entry_points_validate_without_a_gpu():
@@ -96,7 +48,7 @@ def test_footprint_entry_points_validate_without_a_gpu():
     assert lib.rtpb_footprint_stats(*dict(ok, nsurf=64, frames=big.ctypes.data,
                                           workspace_len=1 << 40).values()) == C.RTPB_E_LIMIT
 
-    plan, plan32 = _flat_plan(C.RTPB_F64), _flat_plan(C.RTPB_F32)           # one surface
+    plan, plan32 = flat_plan(C.RTPB_F64), flat_plan(C.RTPB_F32)           # one surface
     one = np.zeros((1, 9))
     one_bad = one.copy()
     one_bad[0, 8] = -np.inf

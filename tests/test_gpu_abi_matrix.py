@@ -14,13 +14,11 @@ import pytest
 
 torch = pytest.importorskip("torch")
 
-import ray_trace_pb_amd.materials as mat  # noqa: E402
-import ray_trace_pb_amd.raytrace as rt  # noqa: E402
 from ray_trace_pb_amd import _capi as C  # noqa: E402
 from ray_trace_pb_amd import _engine as E  # noqa: E402
 from oracle import rt_numpy as O  # noqa: E402
-from parity import same_bits, CASES, GOLDEN  # noqa: E402
-from serialize import material_to_dict, surface_to_dict, system_from_json  # noqa: E402
+from parity import same_bits, CASES, golden_case  # noqa: E402
+from serialize import material_to_dict, surface_to_dict  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 DEV = torch.device("cuda:0")
@@ -28,12 +26,6 @@ PAD = 13                    # extra rays of padding per SoA field / AoS slot
 SENTINEL = 12345.0
 TORCH_DT = {C.RTPB_F64: torch.float64, C.RTPB_F32: torch.float32}
 NP_DT = {C.RTPB_F64: np.float64, C.RTPB_F32: np.float32}
-
-
-def _load(name):
-    d = np.load(f"{GOLDEN}/{name}.npz")
-    system, m0, m1 = system_from_json(rt, mat, str(d["system_json"]))
-    return system, [m0] + list(system.materials) + [m1], d["rays_in"], d["history"]
 
 
 def _selections(P, rng):
@@ -100,7 +92,8 @@ def knob(request):
 
 @pytest.mark.parametrize("name", CASES)
 def test_c_abi_variant_matrix(name, knob):
-    system, materials, rays, ref = _load(name)
+    system, m0, m1, rays, ref = golden_case(name)
+    materials = [m0] + list(system.materials) + [m1]
     n, S = rays.shape[0], len(system.surfaces)
     if S > C.RTPB_MAX_SURFACES:
         pytest.skip("segmented systems go through raytrace.trace_surfaces")

@@ -12,6 +12,7 @@ import ray_trace_pb_amd.raytrace as rt  # noqa: E402
 from ray_trace_pb_amd import analysis  # noqa: E402
 from oracle import rt_numpy as O  # noqa: E402
 from parity import same_bits, GOLDEN  # noqa: E402
+from restatements import fixed_order_sums  # noqa: E402
 from serialize import material_to_dict, surface_to_dict  # noqa: E402
 import systems  # noqa: E402
 
@@ -127,7 +128,7 @@ def test_fused_spot_sweep_bitwise_equals_unfused(case, dtype):
             [systems.OPM_WAVELENGTH, 0.9 * systems.OPM_WAVELENGTH], np.arcsin(1.35 / systems.OPM_N1)
     elif case == "xz":
         # tilted flats and PerfectLens steps in the x-z plane, Constant / Sellmeier / Vacuum media (test_axial.py)
-        from test_axial import tilted_xz_system
+        from sweep_cases import tilted_xz_system
         system, m0, m1 = tilted_xz_system()
         fields, wls, theta = [[0.0, 0.0, -3.0], [0.4, -0.3, -3.0]], [0.5, 0.6], 0.2
     elif case in ("tir", "tir_last"):
@@ -364,38 +365,6 @@ def test_spot_sweep_group_order_does_not_matter():
                                  nt, nph, device=DEV, groups_per_batch=7)      # batches of 7 mix field points
     for k in ("count", "centroid", "rms_radius"):
         assert same_bits(got[k], ref[k][fo][:, wo]), k
-
-
-def fixed_order_sums(plane, group_size, tile=256):
-    """The spot kernels' reduction restated in NumPy, operation for operation (csrc/rtpb_analysis.hip
-    spot_partial_kernel + spot_final_kernel, csrc/rtpb_sweep.hip sweep_kernel): per 256-ray tile a pairwise tree
-    (red[t] += red[t + w], w = 128 ... 1) of (1, x, y, z, x*x, y*y, x*y) over rays with finite x and y;
-    per group, thread t adds tiles t, t + 256, ... in order, then the same tree over the 256 threads."""
-    p = np.asarray(plane, dtype=np.float64).reshape(-1, group_size, plane.shape[-1])
-    G = p.shape[0]
-    tiles = -(-group_size // tile)
-    x, y, z = p[..., 0], p[..., 1], p[..., 2]
-    with np.errstate(invalid="ignore"):
-        ok = (x - x == 0.0) & (y - y == 0.0)
-    v = np.zeros((G, tiles * tile, 7))
-    with np.errstate(invalid="ignore", over="ignore"):
-        terms = np.stack((np.ones_like(x), x, y, z, x * x, y * y, x * y), -1)
-    v[:, :group_size] = np.where(ok[..., None], terms, 0.0)
-    v = v.reshape(G, tiles, tile, 7)
-    w = tile // 2
-    while w:
-        v[:, :, :w] = v[:, :, :w] + v[:, :, w:2 * w]
-        w //= 2
-    part = v[:, :, 0]                                            # (G, tiles, 7)
-    acc = np.zeros((G, tile, 7))
-    for c in range(0, tiles, tile):
-        blk = part[:, c:c + tile]
-        acc[:, :blk.shape[1]] = acc[:, :blk.shape[1]] + blk
-    w = tile // 2
-    while w:
-        acc[:, :w] = acc[:, :w] + acc[:, w:2 * w]
-        w //= 2
-    return acc[:, 0]
 
 
 def test_spot_stats_bitwise_vs_fixed_order_oracle():

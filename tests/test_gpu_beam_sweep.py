@@ -20,14 +20,12 @@ import ray_trace_pb_amd.materials as mat  # noqa: E402
 import ray_trace_pb_amd.raytrace as rt  # noqa: E402
 from ray_trace_pb_amd import analysis  # noqa: E402
 from oracle import rt_numpy as O  # noqa: E402
-from parity import same_bits  # noqa: E402
+from parity import assert_same_summary, same_bits, same_int64  # noqa: E402
 from serialize import material_to_dict, surface_to_dict  # noqa: E402
 import beam_cases as bc  # noqa: E402
 import sweep_cases as sc  # noqa: E402
 import wave_oracle as W  # noqa: E402
-from test_gpu_analysis import fixed_order_sums  # noqa: E402
-from test_gpu_focus import fixed_order_focus_sums  # noqa: E402
-from test_image_host import image_of_plane  # noqa: E402
+from restatements import fixed_order_focus_sums, fixed_order_sums, image_of_plane  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
@@ -48,17 +46,6 @@ def oracle_sums(name, dtype, nd=None, nph=None):
     spot.setflags(write=False)
     focus.setflags(write=False)
     return spot, focus
-
-
-def same_int64(got, ref):
-    got, ref = np.ascontiguousarray(got, dtype=np.float64), np.ascontiguousarray(ref, dtype=np.float64)
-    return got.shape == ref.shape and np.array_equal(got.view(np.int64), ref.view(np.int64))
-
-
-def assert_same_summary(got, exp):
-    assert got.keys() == exp.keys()
-    for k in exp:
-        assert same_bits(got[k], exp[k]), k
 
 
 def assert_spot_and_focus(c, spot, focus, ref_spot, ref_focus):

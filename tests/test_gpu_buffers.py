@@ -6,7 +6,6 @@ keep their stream-ordered pool: never handed to a new owner while work of the pr
 allocation stream or on a recorded stream -- can still touch them."""
 import ctypes
 import gc
-import os
 
 import numpy as np
 import pytest
@@ -16,17 +15,10 @@ torch = pytest.importorskip("torch")
 import ray_trace_pb_amd.materials as mat  # noqa: E402
 import ray_trace_pb_amd.raytrace as rt  # noqa: E402
 from ray_trace_pb_amd import _capi as C  # noqa: E402
-from parity import GOLDEN, same_bits  # noqa: E402
-from serialize import system_from_json  # noqa: E402
+from parity import golden_case, same_bits  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
-
-
-def golden(name):
-    d = np.load(os.path.join(GOLDEN, f"{name}.npz"))
-    system, m0, m1 = system_from_json(rt, mat, str(d["system_json"]))
-    return system, m0, m1, d["rays_in"], d["history"]
 
 
 def test_history_buffer_is_a_plain_cuda_tensor():
@@ -42,7 +34,7 @@ def test_history_buffer_is_a_plain_cuda_tensor():
 @pytest.mark.parametrize("name", ["c1_plano_convex", "c3_relay", "c4_opm", "stress"])
 @pytest.mark.parametrize("dtype", [None, "float32"])
 def test_trace_into_history_buffer_bitwise(name, dtype):
-    system, m0, m1, rays, ref = golden(name)
+    system, m0, m1, rays, ref = golden_case(name)
     x = torch.from_numpy(rays).to(DEV)
     tdt = torch.float32 if dtype else torch.float64
     out = rt.history_buffer(ref.shape, tdt, DEV)
@@ -58,7 +50,7 @@ def test_trace_into_history_buffer_bitwise(name, dtype):
 
 
 def test_out_validation():
-    system, m0, m1, rays, ref = golden("c1_plano_convex")
+    system, m0, m1, rays, ref = golden_case("c1_plano_convex")
     x = torch.from_numpy(rays).to(DEV)
     with pytest.raises(ValueError):
         system.ray_trace(x, m0, m1, out=torch.empty((1,) + ref.shape[1:], dtype=torch.float64, device=DEV))
@@ -145,7 +137,7 @@ def test_large_default_histories_are_pooled_buffers():
     """System.ray_trace without out= allocates histories >= POOLED_HISTORY_BYTES in the history pool: the same
     block comes back once the previous result is dropped, and the history is bit-identical to a trace into a
     torch.empty history."""
-    system, m0, m1, rays, ref = golden("c3_relay")
+    system, m0, m1, rays, ref = golden_case("c3_relay")
     fan = torch.empty((4 * 1000 * 1000, 8), dtype=torch.float64, device=DEV)
     rt.fan_into(fan, np.array([8.0, 0, 0]), np.pi / 180, 2000, 0.635, 2000)
     planes = 2 * len(system.surfaces) + 1
@@ -285,7 +277,7 @@ def test_reuse_waits_for_recorded_streams():
 def test_trace_on_a_side_stream_is_recorded():
     """trace_device records its launch stream on an out= history buffer allocated for another stream: the
     next owner of that memory waits for the trace."""
-    system, m0, m1, rays, ref = golden("c1_plano_convex")
+    system, m0, m1, rays, ref = golden_case("c1_plano_convex")
     from ray_trace_pb_amd import _engine as E
     C.check(C.lib().rtpb_buffer_trim())
     x = torch.from_numpy(np.tile(rays, (2000, 1))).to(DEV)
@@ -342,7 +334,7 @@ def test_torch_allocation_takes_the_pooled_memory():
     """A torch allocation outside the history pool that only fits in memory the pool caches succeeds: torch
     takes the pool's cached block (MemPool use_on_oom) -- here the drop-in call itself, with a history below
     POOLED_HISTORY_BYTES (a default-pool allocation)."""
-    system, m0, m1, rays, ref = golden("c3_relay")
+    system, m0, m1, rays, ref = golden_case("c3_relay")
     from ray_trace_pb_amd import _engine as E
     rt.trim_history_buffers()
     torch.cuda.synchronize()
@@ -375,7 +367,7 @@ def test_dead_va_limit_falls_back_to_plain_allocations():
     """Past rtpb_set_tuning("buffer_dead_va_limit") of never-reused virtual ranges, new history buffers are plain
     hipMalloc allocations (the bound on reserved address space): traced into, they read back bitwise."""
     from ray_trace_pb_amd import _engine as E
-    system, m0, m1, rays, ref = golden("c4_opm")
+    system, m0, m1, rays, ref = golden_case("c4_opm")
     x = torch.from_numpy(rays).to(DEV)
     lib = C.lib()
     rt.trim_history_buffers()
@@ -506,7 +498,7 @@ def test_trace_on_a_raw_stream_is_recorded_with_torch():
     (through torch.cuda.ExternalStream): a torch history traced on a delayed side stream and freed at once is not
     handed to the next allocation of its size before that trace has run -- which then reads back bitwise."""
     from ray_trace_pb_amd import _engine as E
-    system, m0, m1, rays, ref = golden("c3_relay")
+    system, m0, m1, rays, ref = golden_case("c3_relay")
     mats = [m0] + list(system.materials) + [m1]
     low = E.lower(system.surfaces, mats, lambda: np.unique(rays[:, 7]), C.RTPB_F64)
     x = torch.from_numpy(rays).to(DEV)

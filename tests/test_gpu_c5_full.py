@@ -46,7 +46,7 @@ def test_full_c5_sweep_groups_equal_groups_swept_alone():
 
 def test_full_c5_group_bitwise_vs_oracle():
     from oracle_pool import fan_final_plane
-    from test_gpu_analysis import fixed_order_sums
+    from restatements import fixed_order_sums
     system = systems.c5_system(rt, mat)
     field = systems.c5_field_points(8)[0]
     wl = systems.C5_WAVELENGTHS[0]

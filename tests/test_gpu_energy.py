@@ -1,6 +1,6 @@
 """GPU: encircled / ensquared energy -- rtpb_spot_energy on hand-built planes, and rtpb_energy_sweep /
 rtpb_energy_sweep_collimated (fused and unfused) on the cases of tests/sweep_cases.py and tests/beam_cases.py --
-against ``energy_of_plane``, the NumPy restatement of the contribution rule (tests/test_energy_host.py).  Counts are
+against ``energy_of_plane``, the NumPy restatement of the contribution rule (tests/restatements.py).  Counts are
 integers and ``farthest`` is a maximum: every comparison of counts is ``==`` on int arrays, every comparison of
 ``farthest`` is on bit patterns, no tolerance.
 
@@ -18,7 +18,8 @@ torch = pytest.importorskip("torch")
 from ray_trace_pb_amd import analysis  # noqa: E402
 import beam_cases as bc  # noqa: E402
 import sweep_cases as sc  # noqa: E402
-from test_energy_host import bits, energy_of_plane  # noqa: E402
+from parity import bits  # noqa: E402
+from restatements import energy_of_plane  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"

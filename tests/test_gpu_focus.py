@@ -11,46 +11,14 @@ import ray_trace_pb_amd.materials as mat  # noqa: E402
 import ray_trace_pb_amd.raytrace as rt  # noqa: E402
 from ray_trace_pb_amd import analysis  # noqa: E402
 from oracle import rt_numpy as O  # noqa: E402
-from parity import same_bits  # noqa: E402
-from serialize import material_to_dict, surface_to_dict  # noqa: E402
+from parity import oracle_dicts, same_bits  # noqa: E402
+from restatements import fixed_order_focus_sums  # noqa: E402
+from sweep_cases import sweep_case  # noqa: E402
 import systems  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
 NT, NPH = 301, 77                      # 23177 rays per group: 91 tiles, a ragged last one
-
-
-def fixed_order_focus_sums(plane, group_size, tile=256):
-    """The focus kernels' reduction restated in NumPy, operation for operation (csrc/rtpb_stats.h focus_ray /
-    focus_term, rtpb_analysis.hip focus_partial_kernel + spot_final_kernel, rtpb_sweep.hip sweep_kernel):
-    u = dx / dz, v = dy / dz; a ray counts when x, y, u and v are finite; per 256-ray tile a pairwise tree
-    (red[t] += red[t + w], w = 128 ... 1) of the sixteen terms; per group, thread t adds tiles t, t + 256, ... in order, then the same tree over the 256 threads."""
-    p = np.asarray(plane, dtype=np.float64).reshape(-1, group_size, plane.shape[-1])
-    G = p.shape[0]
-    tiles = -(-group_size // tile)
-    x, y, z = p[..., 0], p[..., 1], p[..., 2]
-    with np.errstate(invalid="ignore", divide="ignore", over="ignore"):
-        u, v = p[..., 3] / p[..., 5], p[..., 4] / p[..., 5]
-        ok = (x - x == 0.0) & (y - y == 0.0) & (u - u == 0.0) & (v - v == 0.0)
-        terms = np.stack((np.ones_like(x), x, y, z, x * x, y * y, x * y, u, v, u * u, v * v, u * v, x * u, y * v,
-                          x * v, y * u), -1)
-    acc = np.zeros((G, tiles * tile, 16))
-    acc[:, :group_size] = np.where(ok[..., None], terms, 0.0)
-    acc = acc.reshape(G, tiles, tile, 16)
-    w = tile // 2
-    while w:
-        acc[:, :, :w] = acc[:, :, :w] + acc[:, :, w:2 * w]
-        w //= 2
-    part = acc[:, :, 0]                                           # (G, tiles, 16)
-    fin = np.zeros((G, tile, 16))
-    for c in range(0, tiles, tile):
-        blk = part[:, c:c + tile]
-        fin[:, :blk.shape[1]] = fin[:, :blk.shape[1]] + blk
-    w = tile // 2
-    while w:
-        fin[:, :w] = fin[:, :w] + fin[:, w:2 * w]
-        w //= 2
-    return fin[:, 0]
 
 
 @pytest.mark.parametrize("dtype,tiles", [("float64", 5), ("float32", 5), ("float64", 300)])
@@ -84,18 +52,13 @@ def test_focus_stats_bitwise_vs_fixed_order_oracle(dtype, tiles):
         assert same_bits(summ[k], exp[k]), k
 
 
-def _dicts(system, m0, m1):
-    return ([surface_to_dict(s) for s in system.surfaces],
-            [material_to_dict(m) for m in [m0] + list(system.materials) + [m1]])
-
-
 @functools.lru_cache(maxsize=None)
 def c5_oracle_sums(dtype):
     """The oracle's final planes of the C5 fans (the reference generator's rays, rounded to the storage type going
     in and coming out) reduced in the kernels' order: (2 fields, 2 wavelengths, 16).  Computed once per dtype."""
     system = systems.c5_system(rt, mat)
     fields, wls = systems.c5_field_points(2)[1:3], [0.405, 0.635]
-    S, M = _dicts(system, mat.Constant(1), mat.Constant(1))
+    S, M = oracle_dicts(system, mat.Constant(1), mat.Constant(1))
     finals = []
     for f in fields:
         for w in wls:
@@ -126,38 +89,6 @@ def test_focus_sweep_sums_bitwise_vs_oracle(dtype):
     for k in exp:
         assert same_bits(summ[k], exp[k]), k
     assert timing["rays"] == 4 * NT * NPH and timing["per_device"][0]["kernel_ms"] > 0
-
-
-def sweep_case(case):
-    gpb = 4
-    if case == "c5":
-        system, m0, m1 = systems.c5_system(rt, mat), mat.Constant(1), mat.Constant(1)
-        fields, wls, theta = systems.c5_field_points(2), [0.405, 0.532, 0.785], 0.5 * np.pi / 180
-    elif case == "c5_bundles":
-        # batches of 13 groups over 2 fields x 9 wavelengths: bundle rows of 8 and 4 groups and single rows
-        system, m0, m1 = systems.c5_system(rt, mat), mat.Constant(1), mat.Constant(1)
-        fields, wls, theta = systems.c5_field_points(2), list(np.linspace(0.4, 0.8, 9)), 0.5 * np.pi / 180
-        gpb = 13
-    elif case == "c2":
-        system, m0, m1 = systems.c2_system(rt, mat), mat.Vacuum(), mat.Vacuum()
-        fields, wls, theta = [[0.0, 0.0, -5.0], [1.0, -2.0, -5.0]], list(systems.C2_WAVELENGTHS), 0.05
-    elif case == "c4":
-        system, m0, m1 = systems.c4_system(rt, mat), mat.Constant(systems.OPM_N1), mat.Vacuum()
-        fields, wls, theta = [[1e-3, 1e-3, 1e-3 * np.tan(np.pi / 6)], [0.0, 0.0, 0.0]], \
-            [systems.OPM_WAVELENGTH, 0.9 * systems.OPM_WAVELENGTH], np.arcsin(1.35 / systems.OPM_N1)
-    elif case == "xz":
-        from test_axial import tilted_xz_system
-        system, m0, m1 = tilted_xz_system()
-        fields, wls, theta = [[0.0, 0.0, -3.0], [0.4, -0.3, -3.0]], [0.5, 0.6], 0.2
-    elif case in ("tir", "tir_last"):
-        system, _, m0, m1 = systems.tir_prism(rt, mat)
-        if case == "tir_last":
-            system = rt.System(system.surfaces[:2], system.materials[:1])
-        fields, wls, theta = [[0.0, 0.0, -5.0], [2.0, -1.0, -5.0]], [0.45, 0.55, 0.7], 0.5
-    else:
-        system, m0, m1 = systems.stress_system(rt, mat), mat.Vacuum(), mat.Vacuum()
-        fields, wls, theta = [[0.0, 0.0, -10.0], [3.0, -2.0, -10.0], [-1.5, 2.5, -10.0]], [0.5, 0.6328], 0.3
-    return (system, m0, m1, fields, wls, theta, NT, NPH), gpb
 
 
 @pytest.mark.parametrize("dtype", ["float64", "float32"])
@@ -197,7 +128,7 @@ def test_c2_chromatic_focal_shift_and_astigmatism():
     assert (steps < 0).all() or (steps > 0).all()
     assert 0.05 < abs(z[-1] - z[0]) < 0.1
     assert (np.abs(summ["astigmatism"][0]) < 1e-9).all()
-    S, M = _dicts(system, mat.Vacuum(), mat.Vacuum())
+    S, M = oracle_dicts(system, mat.Vacuum(), mat.Vacuum())
     fin = np.concatenate([O.ray_trace(S, M, rt.get_ray_fan([1.0, -2.0, -5.0], 0.05, 61, w, nphis=12))[-1]
                           for w in wls])
     ref = analysis.summarize_focus(fixed_order_focus_sums(fin, 61 * 12))

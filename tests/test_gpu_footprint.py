@@ -15,7 +15,7 @@ from oracle import rt_numpy as O  # noqa: E402
 import beam_cases as BC  # noqa: E402
 import foot_oracle as FO  # noqa: E402
 import sweep_cases as SC  # noqa: E402
-from test_footprint_host import CASES, NT, NPH, case_columns, case_fans, tilted_frames  # noqa: E402
+from foot_cases import CASES, NT, NPH, case_columns, case_fans, tilted_frames  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"

@@ -13,6 +13,7 @@ torch = pytest.importorskip("torch")
 from ray_trace_pb_amd import _capi as C  # noqa: E402
 from ray_trace_pb_amd import analysis  # noqa: E402
 import griddata_oracle as G  # noqa: E402
+from parity import bits  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
@@ -24,28 +25,24 @@ def _interpolator(name):
     return analysis.GridInterpolator(G.case(name).points, DEV)
 
 
-def _bits(a):
-    return np.ascontiguousarray(a, dtype=np.float64).view(np.int64)
-
-
 def _explain(c, values, got, want):
     """The first grid point whose bits differ: the simplices that accept it and the one the kernel's value matches."""
     acc, c0, c1, c2 = c.acc_c
-    k = int(np.flatnonzero(_bits(got).ravel() != _bits(want).ravel())[0])
+    k = int(np.flatnonzero(bits(got).ravel() != bits(want).ravel())[0])
     iy, ix = divmod(k, len(c.xs))
     accepting = np.flatnonzero(acc[k])
     v = values[c.tri.simplices[accepting]]
     each = ((0.0 + c0[k, accepting] * v[:, 0]) + c1[k, accepting] * v[:, 1]) + c2[k, accepting] * v[:, 2]
-    used = accepting[_bits(each) == _bits(got).ravel()[k]]
+    used = accepting[bits(each) == bits(got).ravel()[k]]
     return (f"{c.name}: grid point {k} (ix {ix}, iy {iy}) = ({c.xs[ix]!r}, {c.ys[iy]!r}): kernel {got.ravel()[k]!r}, "
             f"restatement {want.ravel()[k]!r}; accepted by simplices {accepting.tolist()}, the kernel's value is "
-            f"that of {used.tolist()}; {int((_bits(got) != _bits(want)).sum())} points differ")
+            f"that of {used.tolist()}; {int((bits(got) != bits(want)).sum())} points differ")
 
 
 def _assert_phase(c, kind, got):
     want = c.phase(kind)
     assert got.shape == want.shape
-    if not np.array_equal(_bits(got), _bits(want)):
+    if not np.array_equal(bits(got), bits(want)):
         raise AssertionError(_explain(c, G.values_for(c.points, kind), got, want))
 
 
@@ -101,13 +98,13 @@ def test_pupil_field_mask_phase_and_values(name):
         assert none is None
         fld0, fld1, ph1 = fld0.cpu().numpy(), fld1.cpu().numpy(), ph1.cpu().numpy()
         _assert_phase(c, kind, ph1)
-        assert np.array_equal(_bits(fld0.view(np.float64)), _bits(fld1.view(np.float64)))
+        assert np.array_equal(bits(fld0.view(np.float64)), bits(fld1.view(np.float64)))
         off = G.field_off(c.phase(kind), c.xs, c.ys, radius)
         assert off.any() and not off.all()
         if name == "lattice":
             assert not off[on].any()
         assert np.array_equal(fld0 == 0, off), np.argwhere((fld0 == 0) != off)[:5]
-        assert not _bits(fld0.view(np.float64).reshape(off.shape + (2,))[off]).any()      # +0.0, both components
+        assert not bits(fld0.view(np.float64).reshape(off.shape + (2,))[off]).any()      # +0.0, both components
         ph = ph1[~off]
         dev = np.stack((fld0.real[~off], fld0.imag[~off]))
         host = np.stack((np.cos(ph), np.sin(ph)))

@@ -1,6 +1,6 @@
 """GPU: spot images -- rtpb_spot_image on hand-built planes and rtpb_image_sweep (fused and unfused) on the cases of
 tests/sweep_cases.py -- against ``image_of_plane``, the NumPy restatement of the contribution rule
-(tests/test_image_host.py).  Counts are integers: every comparison is ``==`` on int arrays, no tolerance.
+(tests/restatements.py).  Counts are integers: every comparison is ``==`` on int arrays, no tolerance.
 
 The sweeps' windows are computed here from the oracle's final planes (centroid +- k * RMS radius over the rays with
 finite x and y), so the expected image is the restatement applied to the oracle's planes and nothing of the device's
@@ -15,7 +15,7 @@ torch = pytest.importorskip("torch")
 
 from ray_trace_pb_amd import analysis  # noqa: E402
 import sweep_cases as sc  # noqa: E402
-from test_image_host import image_of_plane  # noqa: E402
+from restatements import image_of_plane  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
@@ -262,8 +262,8 @@ def test_poly6_plans_take_the_image_kernel_of_their_own(dtype):
     import ray_trace_pb_amd.materials as mat
     import ray_trace_pb_amd.raytrace as rt
     import systems
-    from test_gpu_poly6 import _poly_system
-    poly = _poly_system(systems.c3_system(rt, mat))
+    from beam_cases import poly_system
+    poly = poly_system(systems.c3_system(rt, mat))
     fields = np.array([[0.0, 0.0, 0.0], [8.0, 0.0, 0.0], [16.0, 0.0, 0.0]])
     args = (poly, mat.Vacuum(), mat.Vacuum(), fields, (0.532, 0.635), 10 * np.pi / 180, 65, 64)
     spot, _ = analysis.spot_sweep(*args, device=DEV, dtype=dtype)

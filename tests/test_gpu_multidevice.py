@@ -11,18 +11,11 @@ torch = pytest.importorskip("torch")
 import ray_trace_pb_amd.materials as mat  # noqa: E402
 import ray_trace_pb_amd.raytrace as rt  # noqa: E402
 from ray_trace_pb_amd import _capi as C  # noqa: E402
-from oracle import rt_numpy as O  # noqa: E402
-from serialize import material_to_dict, surface_to_dict  # noqa: E402
 import systems  # noqa: E402
-from parity import same_bits  # noqa: E402
+from parity import oracle_trace, same_bits  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
-
-
-def oracle(system, m0, m1, rays):
-    return O.ray_trace([surface_to_dict(s) for s in system.surfaces],
-                       [material_to_dict(m) for m in [m0] + list(system.materials) + [m1]], rays)
 
 
 def device_lists():
@@ -39,7 +32,7 @@ def test_torch_bundle_scattered_over_devices_is_bitwise_equal(devs):
     system, rays, m0, m1 = systems.stress(rt, mat)
     x = torch.from_numpy(rays).to(DEV)
     ref = system.ray_trace(x, m0, m1).cpu().numpy()
-    assert same_bits(ref, oracle(system, m0, m1, rays))
+    assert same_bits(ref, oracle_trace(system, m0, m1, rays))
     got = system.ray_trace(x, m0, m1, devices=devs)
     assert got.device == x.device and same_bits(got.cpu().numpy(), ref)
     parts = system.ray_trace(x, m0, m1, devices=devs, gather=False)
@@ -65,7 +58,7 @@ def test_per_device_fan_shards_traced_in_place(devs):
     assert np.array_equal(np.concatenate([s.cpu().numpy() for s in shards]), host)
     hist = system.ray_trace(shards, m0, m1, dtype="float32")
     assert isinstance(hist, list) and all(h.device == s.device for h, s in zip(hist, shards))
-    ref = oracle(system, m0, m1, host)
+    ref = oracle_trace(system, m0, m1, host)
     assert same_bits(np.concatenate([h.cpu().numpy() for h in hist], axis=1), ref.astype(np.float32))
 
 
@@ -79,7 +72,7 @@ def test_long_system_bitwise_vs_oracle(storage):
     assert S > C.RTPB_MAX_SURFACES
     rays = systems.long_rays(4099)
     m0, m1 = mat.Vacuum(), mat.Vacuum()
-    ref = oracle(system, m0, m1, rays)
+    ref = oracle_trace(system, m0, m1, rays)
     live = np.isfinite(ref[-1, :, 0]).sum()
     assert 0 < live < rays.shape[0]
     exp = ref if storage == "float64" else ref.astype(np.float32)

@@ -16,6 +16,7 @@ from ray_trace_pb_amd import _capi as C  # noqa: E402
 from ray_trace_pb_amd import _engine as E  # noqa: E402
 from oracle import rt_numpy as O  # noqa: E402
 from parity import same_bits, CASES, F32IN_CASES, GOLDEN, compare, load_case  # noqa: E402
+from parity import golden_case, oracle_trace  # noqa: E402
 from serialize import material_to_dict, surface_to_dict, system_from_json  # noqa: E402
 import systems  # noqa: E402
 
@@ -23,20 +24,9 @@ pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
 
 
-def build_case(name):
-    d = np.load(os.path.join(GOLDEN, f"{name}.npz"))
-    system, m0, m1 = system_from_json(rt, mat, str(d["system_json"]))
-    return system, m0, m1, d["rays_in"], d["history"]
-
-
-def oracle(system, m0, m1, rays):
-    return O.ray_trace([surface_to_dict(s) for s in system.surfaces],
-                       [material_to_dict(m) for m in [m0] + list(system.materials) + [m1]], rays)
-
-
 @pytest.mark.parametrize("name", CASES)
 def test_numpy_path_bitwise_vs_reference(name):
-    system, m0, m1, rays, ref = build_case(name)
+    system, m0, m1, rays, ref = golden_case(name)
     got = system.ray_trace(rays, m0, m1)
     assert isinstance(got, np.ndarray) and got.dtype == np.float64 and got.flags.c_contiguous
     assert got.shape == ref.shape
@@ -45,7 +35,7 @@ def test_numpy_path_bitwise_vs_reference(name):
 
 @pytest.mark.parametrize("name", CASES)
 def test_device_path_bitwise_vs_reference(name):
-    system, m0, m1, rays, ref = build_case(name)
+    system, m0, m1, rays, ref = golden_case(name)
     got = system.ray_trace(torch.from_numpy(rays).to(DEV), m0, m1)
     torch.cuda.synchronize()
     assert got.is_cuda and got.dtype == torch.float64
@@ -64,7 +54,7 @@ def test_input_ranks_and_extend_history():
 
 
 def test_surface_propagate_appends_two_planes():
-    system, m0, m1, rays, ref = build_case("c1_plano_convex")
+    system, m0, m1, rays, ref = golden_case("c1_plano_convex")
     mats = [m0] + list(system.materials) + [m1]
     h = rays
     for i, s in enumerate(system.surfaces):
@@ -78,7 +68,7 @@ def test_large_bundle_bitwise_vs_oracle_subsample():
     rays = systems.c2_rays(1_000_000)
     got = system.ray_trace(rays, mat.Vacuum(), mat.Vacuum())
     idx = np.random.default_rng(0).choice(rays.shape[0], 100_000, replace=False)
-    ref = oracle(system, mat.Vacuum(), mat.Vacuum(), rays[idx])
+    ref = oracle_trace(system, mat.Vacuum(), mat.Vacuum(), rays[idx])
     assert same_bits(got[:, idx], ref)
 
 
@@ -99,7 +89,7 @@ def test_full_size_properties_c2():
 
 
 def test_planes_final_and_subset_match_full():
-    system, m0, m1, rays, ref = build_case("c5_odt")
+    system, m0, m1, rays, ref = golden_case("c5_odt")
     fin = system.ray_trace(rays, m0, m1, planes="final")
     assert fin.shape == (1,) + ref.shape[1:]
     assert same_bits(fin[0], ref[-1])
@@ -111,7 +101,7 @@ def test_planes_final_and_subset_match_full():
 
 
 def test_soa_layout_matches_aos():
-    system, m0, m1, rays, ref = build_case("stress")
+    system, m0, m1, rays, ref = golden_case("stress")
     soa = system.ray_trace(torch.from_numpy(rays).to(DEV), m0, m1, layout="soa")
     assert tuple(soa.shape) == (ref.shape[0], 8, ref.shape[1])
     assert same_bits(soa.transpose(1, 2).cpu().numpy(), ref)
@@ -120,13 +110,13 @@ def test_soa_layout_matches_aos():
 @pytest.mark.parametrize("knob", [("aos_staging", 0), ("nt_stores", 0), ("stage_input", 1)])
 def test_tuning_variants_bitwise(knob):
     """Every store/load strategy is a pure data-movement change: bit-identical histories."""
-    system, m0, m1, rays, ref = build_case("stress")
+    system, m0, m1, rays, ref = golden_case("stress")
     lib = C.lib()
     default = {"aos_staging": 1, "nt_stores": 1, "stage_input": 0}[knob[0]]
     C.check(lib.rtpb_set_tuning(knob[0].encode(), knob[1]))
     try:
         r32 = rays.astype(np.float32)
-        ref32 = oracle(system, m0, m1, r32.astype(np.float64))
+        ref32 = oracle_trace(system, m0, m1, r32.astype(np.float64))
         for dt, r, exp in (("float64", rays, ref), ("float32", r32, ref32.astype(np.float32)),
                            ("float32", rays, ref.astype(np.float32)), ("float64", r32, ref32)):
             got = system.ray_trace(torch.from_numpy(r).to(DEV), m0, m1, dtype=dt).cpu().numpy()
@@ -139,10 +129,10 @@ def test_lens_and_flat_kernel_variant_every_store_path():
     """C4's OPM -- PerfectLens and Flat surfaces in the axial and x-z forms only, so its plan takes the lens-and-flat
     kernel variant (rtpb_plan::feat 33, dispatch_kind's kKindsLensFlat) -- through every store path of that variant:
     float64 / float32 storage, AOS and SoA, the final plane, a plane subset, float32 input and each tuning knob."""
-    system, m0, m1, rays, ref = build_case("c4_opm")
+    system, m0, m1, rays, ref = golden_case("c4_opm")
     assert {type(s).__name__ for s in system.surfaces} == {"PerfectLens", "FlatSurface"}
     r32 = rays.astype(np.float32)
-    ref32 = oracle(system, m0, m1, r32.astype(np.float64))
+    ref32 = oracle_trace(system, m0, m1, r32.astype(np.float64))
     lib = C.lib()
 
     def run(r, **kw):
@@ -170,7 +160,7 @@ def test_lens_and_flat_kernel_variant_every_store_path():
 
 def test_sharded_host_trace_is_bitwise_equal():
     """Ray sharding over devices (here: two shards on GPU 0) gives exactly the unsharded history."""
-    system, m0, m1, rays, ref = build_case("stress")
+    system, m0, m1, rays, ref = golden_case("stress")
     got = system.ray_trace(rays, m0, m1, devices=[0, 0])
     assert same_bits(got, ref)
     got3 = system.ray_trace(rays, m0, m1, devices=[0, 0, 0])
@@ -182,7 +172,7 @@ def test_fuzz_sharded_host_trace_and_float32_storage(name):
     """The seeded random systems through rtpb_trace_host split over three shards of GPU 0 (host threads,
     chunked pipeline), float64 and float32 storage, all and final planes: the reference's history
     (rounded once for float32) bit for bit."""
-    system, m0, m1, rays, ref = build_case(name)
+    system, m0, m1, rays, ref = golden_case(name)
     assert same_bits(system.ray_trace(rays, m0, m1, devices=[0, 0, 0]), ref)
     got32 = system.ray_trace(rays, m0, m1, dtype="float32", devices=[0, 0, 0])
     assert same_bits(got32, ref.astype(np.float32))
@@ -193,7 +183,7 @@ def test_fuzz_sharded_host_trace_and_float32_storage(name):
 def test_user_material_subclass_lowers_to_table():
     """A Material subclass overriding n() (the reference's plugin point) traces on the GPU via a
     per-wavelength table, bit-identical to evaluating its n() per ray."""
-    system, m0, m1, rays, ref = build_case("stress")
+    system, m0, m1, rays, ref = golden_case("stress")
     assert any(type(m).__name__ == "Cauchy" for m in system.materials)
     got = system.ray_trace(rays, m0, m1)
     assert same_bits(got, ref)
@@ -205,7 +195,7 @@ def test_float32_storage_of_float64_input_is_the_rounded_reference(name):
     history is the reference's float64 history rounded once to float32 -- bit for bit, NaN pattern
     included (no ray the reference keeps is lost), hence within 1e-5 column-scaled with no mask flip.
     NumPy and torch paths, all planes / final plane / SoA (the mixed-type kernel variants)."""
-    system, m0, m1, rays, ref = build_case(name)
+    system, m0, m1, rays, ref = golden_case(name)
     exp = ref.astype(np.float32)
     got = system.ray_trace(rays, m0, m1, dtype="float32")
     assert got.dtype == np.float32 and same_bits(got, exp)
@@ -229,9 +219,9 @@ def test_float32_input_bitwise_vs_oracle_on_widened_input(name):
     """float32 rays are widened exactly in the kernel (as NumPy promotes them) and traced in float64:
     float32 storage gives the oracle's float64 trace of the widened input rounded once, float64 storage
     gives it exactly."""
-    system, m0, m1, rays, ref = build_case(name)
+    system, m0, m1, rays, ref = golden_case(name)
     r32 = rays.astype(np.float32)
-    full = oracle(system, m0, m1, r32.astype(np.float64))
+    full = oracle_trace(system, m0, m1, r32.astype(np.float64))
     exp = full.astype(np.float32)
     got = system.ray_trace(r32, m0, m1, dtype="float32")
     assert got.dtype == np.float32
@@ -250,7 +240,7 @@ def test_float32_input_vs_reference_run_on_float32_input(name):
     identical, values within 1e-6 column-scaled for float64 storage and 1e-5 for float32 storage.  (Not
     bitwise: NumPy evaluates a few first-surface sub-expressions of the reference in float32, see
     tests/test_oracle_golden.py.)"""
-    system, m0, m1, rays, ref = build_case(name)
+    system, m0, m1, rays, ref = golden_case(name)
     assert rays.dtype == np.float32
     for dt, rtol in ((None, 1e-6), ("float32", 1e-5)):
         got = system.ray_trace(rays, m0, m1, dtype=dt)
@@ -268,7 +258,7 @@ def test_float32_storage_c4_fan_40k_rays():
     args = ([1e-3, 1e-3, 1e-3 * np.tan(theta)], np.arcsin(1.35 / systems.OPM_N1), 201, systems.OPM_WAVELENGTH)
     fan = rt.get_ray_fan(*args, nphis=200)
     assert fan.shape == (40200, 8) and fan.dtype == np.float64
-    ref = oracle(system, m0, m1, fan)
+    ref = oracle_trace(system, m0, m1, fan)
     killed = np.isnan(ref[-1]).all(axis=1).sum()
     assert 0 < killed < fan.shape[0]                      # the NA clip is exercised
     got = system.ray_trace(fan, m0, m1, dtype="float32")
@@ -317,7 +307,7 @@ def test_device_ray_fan_bitwise_vs_host_generator(kw):
 
 
 def test_errors_are_loud():
-    system, m0, m1, rays, _ = build_case("c1_plano_convex")
+    system, m0, m1, rays, _ = golden_case("c1_plano_convex")
     with pytest.raises(ValueError):
         system.ray_trace(rays, m0, m1, planes=[99])
     with pytest.raises(ValueError):
@@ -327,7 +317,7 @@ def test_errors_are_loud():
 
 
 def test_empty_bundle():
-    system, m0, m1, rays, _ = build_case("c1_plano_convex")
+    system, m0, m1, rays, _ = golden_case("c1_plano_convex")
     out = system.ray_trace(rays[:0], m0, m1)
     assert out.shape == (7, 0, 8)
     out = system.ray_trace(torch.zeros((0, 8), dtype=torch.float64, device=DEV), m0, m1)
@@ -335,7 +325,7 @@ def test_empty_bundle():
 
 
 def test_timing_counters():
-    system, m0, m1, rays, _ = build_case("c2_achromat")
+    system, m0, m1, rays, _ = golden_case("c2_achromat")
     lib = C.lib()
     lib.rtpb_timing_enable(1)
     x = torch.from_numpy(rays).to(DEV)
@@ -351,7 +341,7 @@ def test_user_surface_with_own_propagate_runs_between_gpu_segments():
     """A Surface subclass supplying its own propagate (the reference's plugin point) is called with the
     growing history; built-in surfaces around it run as fused GPU traces.  Here the user surface is a
     FlatSurface whose propagate delegates to the oracle, so the whole history must equal the reference."""
-    system, m0, m1, rays, ref = build_case("c5_odt")
+    system, m0, m1, rays, ref = golden_case("c5_odt")
 
     class OracleFlat(rt.FlatSurface):
         calls = 0
@@ -488,7 +478,7 @@ def _hooked(system, spheres=True):
 def test_user_geometry_hooks_bitwise_vs_reference(name):
     """User geometry hooks + GPU front-side / Snell / reflection reproduce the reference history
     exactly, including misses, back-facing rays, TIR, aperture clipping and user materials."""
-    system, m0, m1, rays, ref = build_case(name)
+    system, m0, m1, rays, ref = golden_case(name)
     hooked = _hooked(system)
     n_user = sum(s._rtpb_user_geometry() for s in hooked.surfaces)
     assert n_user >= 1
@@ -505,7 +495,7 @@ def test_user_geometry_hooks_bitwise_vs_reference(name):
 
 def test_user_geometry_hooks_on_device_history():
     """torch CUDA histories: the hooks receive torch tensors and the result stays on the device."""
-    system, m0, m1, rays, ref = build_case("c4_mirror")
+    system, m0, m1, rays, ref = golden_case("c4_mirror")
     hooked = _hooked(system, spheres=False)
     assert any(s._rtpb_user_geometry() for s in hooked.surfaces)
     got = hooked.ray_trace(torch.from_numpy(rays).to(DEV), m0, m1)
@@ -529,7 +519,7 @@ def test_material_dispersion_bitwise_over_wavelength_sweep(material):
     rays[:, 3:6] = d / np.linalg.norm(d, axis=1)[:, None]
     rays[:, 7] = rng.uniform(0.35, 2.0, n)
     got = system.ray_trace(rays, mat.Vacuum(), mat.Vacuum())
-    ref = oracle(system, mat.Vacuum(), mat.Vacuum(), rays)
+    ref = oracle_trace(system, mat.Vacuum(), mat.Vacuum(), rays)
     assert same_bits(got, ref)
 
 
@@ -553,12 +543,12 @@ def test_table_materials_lds_and_global_lookup(n_wl):
     wls = np.linspace(0.4, 1.6, n_wl)
     rays[:, 7] = wls[rng.integers(0, n_wl, n)]
     m0, m1 = mat.Vacuum(), mat.Vacuum()
-    ref = oracle(system, m0, m1, rays)
+    ref = oracle_trace(system, m0, m1, rays)
     assert same_bits(system.ray_trace(rays, m0, m1), ref)
     x = torch.from_numpy(rays).to(DEV)
     assert same_bits(system.ray_trace(x, m0, m1).cpu().numpy(), ref)
     r32 = rays.astype(np.float32)
-    exp32 = oracle(system, m0, m1, r32.astype(np.float64)).astype(np.float32)
+    exp32 = oracle_trace(system, m0, m1, r32.astype(np.float64)).astype(np.float32)
     got32 = system.ray_trace(torch.from_numpy(r32).to(DEV), m0, m1, dtype="float32").cpu().numpy()
     assert same_bits(got32, exp32)
     # float64 rays into float32 storage: the table keys are the rays' own float64 wavelengths
@@ -577,7 +567,7 @@ def test_more_than_2_31_rays_in_one_launch():
     """Maximum sizes: one trace of 2^31 + 4633 rays (int64 ray indexing, > 2^25 workgroups), float32
     storage, final plane only (68.7 GB in + 68.7 GB out of HBM).  Rays on both sides of index 2^31 and
     at the very end are bit-exact against the oracle on the same float32 input."""
-    system, m0, m1, _, _ = build_case("c1_plano_convex")
+    system, m0, m1, _, _ = golden_case("c1_plano_convex")
     nt = nph = 46341                                  # 46341^2 = 2^31 + 4633
     n = nt * nph
     assert n > 2 ** 31
@@ -591,7 +581,7 @@ def test_more_than_2_31_rays_in_one_launch():
     got = out[0].index_select(0, idx).cpu().numpy()
     del rays, out
     torch.cuda.empty_cache()
-    ref = oracle(system, m0, m1, r_in)[-1].astype(np.float32)
+    ref = oracle_trace(system, m0, m1, r_in)[-1].astype(np.float32)
     assert same_bits(got, ref)
     assert np.isfinite(got[:, 0]).sum() > 1000        # not an all-NaN comparison
 
@@ -601,7 +591,7 @@ def test_concurrent_host_threads_give_identical_results():
     cache, one device): every result equals its single-threaded trace."""
     import threading
     cases = ["c1_plano_convex", "c2_achromat", "c4_mirror", "stress"]
-    built = [build_case(c) for c in cases]
+    built = [golden_case(c) for c in cases]
     want = [b[4] for b in built]
     got = [[None] * 3 for _ in cases]
     errors = []

@@ -11,8 +11,8 @@ torch = pytest.importorskip("torch")
 
 import ray_trace_pb_amd.materials as mat  # noqa: E402
 import ray_trace_pb_amd.raytrace as rt  # noqa: E402
-from ray_trace_pb_amd import _capi as C  # noqa: E402
 from ray_trace_pb_amd import analysis  # noqa: E402
+from beam_cases import poly_system  # noqa: E402
 from parity import same_bits, compare  # noqa: E402
 import systems  # noqa: E402
 
@@ -20,22 +20,9 @@ pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
 
 
-class Ebaf11Poly(mat.Ebaf11):
-    """Ebaf11 sent to the kernels as RTPB_POLY6 (device pow) instead of a host table."""
-
-    def _rtpb_lower(self):
-        return C.RTPB_POLY6, tuple(self.params)
-
-
-def _poly_system(system):
-    mats = [Ebaf11Poly() if type(m) is mat.Ebaf11 else m for m in system.materials]
-    assert any(isinstance(m, Ebaf11Poly) for m in mats)
-    return rt.System(system.surfaces, mats)
-
-
 def test_poly6_trace_matches_table_trace():
     system = systems.c3_system(rt, mat)
-    poly = _poly_system(system)
+    poly = poly_system(system)
     m0, m1 = mat.Vacuum(), mat.Vacuum()
     rays = systems.c3_rays(rt, 41, 40)
     x = torch.from_numpy(rays).to(DEV)
@@ -56,7 +43,7 @@ def test_poly6_spot_sweep_matches_table_sweep(deg):
     """deg=10 vignettes 12 % of the rays at intermediate surfaces: a lane whose first ray dies there keeps
     evaluating its second ray's media at the group's wavelength (not at the dead ray's NaN)."""
     system = systems.c3_system(rt, mat)
-    poly = _poly_system(system)
+    poly = poly_system(system)
     fields = np.array([[0.0, 0.0, 0.0], [8.0, 0.0, 0.0], [16.0, 0.0, 0.0]])
     wls = (0.532, 0.635)
     th = deg * np.pi / 180

@@ -1,5 +1,5 @@
 """GPU: rtpb_huygens_psf and analysis.huygens_psf / collimated_huygens_psf against the NumPy restatement of the rule
-(tests/test_psf_host.py psf_of_plane), within the bound derived there: each of re and im within
+(tests/restatements.py psf_of_plane), within the bound derived there: each of re and im within
 norm_abs * (8e-15 + 4 * N * 2^-53), the norm within N * 2^-53 * norm_abs, rtol 0.  Nothing of the device's output
 enters an expectation: the hand-built planes are inputs, and the end-to-end cases take the oracle's final planes
 (tests/sweep_cases.py, tests/beam_cases.py), references from the rays that survive in them (wave_oracle.
@@ -19,7 +19,8 @@ import beam_cases as bc  # noqa: E402
 import sweep_cases as sc  # noqa: E402
 import wave_cases as wc  # noqa: E402
 import wave_oracle as W  # noqa: E402
-from test_psf_host import bound, psf_of_plane  # noqa: E402
+from restatements import bound, psf_of_plane  # noqa: E402
+from wave_refs import hand_plane, hand_refs  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
@@ -30,40 +31,12 @@ GROUP_SIZES = (1, 63, 64, 65, 255, 256, 257, 600)
 SHAPES = ((1, 1), (5, 3), (16, 16), (17, 16), (33, 33))
 
 
-def hand_refs():
-    """An ordinary reference, one with another kf, and a NaN reference."""
-    return np.array([[0.1, -0.2, 5.0, 0.01, 0.0, 0.99995, 1000.0, 2.0],
-                     [-0.3, 0.1, 5.0, 0.0, -0.02, 0.9998, -250.0, 1.3],
-                     [np.nan] * 8])
-
-
 def hand_windows(nx, ny):
     """Square pixels, sx != sy, and square again (the NaN reference's: never used)."""
     w = np.concatenate((analysis.psf_windows(6.0, nx, ny), analysis.psf_windows(9.0, nx, ny),
                         analysis.psf_windows(6.0, nx, ny)))
     w[1, 3] = 0.7 * w[1, 3]
     return w
-
-
-@functools.lru_cache(maxsize=None)
-def hand_plane(group_size):
-    """(3 * group_size, 8): rows near each group's reference point with directions within 0.05 of its pivot and an
-    OPD spread over +-3 waves (so rint matters); every fourth row dead -- a NaN x, an infinite y, a NaN direction, a
-    NaN phase in turn.  Read-only."""
-    rng = np.random.default_rng(1000 + group_size)
-    refs = hand_refs()
-    refs[2] = refs[0]                                          # (the third group's rays are as alive as the first's)
-    p = np.empty((3, group_size, 8))
-    for g in range(3):
-        p[g, :, 0:3] = refs[g, 0:3] + rng.uniform(-1e-3, 1e-3, (group_size, 3))
-        p[g, :, 3:6] = refs[g, 3:6] + rng.uniform(-0.05, 0.05, (group_size, 3))
-        p[g, :, 6] = refs[g, 6] + 2 * np.pi * rng.uniform(-3.0, 3.0, group_size)
-        p[g, :, 7] = 0.5
-    for k, (col, val) in enumerate(((0, np.nan), (1, np.inf), (4, np.nan), (6, np.nan))):
-        p[:, 3 + 4 * k::16, col] = val
-    p = p.reshape(-1, 8)
-    p.setflags(write=False)
-    return p
 
 
 def hand_weights(group_size):

@@ -11,16 +11,14 @@ compares 0 with 0.  The same comparison runs for the unfused pipeline (fan kerne
 statistics), so a failure says which of the two paths left the reference."""
 import functools
 
-import numpy as np
 import pytest
 
 torch = pytest.importorskip("torch")
 
 from ray_trace_pb_amd import analysis  # noqa: E402
-from parity import same_bits  # noqa: E402
+from parity import same_bits, same_int64  # noqa: E402
 import sweep_cases as sc  # noqa: E402
-from test_gpu_analysis import fixed_order_sums  # noqa: E402
-from test_gpu_focus import fixed_order_focus_sums  # noqa: E402
+from restatements import fixed_order_focus_sums, fixed_order_sums  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
@@ -38,11 +36,6 @@ def oracle_sums(name, dtype):
     spot.setflags(write=False)
     focus.setflags(write=False)
     return spot, focus
-
-
-def same_int64(got, ref):
-    got, ref = np.ascontiguousarray(got, dtype=np.float64), np.ascontiguousarray(ref, dtype=np.float64)
-    return got.shape == ref.shape and np.array_equal(got.view(np.int64), ref.view(np.int64))
 
 
 @pytest.mark.parametrize("fused", [True, False], ids=["fused", "unfused"])

@@ -13,10 +13,8 @@ import ray_trace_pb_amd.materials as mat  # noqa: E402
 import ray_trace_pb_amd.raytrace as rt  # noqa: E402
 from ray_trace_pb_amd import _capi as C  # noqa: E402
 from ray_trace_pb_amd import _engine as E  # noqa: E402
-from oracle import rt_numpy as O  # noqa: E402
-from serialize import material_to_dict, surface_to_dict  # noqa: E402
 import systems  # noqa: E402
-from parity import same_bits  # noqa: E402
+from parity import oracle_trace, same_bits  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
@@ -40,11 +38,6 @@ def _rays(n, wls, seed):
     return rays
 
 
-def _oracle(system, m0, m1, rays):
-    return O.ray_trace([surface_to_dict(s) for s in system.surfaces],
-                       [material_to_dict(m) for m in [m0] + list(system.materials) + [m1]], rays)
-
-
 @pytest.mark.parametrize("variant", ["indexed", "lds", "global"])
 def test_miss_flag_every_table_variant(variant):
     """The flag is 0 when every ray's wavelength is a key and 1 otherwise (a foreign wavelength, or a NaN
@@ -64,7 +57,7 @@ def test_miss_flag_every_table_variant(variant):
         flag = torch.zeros(1, dtype=torch.int32, device=DEV)
         out = E.trace_device(low, x, sel, miss=flag)
         assert int(flag.item()) == 0
-        assert same_bits(out.cpu().numpy(), _oracle(system, m0, m1, rays))
+        assert same_bits(out.cpu().numpy(), oracle_trace(system, m0, m1, rays))
         for bad in (0.5123, np.nan):
             r2 = rays.copy()
             r2[1777, 7] = bad
@@ -79,7 +72,7 @@ def test_miss_flag_every_table_variant(variant):
         flag.zero_()
         out3 = E.trace_device(low_nan, torch.from_numpy(r3).to(DEV), sel, miss=flag)
         assert int(flag.item()) == 0
-        assert same_bits(out3.cpu().numpy(), _oracle(system, m0, m1, r3))
+        assert same_bits(out3.cpu().numpy(), oracle_trace(system, m0, m1, r3))
         # no flag pointer: the plain launch
         E.trace_device(low, x, sel)
     finally:
@@ -100,7 +93,7 @@ def test_optimistic_keys_reused_and_rescanned_on_a_miss(monkeypatch):
 
     def check(rays, dtype=None):
         got = system.ray_trace(torch.from_numpy(rays).to(DEV), m0, m1, dtype=dtype).cpu().numpy()
-        ref = _oracle(system, m0, m1, rays)
+        ref = oracle_trace(system, m0, m1, rays)
         assert same_bits(got, ref if dtype is None else ref.astype(np.float32))
 
     check(_rays(2049, [0.5, 0.6, 0.7], 1))
@@ -119,7 +112,7 @@ def test_optimistic_keys_reused_and_rescanned_on_a_miss(monkeypatch):
     rays = _rays(513, [0.9], 7)
     hist = system.ray_trace(torch.from_numpy(rays).to(DEV), m0, m1)
     ext = system.ray_trace(hist, m0, m1).cpu().numpy()
-    ref = _oracle(system, m0, m1, rays)
+    ref = oracle_trace(system, m0, m1, rays)
     assert same_bits(ext[:ref.shape[0]], ref) and ext.shape[0] == 2 * ref.shape[0] - 1
     fin = system.ray_trace(torch.from_numpy(rays).to(DEV), m0, m1, planes="final").cpu().numpy()
     assert same_bits(fin[0], ref[-1])

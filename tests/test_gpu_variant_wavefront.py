@@ -19,24 +19,13 @@ torch = pytest.importorskip("torch")
 from ray_trace_pb_amd import analysis  # noqa: E402
 import ray_trace_pb_amd.materials as mat  # noqa: E402
 import ray_trace_pb_amd.raytrace as rt  # noqa: E402
-from parity import same_bits  # noqa: E402
+from parity import assert_same_summary, same_bits, same_int64  # noqa: E402
 import systems  # noqa: E402
 import variant_cases as vc  # noqa: E402
 import variant_wave_cases as vw  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
-
-
-def same_int64(got, ref):
-    got, ref = np.ascontiguousarray(got, dtype=np.float64), np.ascontiguousarray(ref, dtype=np.float64)
-    return got.shape == ref.shape and np.array_equal(got.view(np.int64), ref.view(np.int64))
-
-
-def assert_same_summary(got, exp):
-    assert got.keys() == exp.keys()
-    for k in exp:
-        assert same_bits(got[k], exp[k]), k
 
 
 @pytest.mark.parametrize("fused", [True, False], ids=["fused", "unfused"])

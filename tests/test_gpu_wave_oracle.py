@@ -17,18 +17,13 @@ import pytest
 torch = pytest.importorskip("torch")
 
 from ray_trace_pb_amd import analysis  # noqa: E402
-from parity import same_bits  # noqa: E402
+from parity import same_bits, same_int64  # noqa: E402
 import sweep_cases as sc  # noqa: E402
 import variant_wave_cases as vw  # noqa: E402
 import wave_cases as wc  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
-
-
-def same_int64(got, ref):
-    got, ref = np.ascontiguousarray(got, dtype=np.float64), np.ascontiguousarray(ref, dtype=np.float64)
-    return got.shape == ref.shape and np.array_equal(got.view(np.int64), ref.view(np.int64))
 
 
 @pytest.mark.parametrize("fused", [True, False], ids=["fused", "unfused"])

@@ -12,29 +12,18 @@ import ray_trace_pb_amd.materials as mat  # noqa: E402
 import ray_trace_pb_amd.raytrace as rt  # noqa: E402
 from ray_trace_pb_amd import analysis  # noqa: E402
 from oracle import rt_numpy as O  # noqa: E402
-from parity import same_bits  # noqa: E402
-from serialize import material_to_dict, surface_to_dict  # noqa: E402
+from parity import assert_same_summary, oracle_dicts, same_bits  # noqa: E402
 import sweep_cases as SC  # noqa: E402
 import systems  # noqa: E402
 import wave_oracle as W  # noqa: E402
-from test_gpu_focus import fixed_order_focus_sums, sweep_case  # noqa: E402
-from test_wavefront_host import ALIVE, case_refs  # noqa: E402
+from restatements import fixed_order_focus_sums  # noqa: E402
+from sweep_cases import sweep_case  # noqa: E402
+from wave_refs import ALIVE, case_refs  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
 NT, NPH = 301, 77                      # 23177 rays per group: 91 tiles, a ragged last one
 EPS = 2.0 ** -52
-
-
-def _dicts(system, m0, m1):
-    return ([surface_to_dict(s) for s in system.surfaces],
-            [material_to_dict(m) for m in [m0] + list(system.materials) + [m1]])
-
-
-def assert_same_summary(got, exp):
-    assert got.keys() == exp.keys()
-    for k in exp:
-        assert same_bits(got[k], exp[k]), k
 
 
 @pytest.mark.parametrize("tiles", [5, 300])
@@ -85,7 +74,7 @@ def c5_oracle():
     the references built from them and the oracle's chief rays.  Computed once."""
     system, one = systems.c5_system(rt, mat), mat.Constant(1)
     fields, wls, theta = systems.c5_field_points(2)[1:3], [0.405, 0.635], 0.5 * np.pi / 180
-    S, M = _dicts(system, one, one)
+    S, M = oracle_dicts(system, one, one)
     fin = np.concatenate([O.ray_trace(S, M, rt.get_ray_fan(f, theta, NT, w, nphis=NPH))[-1]
                           for f in fields for w in wls])
     refs = W.oracle_refs(S, M, one, fields, wls, fin)
@@ -198,7 +187,7 @@ def test_perfect_lens_pair_is_aberration_free_and_defocus_is_the_closed_form():
     system = rt.System([rt.PerfectLens(f1, [0, 0, f1], [0, 0, 1], 0.6),
                         rt.PerfectLens(f2, [0, 0, f1 + sep], [0, 0, 1], 0.6),
                         rt.FlatSurface([0, 0, z_focus - gap], [0, 0, 1], 50.0)], [vac, vac])
-    S, M = _dicts(system, vac, vac)
+    S, M = oracle_dicts(system, vac, vac)
     fields = np.array([[0.0, 0.0, 0.0], [0.3, -0.2, 0.0]])
     theta, nt, nph = 0.3, 61, 12
     kf = float(vac.n(wl)) / wl

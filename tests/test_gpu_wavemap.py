@@ -1,6 +1,6 @@
 """GPU: wavefront maps -- rtpb_wavefront_map on hand-built planes, and rtpb_wavefront_map_sweep /
 rtpb_wavefront_map_sweep_collimated (fused and unfused) on the cases of tests/sweep_cases.py and tests/beam_cases.py --
-against ``wavemap_of_plane``, the NumPy restatement of the rule (tests/test_wavemap_host.py).  The map is made of
+against ``wavemap_of_plane``, the NumPy restatement of the rule (tests/restatements.py).  The map is made of
 integers and ``farthest`` is a maximum: every comparison of counts and sums is ``==`` on int arrays, every comparison
 of ``farthest`` is on bit patterns, no tolerance.
 
@@ -20,8 +20,9 @@ import beam_cases as bc  # noqa: E402
 import sweep_cases as sc  # noqa: E402
 import wave_cases as wc  # noqa: E402
 import wave_oracle as W  # noqa: E402
-from test_gpu_psf import hand_plane, hand_refs  # noqa: E402
-from test_wavemap_host import bits, same_map, two_pass, wavemap_of_plane  # noqa: E402
+from parity import bits  # noqa: E402
+from restatements import same_map, two_pass, wavemap_of_plane  # noqa: E402
+from wave_refs import hand_plane, hand_refs  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"

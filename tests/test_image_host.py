@@ -1,46 +1,19 @@
 """Spot images on the host: the argument checks of rtpb_spot_image / rtpb_image_sweep (no GPU is touched), the window
-helpers of the Python front end, and ``image_of_plane``, the NumPy restatement of the contribution rule that
-tests/test_gpu_image.py holds the kernels to.
+helpers of the Python front end, and ``image_of_plane`` (tests/restatements.py), the NumPy restatement of the
+contribution rule that tests/test_gpu_image.py holds the kernels to, on values worked out by hand.
 
 The rule (include/rtpb.h): a ray counts when x and y are finite; tx = (x - x_lo) * x_scale, ty likewise, one rounded
 subtract and one rounded multiply each; inside iff 0 <= tx < nx and 0 <= ty < ny in floating point; only then
 ix = int(tx), iy = int(ty) and image[g, iy, ix] += 1; a counting ray that is not inside adds 1 to outside[g]."""
-import ctypes
 
 import numpy as np
 import pytest
 
 from ray_trace_pb_amd import _capi as C
 from ray_trace_pb_amd import analysis
-
-
-def image_of_plane(plane, group_size, windows, nx, ny):
-    """(image (G, ny, nx) int32, outside (G,) int32) of an (N, 8) plane (float64 values: a float32 plane widened),
-    N = G * group_size, with windows (G, 4) float64."""
-    plane = np.asarray(plane, dtype=np.float64)
-    w = np.asarray(windows, dtype=np.float64).reshape(-1, 4)
-    G = plane.shape[0] // group_size
-    assert plane.shape[0] == G * group_size and w.shape[0] == G
-    x, y = plane[:, 0].reshape(G, group_size), plane[:, 1].reshape(G, group_size)
-    image = np.zeros((G, ny, nx), dtype=np.int32)
-    outside = np.zeros(G, dtype=np.int32)
-    with np.errstate(all="ignore"):
-        counts = np.isfinite(x) & np.isfinite(y)
-        tx = (x - w[:, 0:1]) * w[:, 2:3]
-        ty = (y - w[:, 1:2]) * w[:, 3:4]
-        inside = counts & (tx >= 0) & (tx < nx) & (ty >= 0) & (ty < ny)
-    for g in range(G):
-        ix = tx[g, inside[g]].astype(np.int64)           # (truncation, as the C cast; the values are in [0, nx))
-        iy = ty[g, inside[g]].astype(np.int64)
-        np.add.at(image[g], (iy, ix), 1)
-        outside[g] = np.count_nonzero(counts[g] & ~inside[g])
-    return image, outside
-
-
-def plane_of(x, y):
-    p = np.zeros((len(x), 8))
-    p[:, 0], p[:, 1], p[:, 5] = x, y, 1.0
-    return p
+from flat_plans import flat_plan
+from parity import plane_of
+from restatements import image_of_plane
 
 
 def test_restatement_on_hand_made_values():
@@ -180,22 +153,6 @@ def test_automatic_windows_fall_back_to_one(monkeypatch):
     assert seen["auto"] == (summ, (8, 4), 2.0)
 
 
-def _flat_plan():
-    surf = (C.Surface * 1)()
-    surf[0].kind = C.RTPB_FLAT
-    surf[0].normal[:] = [0, 0, 1]
-    surf[0].input_axis[:] = [0, 0, 1]
-    surf[0].aperture = 1.0
-    surf[0].on_tol = 1e-12
-    mats = (C.Material * 2)()
-    for m in mats:
-        m.kind = C.RTPB_CONSTANT
-        m.c[0] = 1.0
-    plan = ctypes.c_void_p()
-    assert C.lib().rtpb_plan_create(surf, 1, mats, 2, C.RTPB_F64, ctypes.byref(plan)) == 0
-    return plan
-
-
 def test_image_entry_points_validate_without_a_gpu():
     """rtpb_spot_image / rtpb_image_sweep: NULL pointers, non-positive sizes and a bad dtype are RTPB_E_INVALID with
     a message that names the call, sides past RTPB_MAX_IMAGE_SIDE and groups past 2^31 - 1 rays RTPB_E_LIMIT, all
@@ -215,7 +172,7 @@ def test_image_entry_points_validate_without_a_gpu():
         assert lib.rtpb_spot_image(*dict(ok, **bad).values()) == C.RTPB_E_LIMIT, bad
         assert b"spot-image" in lib.rtpb_last_error(), bad
 
-    plan = _flat_plan()
+    plan = flat_plan()
     try:
         ok = dict(plan=plan, device=0, n_groups=2, group_params=p, n_thetas=30, nphis=10, center_ray=p, ex=p, ey=p,
                   theta_cos_sin=p, phi_cos_sin=p, windows=p, nx=16, ny=12, image_out=p, outside_out=p, stream=None)

@@ -6,7 +6,7 @@ the argument checks of the C entry point and of the Python calls (no GPU is touc
 operation for operation), then a = n * weight, qx = ex * kf, qy = ey * kf, X = (ix - cx) * sx, Y = (iy - cy) * sy,
 t = (w + qx * X) + qy * Y and fr = t - rint(t), each one rounded operation as the device does them with contraction
 off -- so t and fr are the device's bits -- then np.cos(2 pi fr) and np.sin(2 pi fr) and np.sum over the rays.
-tests/test_gpu_psf.py compares the kernel with it.
+It lives in tests/restatements.py, with ``bound``; tests/test_gpu_psf.py compares the kernel with it.
 
 Tolerance of that comparison (``bound``; derived, not measured).  Device and restatement differ only in (1) the sine
 and cosine: the device's sincospi is within 2 ulp, NumPy rounds 2 pi fr once (a relative 2^-53 of an argument of at
@@ -22,48 +22,7 @@ import pytest
 from ray_trace_pb_amd import _capi as C
 from ray_trace_pb_amd import analysis
 import ray_trace_pb_amd.raytrace as rt
-import wave_oracle as W
-
-CHUNK_ELEMS = 1 << 22                   # the (rays x pixels) temporaries of the restatement stay under 32 MiB
-
-
-def psf_of_plane(plane, group_size, refs, windows, weights, nx, ny):
-    """The rule of rtpb_huygens_psf in NumPy: (field (G, ny, nx) complex128, norm (G,), norm_abs (G,), count (G,)) of
-    an (N, 8) float64 plane against refs (G, 8) and windows (G, 4); weights (group_size,) or None.  norm_abs is the
-    sum of |a| over the counting rays (what the tolerance scales with), count their number."""
-    terms = W.wave_terms(plane, group_size, refs)                     # (G, per, 15): n, w, ., ex, ey
-    refs = np.asarray(refs, dtype=np.float64).reshape(-1, 8)
-    windows = np.asarray(windows, dtype=np.float64).reshape(-1, 4)
-    G = terms.shape[0]
-    wt = np.ones(group_size) if weights is None else np.asarray(weights, dtype=np.float64)
-    field = np.zeros((G, ny, nx), dtype=np.complex128)
-    norm, norm_abs, count = np.zeros(G), np.zeros(G), np.zeros(G, dtype=np.int64)
-    ix, iy = np.arange(nx, dtype=np.float64), np.arange(ny, dtype=np.float64)
-    for g in range(G):
-        counts = terms[g, :, 0] == 1.0
-        kf = refs[g, 7]
-        with np.errstate(invalid="ignore", over="ignore"):
-            a = (terms[g, :, 0] * wt)[counts]                          # (a ray that does not count is skipped)
-            w = terms[g, counts, 1]
-            qx, qy = terms[g, counts, 3] * kf, terms[g, counts, 4] * kf
-            X = (ix - windows[g, 0]) * windows[g, 2]
-            Y = (iy - windows[g, 1]) * windows[g, 3]
-            re, im = np.zeros((ny, nx)), np.zeros((ny, nx))
-            rows = max(1, CHUNK_ELEMS // (nx * ny))
-            for k in range(0, a.size, rows):
-                s = slice(k, k + rows)
-                t = (w[s, None, None] + qx[s, None, None] * X[None, None, :]) + qy[s, None, None] * Y[None, :, None]
-                fr = t - np.rint(t)
-                re += (a[s, None, None] * np.cos(2 * np.pi * fr)).sum(axis=0)
-                im += (a[s, None, None] * np.sin(2 * np.pi * fr)).sum(axis=0)
-        field[g] = re + 1j * im
-        norm[g], norm_abs[g], count[g] = a.sum(), np.abs(a).sum(), a.size
-    return field, norm, norm_abs, count
-
-
-def bound(norm_abs, group_size):
-    """The derived bound on |device - restatement| of re and of im (the module docstring)."""
-    return norm_abs * (8e-15 + 4 * group_size * 2.0 ** -53)
+from restatements import psf_of_plane
 
 
 def focused_plane(dirs, at=(0.0, 0.0, 0.0), phase=0.0, wl=0.5):

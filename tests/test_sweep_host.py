@@ -3,30 +3,19 @@ instantiated by the CPU harness, and the order of rtpb_spot_sweep's checks.  No 
 
 The planner runs with the shipped constants: two rays per lane, at most eight groups per bundle row."""
 import ctypes
+import functools
 
 import numpy as np
 import pytest
 
 import ray_trace_pb_amd.materials as mat
 from ray_trace_pb_amd import _capi as C
+from flat_plans import flat_plan
 from native_harness import harness
+import sweep_rows
+from sweep_rows import MAX_BUNDLE, RPL
 
-RPL, MAX_BUNDLE = 2, 8
-
-
-def plan_rows(params, bundles_allowed=True):
-    """(bundles, rows, singles) of plan_sweep_rows for (G, 4) group parameters (x, y, z, wavelength)."""
-    params = np.ascontiguousarray(params, dtype=np.float64)
-    G = params.shape[0]
-    bundles, rows, singles = (np.full(G, -1, dtype=np.int32) for _ in range(3))
-    counts = np.zeros(3, dtype=np.int64)
-    fn = harness().harness_sweep_rows
-    fn.argtypes = [ctypes.c_void_p, ctypes.c_int64, ctypes.c_int, ctypes.c_int, ctypes.c_int] + [ctypes.c_void_p] * 4
-    fn.restype = None
-    fn(params.ctypes.data, G, int(bundles_allowed), RPL, MAX_BUNDLE, bundles.ctypes.data, rows.ctypes.data,
-       singles.ctypes.data, counts.ctypes.data)
-    assert (counts <= G).all()
-    return bundles[:counts[0]], rows[:counts[1]], singles[:counts[2]]
+plan_rows = functools.partial(sweep_rows.plan_rows, trailing=0)       # the fan sweeps' call: point keys alone
 
 
 def at_points(points, order):
@@ -154,22 +143,6 @@ def test_group_media_table(dtype, second):
     assert (0.0 in flags) == (second.n(0.5) == 1e-40) and 1.0 in flags
 
 
-def _flat_plan():
-    surf = (C.Surface * 1)()
-    surf[0].kind = C.RTPB_FLAT
-    surf[0].normal[:] = [0, 0, 1]
-    surf[0].input_axis[:] = [0, 0, 1]
-    surf[0].aperture = 1.0
-    surf[0].on_tol = 1e-12
-    mats = (C.Material * 2)()
-    for m in mats:
-        m.kind = C.RTPB_CONSTANT
-        m.c[0] = 1.0
-    plan = ctypes.c_void_p()
-    assert C.lib().rtpb_plan_create(surf, 1, mats, 2, C.RTPB_F64, ctypes.byref(plan)) == 0
-    return plan
-
-
 def _spot_sweep_args(plan):
     buf = np.zeros(4096)
     p = buf.ctypes.data
@@ -193,7 +166,7 @@ def test_spot_sweep_checks_the_device_before_its_arguments():
     """Unlike rtpb_focus_sweep, rtpb_spot_sweep looks for the device before it looks at its arguments: without a
     GPU every bad call (and a good one) is RTPB_E_NODEV."""
     lib = C.lib()
-    plan = _flat_plan()
+    plan = flat_plan()
     try:
         buf, ok = _spot_sweep_args(plan)
         for bad in (dict(), dict(group_params=None), dict(n_groups=0), dict(nphis=-3), dict(workspace_len=3),

@@ -1,11 +1,8 @@
 """The variant sweeps on the host: the bundle-row key with the groups' variants and the upload layout
-(csrc/rtpb_sweep_host.h through tests/native/variant_rows.cpp), the argument checks of rtpb_focus_sweep_variants /
+(csrc/rtpb_sweep_host.h through tests/sweep_rows.py), the argument checks of rtpb_focus_sweep_variants /
 _variants_collimated (no GPU is touched) and their ctypes signatures, analysis.rigid_move, and what the Python wrappers
 refuse before any device call."""
 import ctypes
-import fcntl
-import os
-import subprocess
 
 import numpy as np
 import pytest
@@ -15,52 +12,16 @@ from ray_trace_pb_amd import _engine as E
 from ray_trace_pb_amd import analysis
 import ray_trace_pb_amd.materials as mat
 import ray_trace_pb_amd.raytrace as rt
+from flat_plans import _systems
+import sweep_rows
+from sweep_rows import MAX_BUNDLE, RPL, native
 import systems
-from test_beam_host import plan_rows as beam_plan_rows
-
-HERE = os.path.dirname(os.path.abspath(__file__))
-SRC = os.path.join(HERE, "native", "variant_rows.cpp")
-OUT = os.path.join(HERE, "native", "_build", "libvariant_rows.so")
-RPL, MAX_BUNDLE = 2, 8                  # the shipped constants: two rays per lane, eight groups per bundle row
 
 
-def native():
-    csrc = os.path.join(HERE, "..", "ray_trace_pb_amd", "csrc")
-    deps = [SRC, os.path.join(csrc, "rtpb_sweep_host.h"), os.path.join(csrc, "rtpb_math.h")]
-    os.makedirs(os.path.dirname(OUT), exist_ok=True)
-    with open(OUT + ".lock", "w") as lk:                # several test processes may race to (re)build
-        fcntl.flock(lk, fcntl.LOCK_EX)
-        if not os.path.exists(OUT) or any(os.path.getmtime(OUT) < os.path.getmtime(d) for d in deps):
-            tmp = f"{OUT}.{os.getpid()}.tmp"
-            subprocess.run(["g++", "-O2", "-std=c++17", "-ffp-contract=off", "-fPIC", "-shared",
-                            "-I", os.path.join(HERE, "..", "include"), "-o", tmp, SRC], check=True)
-            os.replace(tmp, OUT)
-    lib = ctypes.CDLL(OUT)
-    lib.variant_sweep_rows.argtypes = [ctypes.c_void_p] * 3 + [ctypes.c_int, ctypes.c_int64] + [ctypes.c_int] * 3 + \
-        [ctypes.c_void_p] * 4
-    lib.variant_sweep_rows.restype = None
-    lib.variant_surface_code.argtypes = [ctypes.POINTER(C.Surface)]
-    lib.variant_surface_code.restype = ctypes.c_int
-    lib.variant_sweep_layout.argtypes = [ctypes.c_int64] * 7 + [ctypes.c_void_p]
-    lib.variant_sweep_layout.restype = None
-    return lib
-
-
-def plan_rows(params, frames=None, variants=None, with_arg=True):
-    """(bundles, rows, singles) of plan_sweep_rows; ``with_arg=False`` leaves its variant argument out."""
-    params = np.ascontiguousarray(params, dtype=np.float64)
-    G = params.shape[0]
-    if frames is not None:
-        frames = np.ascontiguousarray(frames, dtype=np.float64)
-    if variants is not None:
-        variants = np.ascontiguousarray(variants, dtype=np.int32)
-    bundles, rows, singles = (np.full(G, -1, dtype=np.int32) for _ in range(3))
-    counts = np.zeros(3, dtype=np.int64)
-    native().variant_sweep_rows(params.ctypes.data, None if frames is None else frames.ctypes.data,
-                                None if variants is None else variants.ctypes.data, int(with_arg), G, 1, RPL,
-                                MAX_BUNDLE, bundles.ctypes.data, rows.ctypes.data, singles.ctypes.data,
-                                counts.ctypes.data)
-    return bundles[:counts[0]].tolist(), rows[:counts[1]].tolist(), singles[:counts[2]].tolist()
+def row_lists(params, frames=None, variants=None, trailing=2):
+    """(bundles, rows, singles) of plan_sweep_rows as lists; ``trailing=1`` leaves its variant argument out,
+    ``trailing=0`` its frames too."""
+    return tuple(a.tolist() for a in sweep_rows.plan_rows(params, frames, variants, trailing=trailing))
 
 
 def _mixed():
@@ -76,22 +37,23 @@ def _mixed():
 
 
 def test_rows_without_the_variant_argument_are_todays():
-    """The call every other sweep makes -- no variant argument -- gives on a mixed input exactly the rows of the
-    beam harness (built from the same header through the old signature), with and without frames; a NULL variant
-    argument and one with all variants equal give them too."""
+    """The call every other sweep makes -- no variant argument -- gives on a mixed input exactly the recorded rows,
+    with and without frames (without them also with the frames left to their default, the fan sweeps' call); a NULL
+    variant argument and one with all variants equal give them too."""
     params, frames = _mixed()
     # the rows the commit before the variant key gave on this input, recorded from its build (keys in the order of
     # their bit patterns: the point (0, 0, -1) first, then (0.5, 0, -1), then (-2, 1, -1))
     recorded = ([4, 5, 6, 7, 8, 9, 10, 11, 1, 2, 0, 13], [0, 8, 8, 2, 10, 2], [3, 12, 14])
     for fr in (None, frames):
-        old = beam_plan_rows(params, fr)
+        old = row_lists(params, fr, trailing=1)
         assert old == recorded
-        assert plan_rows(params, fr, with_arg=False) == old
-        assert plan_rows(params, fr, None) == old
-        assert plan_rows(params, fr, np.zeros(len(params))) == old
-        assert plan_rows(params, fr, np.full(len(params), 6)) == old
+        if fr is None:
+            assert row_lists(params, trailing=0) == old
+        assert row_lists(params, fr, None) == old
+        assert row_lists(params, fr, np.zeros(len(params))) == old
+        assert row_lists(params, fr, np.full(len(params), 6)) == old
     # the point's rows, spelled out: nine wavelengths are a row of eight and a single, three a row of two and a single
-    bundles, rows, singles = plan_rows(params, None, with_arg=False)
+    bundles, rows, singles = row_lists(params, None, trailing=1)
     assert sorted(rows[1::2]) == [2, 2, 8] and sorted(bundles + singles) == list(range(len(params)))
 
 
@@ -101,7 +63,7 @@ def test_no_bundle_row_mixes_variants_and_every_group_appears_once():
     rng = np.random.default_rng(11)
     for fr in (None, frames):
         for variants in (np.arange(G) % 2, np.arange(G) % 3, rng.integers(0, 4, G), np.arange(G)):
-            bundles, rows, singles = plan_rows(params, fr, variants)
+            bundles, rows, singles = row_lists(params, fr, variants)
             assert sorted(bundles + singles) == list(range(G))
             assert singles == sorted(singles) and len(rows) % 2 == 0
             offs, lens = rows[0::2], rows[1::2]
@@ -115,15 +77,15 @@ def test_no_bundle_row_mixes_variants_and_every_group_appears_once():
                 if fr is not None:
                     assert len({fr[g].tobytes() for g in gs}) == 1
     # one variant per group: nothing can share a row
-    assert plan_rows(params, None, np.arange(G))[1] == []
+    assert row_lists(params, None, np.arange(G))[1] == []
     # the sweep's own order, group = (variant * fields + field) * wavelengths + wavelength: a row per (variant, field)
     V, nf, nw = 3, 2, 3
     p = np.zeros((V * nf * nw, 4))
     p[:, 0] = np.tile(np.repeat([0.0, 1.0], nw), V)
     p[:, 3] = np.tile([0.5, 0.6, 0.7], V * nf)
-    bundles, rows, singles = plan_rows(p, None, np.repeat(np.arange(V), nf * nw))
+    bundles, rows, singles = row_lists(p, None, np.repeat(np.arange(V), nf * nw))
     assert rows[1::2] == [2] * (V * nf) and len(singles) == V * nf
-    assert plan_rows(p, None, with_arg=False)[1][1::2] == [8, 8]          # (the point alone would merge the variants)
+    assert row_lists(p, None, trailing=1)[1][1::2] == [8, 8]          # (the point alone would merge the variants)
 
 
 def test_upload_layout_keeps_its_offsets_and_places_the_descriptors():
@@ -144,22 +106,6 @@ def test_upload_layout_keeps_its_offsets_and_places_the_descriptors():
         assert {k: var[k] for k in ("grp", "gn", "img", "win", "frm", "dsc")} == \
             {k: plain[k] for k in ("grp", "gn", "img", "win", "frm", "dsc")}
         assert var["dsc"] % 8 == 0 and var["idx"] == var["dsc"] + desc and var["bytes"] == var["idx"] + 4 * (n_idx + G)
-
-
-def _systems(n_variants, dtype=C.RTPB_F64):
-    """n_variants copies of a flat between Constant media, as the variant calls take them."""
-    surf = (C.Surface * n_variants)()
-    mats = (C.Material * (2 * n_variants))()
-    for s in surf:
-        s.kind = C.RTPB_FLAT
-        s.normal[:] = [0, 0, 1]
-        s.input_axis[:] = [0, 0, 1]
-        s.aperture = 1.0
-        s.on_tol = 1e-12
-    for m in mats:
-        m.kind = C.RTPB_CONSTANT
-        m.c[0] = 1.0
-    return surf, mats
 
 
 def test_entry_points_validate_without_a_gpu():

@@ -14,7 +14,7 @@ import ray_trace_pb_amd.raytrace as rt
 import systems
 import variant_cases as vc
 import variant_wave_cases as vw
-from test_variant_host import _systems
+from flat_plans import _systems
 
 WAVE = ("rtpb_wavefront_sweep_variants", "rtpb_wavefront_sweep_variants_collimated")
 RAYS = ("rtpb_final_rays_variants", "rtpb_final_rays_variants_collimated")

@@ -12,7 +12,7 @@ import pytest
 import sweep_cases as sc
 import wave_cases as wc
 import wave_oracle as W
-from test_wavefront_host import case_refs
+from wave_refs import case_refs
 
 LIVE_GOLDEN = tuple(n for n in sc.GOLDEN_SYSTEMS if n not in sc.GOLDEN_MAY_BE_DEAD)
 

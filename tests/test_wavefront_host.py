@@ -7,7 +7,6 @@ n rounded products of size at most max|w|^2; accumulated in any order the roundi
 eps * max|w|^2 * sqrt(n), and the division and the subtraction add a few eps * max|w|^2 more.  With a factor 16 of
 slack  |Var - exact| <= 16 * eps * max|w|^2 * sqrt(n).  The best-reference variance adds 2 kf delta . cov_we +
 kf^2 delta' cov_ee delta, moments of kf delta . e, which cancels w and is of its size: the same bound holds it."""
-import ctypes
 
 import numpy as np
 import pytest
@@ -16,41 +15,20 @@ from ray_trace_pb_amd import _capi as C
 from ray_trace_pb_amd import analysis
 from oracle import rt_numpy as O
 import ray_trace_pb_amd.raytrace as rt
+from flat_plans import flat_plan
 import sweep_cases as SC
+from wave_refs import ALIVE, case_refs
 import wave_oracle as W
 
 EPS = 2.0 ** -52
-# every group has a finite chief ray and counts rays; ... of these, the ones with dead rows beside them
-ALIVE = ("c2", "xz", "c5_wide", "c5_tail2_before", "tangent", "c4")
+# of wave_refs.ALIVE (every group has a finite chief ray and counts rays), the cases with dead rows beside them
 WITH_DEAD_ROWS = ("xz", "c5_wide", "c4", "tangent")
-
-
-def case_refs(name):
-    """The oracle's references of a named sweep case at its own fan shape (what the GPU tests pass)."""
-    c = SC.case(name)
-    return W.oracle_refs(c.S, c.M, c.m1, c.fields, c.wls, SC.oracle_finals(name), c.center_ray)
 
 
 def case_counts(name, refs):
     c = SC.case(name)
     terms = W.wave_terms(SC.oracle_finals(name), c.nt * c.nph, refs)
     return terms[..., 0].sum(axis=1).reshape(len(c.fields), len(c.wls))
-
-
-def _flat_plan(dtype):
-    surf = (C.Surface * 1)()
-    surf[0].kind = C.RTPB_FLAT
-    surf[0].normal[:] = [0, 0, 1]
-    surf[0].input_axis[:] = [0, 0, 1]
-    surf[0].aperture = 1.0
-    surf[0].on_tol = 1e-12
-    mats = (C.Material * 2)()
-    for m in mats:
-        m.kind = C.RTPB_CONSTANT
-        m.c[0] = 1.0
-    plan = ctypes.c_void_p()
-    assert C.lib().rtpb_plan_create(surf, 1, mats, 2, dtype, ctypes.byref(plan)) == 0
-    return plan
 
 
 def test_wavefront_entry_points_validate_without_a_gpu():
@@ -73,7 +51,7 @@ def test_wavefront_entry_points_validate_without_a_gpu():
     assert b"workspace too small" in lib.rtpb_last_error() and b"* 15 doubles" in lib.rtpb_last_error()
     assert lib.rtpb_wavefront_stats(*dict(ok, n_groups=65536, workspace_len=1 << 40).values()) == C.RTPB_E_LIMIT
 
-    plan, plan32 = _flat_plan(C.RTPB_F64), _flat_plan(C.RTPB_F32)
+    plan, plan32 = flat_plan(C.RTPB_F64), flat_plan(C.RTPB_F32)
     try:
         ok = dict(plan=plan, device=0, n_groups=G, group_params=p, n_thetas=30, nphis=10, center_ray=p, ex=p, ey=p,
                   theta_cos_sin=p, phi_cos_sin=p, refs=p, workspace=p, workspace_len=G * tiles * 15, stats_out=p,

@@ -1,5 +1,5 @@
-"""Wavefront maps on the host: ``wavemap_of_plane``, the NumPy restatement of the map's rule that
-tests/test_gpu_wavemap.py holds the kernels to, built on wave_oracle.wave_terms so that w, ex and ey are the pinned
+"""Wavefront maps on the host: ``wavemap_of_plane`` (tests/restatements.py), the NumPy restatement of the map's rule
+that tests/test_gpu_wavemap.py holds the kernels to, built on wave_oracle.wave_terms so that w, ex and ey are the pinned
 bits; the rule itself through a g++ harness of csrc/rtpb_wavemap.h (tests/wavemap_harness.py); the map's two bounds
 on the oracle's final planes of the sweep cases; the Zernike basis and fit; and the argument checks of
 rtpb_wavefront_map / rtpb_wavefront_map_sweep / rtpb_wavefront_map_sweep_collimated (no GPU is touched).
@@ -7,7 +7,6 @@ rtpb_wavefront_map / rtpb_wavefront_map_sweep / rtpb_wavefront_map_sweep_collima
 The rule (include/rtpb.h): f = wave_ray(...), a ray with f.n == 0 contributes nothing; every counting ray enters
 far_e = max(|ex|, |ey|) and far_w = |w|; b = image_bin(ex, ey, window): not inside -> outside[g] += 1; inside and not
 |w| <= w_lim -> clipped[g] += 1; otherwise q = (int64) rint(w * 2^q_bits), count[g, b] += 1, sum[g, b] += q."""
-import ctypes
 import functools
 
 import numpy as np
@@ -15,60 +14,15 @@ import pytest
 
 from ray_trace_pb_amd import _capi as C
 from ray_trace_pb_amd import analysis
+from flat_plans import flat_plan
+from parity import bits
+from restatements import same_map, two_pass, wavemap_of_plane
 import sweep_cases as sc
 import wave_cases as wc
 import wave_oracle as W
 import wavemap_harness as H
 
 CASES = ("c2", "c4", "tir", "stress", "xz", "c5_wide", "tangent", "c5_far")
-
-
-def wavemap_of_plane(plane, group_size, refs, windows, bins, q_bits, w_lim):
-    """(count (G, ny, nx) int32, sum (G, ny, nx) int64, outside (G,) int32, clipped (G,) int32, farthest (G, 2)) of an
-    (N, 8) float64 plane, N = G * group_size, against refs (G, 8) and windows (G, 4)."""
-    nx, ny = bins
-    t = W.wave_terms(plane, group_size, refs)
-    G = t.shape[0]
-    win = np.asarray(windows, dtype=np.float64).reshape(G, 1, 4)
-    n, w, ex, ey = t[..., 0] != 0.0, t[..., 1], t[..., 3], t[..., 4]
-    with np.errstate(all="ignore"):
-        tx, ty = (ex - win[..., 0]) * win[..., 2], (ey - win[..., 1]) * win[..., 3]
-        inside = n & (tx >= 0.0) & (tx < nx) & (ty >= 0.0) & (ty < ny)
-        keep = inside & (np.abs(w) <= w_lim)
-        q = np.rint(w * 2.0 ** q_bits)
-    count = np.zeros((G, ny * nx), dtype=np.int32)
-    total = np.zeros((G, ny * nx), dtype=np.int64)
-    farthest = np.zeros((G, 2))
-    for g in range(G):
-        k = keep[g]
-        b = ty[g, k].astype(np.int64) * nx + tx[g, k].astype(np.int64)     # (truncation, as the C cast)
-        np.add.at(count[g], b, 1)
-        np.add.at(total[g], b, q[g, k].astype(np.int64))
-        if n[g].any():
-            farthest[g] = (np.maximum(np.abs(ex[g, n[g]]), np.abs(ey[g, n[g]])).max(), np.abs(w[g, n[g]]).max())
-    outside = (n & ~inside).sum(axis=1).astype(np.int32)
-    clipped = (inside & ~keep).sum(axis=1).astype(np.int32)
-    return count.reshape(G, ny, nx), total.reshape(G, ny, nx), outside, clipped, farthest
-
-
-def bits(a):
-    return np.ascontiguousarray(a, dtype=np.float64).view(np.int64)
-
-
-def same_map(got, exp):
-    """count, sum, outside and clipped == as integers of the right types, farthest the same bits."""
-    return (got[0].dtype == np.int32 and got[1].dtype == np.int64 and all(np.array_equal(a, b) for a, b in
-                                                                           zip(got[:4], exp[:4])) and
-            got[4].shape == exp[4].shape and np.array_equal(bits(got[4]), bits(exp[4])))
-
-
-def two_pass(plane, group_size, refs, bins):
-    """The sweeps' default window, limit and q_bits, from the restatement's own first pass: (windows, w_lim, q_bits)."""
-    G = plane.shape[0] // group_size
-    unit = np.tile([-1.0, -1.0, 0.5, 0.5], (G, 1))
-    far = wavemap_of_plane(plane, group_size, refs, unit, (1, 1), 0, 0.0)[4]
-    w_lim = max(1.0, float(far[:, 1].max()))
-    return analysis.wavefront_map_windows(far[:, 0], bins), w_lim, analysis.wavefront_map_q_bits(group_size, w_lim)
 
 
 # ------------------------------------------------------------------------------------------ the bounds, on the oracle
@@ -351,22 +305,6 @@ def test_c2_map_and_fifteen_term_fit_on_the_oracle():
 
 
 # ------------------------------------------------------------------------------------------ the C ABI's checks
-def _flat_plan(dtype=C.RTPB_F64):
-    surf = (C.Surface * 1)()
-    surf[0].kind = C.RTPB_FLAT
-    surf[0].normal[:] = [0, 0, 1]
-    surf[0].input_axis[:] = [0, 0, 1]
-    surf[0].aperture = 1.0
-    surf[0].on_tol = 1e-12
-    mats = (C.Material * 2)()
-    for m in mats:
-        m.kind = C.RTPB_CONSTANT
-        m.c[0] = 1.0
-    plan = ctypes.c_void_p()
-    assert C.lib().rtpb_plan_create(surf, 1, mats, 2, dtype, ctypes.byref(plan)) == 0
-    return plan
-
-
 # what every one of the three calls refuses, beside its own source's arguments: (bad arguments, code)
 def _common_refusals(size_key):
     inv, lim = C.RTPB_E_INVALID, C.RTPB_E_LIMIT
@@ -406,7 +344,7 @@ def test_map_entry_points_validate_without_a_gpu():
     assert H.harness().wavemap_harness_bound(53, 1.0, 10) == 1 and H.harness().wavemap_harness_bound(0, np.nan, 10) == 1
     assert lib.rtpb_wavefront_map(*edge.values()) == C.RTPB_E_NODEV
 
-    plan, plan32 = _flat_plan(), _flat_plan(C.RTPB_F32)
+    plan, plan32 = flat_plan(), flat_plan(C.RTPB_F32)
     try:
         fan = dict(plan=plan, device=0, n_groups=2, group_params=p, n_thetas=30, nphis=10, center_ray=p, ex=p, ey=p,
                    theta_cos_sin=p, phi_cos_sin=p, **tail)

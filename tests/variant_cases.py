@@ -23,7 +23,7 @@ from ray_trace_pb_amd import analysis
 from oracle import rt_numpy as O
 from serialize import material_to_dict, surface_to_dict
 import systems
-from test_gpu_focus import fixed_order_focus_sums
+from restatements import fixed_order_focus_sums
 
 NA, NB = 67, 23
 DEG = np.pi / 180

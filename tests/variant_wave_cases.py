@@ -19,7 +19,7 @@ from oracle import rt_numpy as O
 from serialize import material_to_dict, surface_to_dict
 import variant_cases as vc
 import wave_oracle as W
-from test_gpu_focus import fixed_order_focus_sums
+from restatements import fixed_order_focus_sums
 
 NAMES = vc.NAMES
 

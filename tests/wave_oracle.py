@@ -2,7 +2,7 @@
 
 ``wave_terms`` is the one definition of a ray's contribution (include/rtpb.h, csrc/rtpb_stats.h wave_ray /
 wave_term), operation for operation; ``fixed_order_wave_sums`` adds the kernels' two-stage reduction (a pairwise
-tree per 256-ray tile, then the tiles in the final kernel's order), as tests/test_gpu_focus.py does for the focus
+tree per 256-ray tile, then the tiles in the final kernel's order), as tests/restatements.py does for the focus
 sums.  ``oracle_refs`` gives the references (C0, d0, p0, kf) of a sweep's groups from oracle-traced fans and chief
 rays; tests/test_wavefront_host.py checks on the CPU what tests/test_gpu_wavefront.py assumes about them.
 ``survivor_refs_of`` gives references from the surviving rays alone, for groups whose chief ray dies

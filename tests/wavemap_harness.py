@@ -1,41 +1,21 @@
-"""Build + load the CPU harness of the wavefront map's per-ray rule (tests/native/wavemap_harness.cpp), as
-foot_harness.py builds foot_harness.cpp.  TEST INFRASTRUCTURE ONLY."""
+"""Load the CPU harness of the wavefront map's per-ray rule (tests/native/wavemap_harness.cpp; built by
+native_harness.load).  TEST INFRASTRUCTURE ONLY."""
 import ctypes
-import os
-import subprocess
 
 import numpy as np
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-SRC = os.path.join(HERE, "native", "wavemap_harness.cpp")
-OUT = os.path.join(HERE, "native", "_build", "libwavemap_harness.so")
-DEPS = [SRC, os.path.join(HERE, "..", "ray_trace_pb_amd", "csrc", "rtpb_wavemap.h"),
-        os.path.join(HERE, "..", "ray_trace_pb_amd", "csrc", "rtpb_math.h"),
-        os.path.join(HERE, "..", "include", "rtpb.h")]
-
-_lib = None
+import native_harness
 
 
 def harness():
-    global _lib
-    if _lib is None:
-        os.makedirs(os.path.dirname(OUT), exist_ok=True)
-        import fcntl
-        with open(OUT + ".lock", "w") as lk:        # several test processes may race to (re)build
-            fcntl.flock(lk, fcntl.LOCK_EX)
-            if not os.path.exists(OUT) or any(os.path.getmtime(OUT) < os.path.getmtime(d) for d in DEPS):
-                tmp = f"{OUT}.{os.getpid()}.tmp"
-                subprocess.run(["g++", "-O2", "-std=c++17", "-ffp-contract=off", "-fPIC", "-shared",
-                                "-I", os.path.join(HERE, "..", "include"), "-o", tmp, SRC], check=True)
-                os.replace(tmp, OUT)
-        _lib = ctypes.CDLL(OUT)
-        P = ctypes.c_void_p
-        _lib.wavemap_harness_map.argtypes = [P, ctypes.c_int64, ctypes.c_int64, P, P, ctypes.c_int32, ctypes.c_int32,
-                                             ctypes.c_int32, ctypes.c_double, P, P, P, P, P]
-        _lib.wavemap_harness_map.restype = ctypes.c_int
-        _lib.wavemap_harness_bound.argtypes = [ctypes.c_int32, ctypes.c_double, ctypes.c_int64]
-        _lib.wavemap_harness_bound.restype = ctypes.c_int
-    return _lib
+    lib = native_harness.load("wavemap_harness")
+    P = ctypes.c_void_p
+    lib.wavemap_harness_map.argtypes = [P, ctypes.c_int64, ctypes.c_int64, P, P, ctypes.c_int32, ctypes.c_int32,
+                                        ctypes.c_int32, ctypes.c_double, P, P, P, P, P]
+    lib.wavemap_harness_map.restype = ctypes.c_int
+    lib.wavemap_harness_bound.argtypes = [ctypes.c_int32, ctypes.c_double, ctypes.c_int64]
+    lib.wavemap_harness_bound.restype = ctypes.c_int
+    return lib
 
 
 def wavemap(plane, group_size, refs, windows, bins, q_bits, w_lim):
