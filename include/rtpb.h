@@ -66,7 +66,10 @@ extern "C" {
                                     rtpb_energy_sweep_collimated (encircled and ensquared energy), then
                                     rtpb_huygens_psf (the diffraction PSF of a plane), then rtpb_wavefront_map /
                                     rtpb_wavefront_map_sweep / rtpb_wavefront_map_sweep_collimated (pupil OPD
-                                    maps) joined within 10: new symbols only, nothing existing changed */
+                                    maps), then rtpb_transmission_stats / rtpb_transmission_sweep /
+                                    rtpb_transmission_sweep_collimated / rtpb_ray_transmission / rtpb_plan_media
+                                    (Fresnel losses per surface and throughput) joined within 10: new symbols
+                                    only, nothing existing changed */
 
 /* ---- error codes ---------------------------------------------------------------------------- */
 #define RTPB_OK 0
@@ -691,6 +694,74 @@ int rtpb_footprint_sweep_collimated(const rtpb_plan* plan, int32_t device, int64
                                     int64_t nphis, const double* offsets, const double* phi_cos_sin,
                                     const double* frames, int32_t n_frames, double* workspace, int64_t workspace_len,
                                     double* stats_out, void* stream);
+
+/* TRANSMISSION statistics: per (group, surface), how much LIGHT gets through -- Fresnel's equations for uncoated
+   refracting surfaces at each ray's own angle of incidence, or a constant per surface: the loss per surface, the
+   throughput per group and the apodisation across the pupil.  Defined on the stored history, like the footprints: for
+   surface s and one ray, A is the ray's row in plane 2s + 1 (the position at the surface and the INCOMING direction),
+   B its row in plane 2s + 2 (the OUTGOING direction), n1 and n2 the indices before and after the surface at the
+   group's wavelength.  float64 ONLY (a float32 dtype or plan is RTPB_E_INVALID).  Every operation one rounded IEEE
+   operation in this order, no FMA:
+       the ray PASSES surface s exactly when the footprint statistics say so: A.xyz finite and B.xyz finite
+       a surface's COATING is two doubles {mode, value}:
+         mode 0, CONSTANT: t = value, 0 <= value <= 1 (an ideal lens, a mirror's reflectance, an AR coating as a number)
+         mode 1, FRESNEL (uncoated, unpolarised; value is ignored): t = 1 where n1 == n2; else, dA = A.dxyz, dB = B.dxyz,
+           g  = n1*dA - n2*dB                      (componentwise; by Snell's law g is along the normal)
+           p1 = |(dA.x*g.x + dA.y*g.y) + dA.z*g.z|      p2 = |(dB.x*g.x + dB.y*g.y) + dB.z*g.z|
+           rs = (n1*p1 - n2*p2) / (n1*p1 + n2*p2)       rp = (n2*p1 - n1*p2) / (n2*p1 + n1*p2)
+           t  = 1 - 0.5*(rs*rs + rp*rp);   a t that is NaN or outside [0, 1] becomes 0
+       cum_s = cum_(s-1) * t_s in surface order, cum_(-1) = 1 (a ray that passes s has passed every earlier surface)
+       qt = rint(t * 2^q_bits),   qc = rint(cum * 2^q_bits)
+   The rule uses no normal, no surface kind, no square root and no normalisation (|g| cancels in both ratios), so it
+   holds for every surface that refracts by Snell's law.  What it is NOT: no polarisation state is carried from surface
+   to surface (each surface sees unpolarised light), there is no absorption, and there are no thin-film stacks.
+   stats_out (device, n_groups x nsurf x 5 doubles, all integer-valued or infinite), per (group, surface):
+       0  the number of rays that pass        1  the sum of qt over them        2  the sum of qc over them
+       3  min qc over them (+inf for none)    4  max qc over them (-inf for none)
+   1 <= q_bits <= 40 (RTPB_E_INVALID otherwise); rays per group * 2^q_bits <= 2^53 (RTPB_E_LIMIT beyond): every sum is
+   then an exact integer in a double in any order, so the two-pass reduction, any batching and any split over devices
+   give the same bits.
+   media: HOST, n_groups x (nsurf + 1) indices (rtpb_plan_media).  coatings: HOST, nsurf x 2, every entry finite, mode 0
+   or 1, value in [0, 1] (RTPB_E_INVALID otherwise); both are uploaded on `stream`.  nsurf <= RTPB_MAX_SURFACES,
+   n_groups <= 65535 (RTPB_E_LIMIT beyond).  The arguments are checked before the device is.
+   rtpb_transmission_stats: a stored float64 AOS history as rtpb_footprint_stats takes it.
+   workspace: device doubles, >= n_groups * ceil(group_size / 256) * nsurf * 5. */
+int rtpb_transmission_stats(int32_t device, int32_t dtype, const void* history, int64_t group_size, int64_t n_groups,
+                            int32_t nsurf, const double* media, const double* coatings, int32_t q_bits,
+                            double* workspace, int64_t workspace_len, double* stats_out, void* stream);
+
+/* Each ray's energy weight, for a caller's own apodised sums: out (device, one double per ray of the history) holds cum
+   after the last surface, unquantised, NaN for a ray that does not pass it.  The arguments and checks of
+   rtpb_transmission_stats without q_bits and the workspace. */
+int rtpb_ray_transmission(int32_t device, int32_t dtype, const void* history, int64_t group_size, int64_t n_groups,
+                          int32_t nsurf, const double* media, const double* coatings, double* out, void* stream);
+
+/* The indices a float64 sweep of `plan` traces with: out (HOST, n x (nsurf + 1)) holds n of every material of the plan
+   at wavelengths[i] (HOST, n of them), by the host arithmetic that fills the fused sweeps' media table.  Host only: no
+   device is touched.  A float32 plan is RTPB_E_INVALID.  A plan with an RTPB_POLY6 material is RTPB_E_INVALID as well:
+   that polynomial is evaluated on the device with the device's pow(), which the host does not reproduce bit for bit --
+   lower the material as RTPB_TABLE at the call's wavelengths instead (the variant sweeps' rule).  The fused
+   transmission sweeps refuse the same plans with the same code. */
+int rtpb_plan_media(const rtpb_plan* plan, const double* wavelengths, int64_t n, double* out);
+
+/* Fused transmission sweep: rtpb_footprint_sweep's arguments with coatings (HOST, n_coatings x 2; they ride in the
+   sweep's one upload), n_coatings, which must be the plan's number of surfaces, and q_bits in the frames' place.  The
+   surface steps are the footprint sweep's; the rule reads the indices the kernel traces with, so nothing is uploaded
+   per group.
+   CONTRACT: stats_out (device, n_groups x nsurf x 5) is bit-identical to rtpb_transmission_stats of the stored history
+   of the same rays with the media rtpb_plan_media gives for the groups' wavelengths.
+   workspace: device doubles, >= n_groups * ceil(ceil(rays per group / 256) / 2) * nsurf * 5.  float64 plans without
+   POLY6 media only; the group and tile limits and error codes of rtpb_footprint_sweep. */
+int rtpb_transmission_sweep(const rtpb_plan* plan, int32_t device, int64_t n_groups, const double* group_params,
+                            int64_t n_thetas, int64_t nphis, const double center_ray[3], const double ex[3],
+                            const double ey[3], const double* theta_cos_sin, const double* phi_cos_sin,
+                            const double* coatings, int32_t n_coatings, int32_t q_bits, double* workspace,
+                            int64_t workspace_len, double* stats_out, void* stream);
+int rtpb_transmission_sweep_collimated(const rtpb_plan* plan, int32_t device, int64_t n_groups,
+                                       const double* group_params, const double* group_frames, int64_t n_disps,
+                                       int64_t nphis, const double* offsets, const double* phi_cos_sin,
+                                       const double* coatings, int32_t n_coatings, int32_t q_bits, double* workspace,
+                                       int64_t workspace_len, double* stats_out, void* stream);
 
 /* VARIANT sweeps (tolerance runs): rtpb_focus_sweep / rtpb_focus_sweep_collimated over MANY systems in one call.
    The systems come in the call, as in rtpb_trace_f64: there is no plan and no per-system device memory.

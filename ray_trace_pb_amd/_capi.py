@@ -160,6 +160,14 @@ SIGNATURES = {
                                                 _i32, _dbl, _P, _P, _P, _P, _P, _P]),
     "rtpb_wavefront_map_sweep_collimated": (ctypes.c_int, [_P, _i32, _i64, _P, _P, _i64, _i64, _P, _P, _P, _P, _i32,
                                                            _i32, _i32, _dbl, _P, _P, _P, _P, _P, _P]),
+    # (the footprint calls' shape: media, coatings and q_bits, or coatings, their count and q_bits, in the frames' place)
+    "rtpb_transmission_stats": (ctypes.c_int, [_i32, _i32, _P, _i64, _i64, _i32, _P, _P, _i32, _P, _i64, _P, _P]),
+    "rtpb_ray_transmission": (ctypes.c_int, [_i32, _i32, _P, _i64, _i64, _i32, _P, _P, _P, _P]),
+    "rtpb_plan_media": (ctypes.c_int, [_P, _P, _i64, _P]),
+    "rtpb_transmission_sweep": (ctypes.c_int, [_P, _i32, _i64, _P, _i64, _i64, _P, _P, _P, _P, _P, _P, _i32, _i32, _P,
+                                               _i64, _P, _P]),
+    "rtpb_transmission_sweep_collimated": (ctypes.c_int, [_P, _i32, _i64, _P, _P, _i64, _i64, _P, _P, _P, _i32, _i32,
+                                                          _P, _i64, _P, _P]),
     "rtpb_set_tuning":(ctypes.c_int, [ctypes.c_char_p, _i64]),
     "rtpb_timing_enable": (ctypes.c_int, [_i32]),
     "rtpb_timing_collect": (ctypes.c_int, [ctypes.POINTER(_dbl), ctypes.POINTER(_i64)]),

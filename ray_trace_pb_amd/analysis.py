@@ -235,7 +235,8 @@ def focus_stats(plane, group_size):
 
 # A sweep mode states once what differs between the analyses; the drivers below derive the rest from it:
 #   entry, plane_entry   the fused C entry point (None: the Huygens PSF has none) and the one that reduces a stored
-#                   plane (None: the final rays are their own result)
+#                   plane (None: the final rays are their own result; a function: called in its place, with its
+#                   arguments)
 #   outputs         per output (the shape that follows the group index, the NumPy dtype).  The shard's device tensors
 #                   of the fused sweep, the zeroed host arrays host(G) of the unfused one and the allocation inside a
 #                   plane call all come from this list, one row per group
@@ -323,7 +324,9 @@ def _plane(mode, plane, group_size, b0=0, stream=None):
     outputs = _device_outputs(mode, ngroups, dev)
     if stream is None:
         stream = torch.cuda.current_stream(dev).cuda_stream
-    C.check(getattr(C.lib(), mode.plane_entry)(
+    # (a mode outside this module may give the call itself: the transmission statistics take S before their table)
+    call = mode.plane_entry if callable(mode.plane_entry) else getattr(C.lib(), mode.plane_entry)
+    C.check(call(
         dev.index or 0, C.RTPB_F64 if plane.dtype == torch.float64 else C.RTPB_F32, plane.data_ptr(), group_size,
         ngroups, *(_address(t) for t in tables), *(_address(c) for c in consts),
         *(a for w in ws for a in (w.data_ptr(), w.numel())), *(t.data_ptr() for t in outputs), stream))

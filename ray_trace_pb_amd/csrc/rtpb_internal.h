@@ -20,6 +20,10 @@
 //                          the fused footprint sweep (per-surface beam footprints and vignetting; fans, beams)
 //   rtpb_footprint.hip     the footprint statistics of a stored history and their second pass (rtpb_foot.h: the
 //                          per-ray term, plain C++)
+//   rtpb_sweep_trans.hip, rtpb_sweep_trans_beam.hip
+//                          the fused transmission sweep (Fresnel losses per surface and throughput; fans, beams)
+//   rtpb_transmission.hip  the transmission statistics of a stored history, their second pass, each ray's energy
+//                          weight and a plan's indices (rtpb_trans.h: the per-ray rule, plain C++)
 //   rtpb_surface_ops.hip   propagate_ray2plane and the user-geometry hook kernels
 #pragma once
 
@@ -464,6 +468,16 @@ int launch_stats_final(int n_stats, double* partials, double* stats, int64_t n_g
 // partials[n_groups][blocks][nsurf][8] into stats[n_groups][nsurf][8].  n_groups <= 65535, nsurf <= RTPB_MAX_SURFACES.
 int launch_foot_final(const double* partials, double* stats, int64_t n_groups, int64_t blocks, int32_t nsurf,
                       hipStream_t st);
+
+// The same for the transmission statistics (trans_final_kernel, rtpb_transmission.hip): partials[n_groups][blocks]
+// [nsurf][5] into stats[n_groups][nsurf][5].  And what the transmission calls share before the device is touched:
+// every coating finite with mode 0 or 1 and value in [0, 1], 1 <= q_bits <= 40 (RTPB_E_INVALID) and group_size *
+// 2^q_bits <= 2^53 (RTPB_E_LIMIT); and the refusal of a plan whose media the host does not evaluate (a POLY6
+// material: RTPB_E_INVALID), by rtpb_plan_media and the fused entry points alike.  `call` names the call.
+int launch_trans_final(const double* partials, double* stats, int64_t n_groups, int64_t blocks, int32_t nsurf,
+                       hipStream_t st);
+int trans_check(const char* call, const double* coatings, int32_t nsurf, int32_t q_bits, int64_t group_size);
+int trans_plan_check(const char* call, const rtpb_plan* plan);
 
 // What the two image calls share (rtpb_image.hip): the checks of the image arguments -- `call` names the call in the
 // message ("spot-image", "image-sweep"), group_size is the rays per group -- and the zeroing of a call's n_groups

@@ -10,6 +10,7 @@
 #include "rtpb_internal.h"
 
 #include "rtpb_foot.h"
+#include "rtpb_trans.h"
 #include "rtpb_wavemap.h"
 
 namespace {
@@ -338,6 +339,29 @@ __device__ __forceinline__ double foot_block_reduce(rtpb::FootRay& f, double (*t
         for (int w = 1; w < 4; ++w) v = rtpb::foot_col(t, v, tab[w][t]);
     }
     return v;
+}
+
+// Transmission statistics (rtpb_trans.h: trans_ray, trans_merge): the footprints' wave reduction with another merge.
+// Sums of integers that stay exact, a minimum and a maximum: any order gives the same bits.
+template <int CTRL>
+__device__ __forceinline__ void trans_dpp_step(rtpb::TransRay& f) {
+    rtpb::TransRay o;
+#pragma unroll
+    for (int c = 0; c < rtpb::kTransCols; ++c) o.v[c] = foot_dpp<CTRL>(f.v[c]);
+    rtpb::trans_merge(f, o);
+}
+__device__ __forceinline__ void trans_wave_reduce(rtpb::TransRay& f) {
+    trans_dpp_step<0xB1>(f);        // quad_perm [1, 0, 3, 2]
+    trans_dpp_step<0x4E>(f);        // quad_perm [2, 3, 0, 1]
+    trans_dpp_step<0x124>(f);       // row_ror 4
+    trans_dpp_step<0x128>(f);       // row_ror 8
+#pragma unroll
+    for (int w = 16; w <= 32; w <<= 1) {
+        rtpb::TransRay o;
+#pragma unroll
+        for (int c = 0; c < rtpb::kTransCols; ++c) o.v[c] = __shfl_xor(f.v[c], w, 64);
+        rtpb::trans_merge(f, o);
+    }
 }
 
 }  // namespace

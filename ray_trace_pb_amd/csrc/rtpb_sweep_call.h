@@ -196,6 +196,58 @@ struct SweepHost<kFootStats> : SweepMode<kFootStats> {
     }
 };
 
+// Transmission: one coating per surface of the plan (host, nsurf x kTransCoat) behind the SweepTrans words -- nothing
+// per group; the workspace holds one partial per block of kSweepRays tiles (n_groups x blocks x nsurf x kTransCols) and
+// stats_out is n_groups x nsurf x kTransCols, combined by launch_trans_final.  The checks of the coatings and of q_bits
+// are rtpb_transmission_stats's (trans_check).
+template <>
+struct SweepHost<kTransStats> : SweepMode<kTransStats> {
+    struct Call : StatsCall {
+        const double* coatings;
+        int32_t n_coatings, q_bits;
+    };
+    template <int SRC>
+    static const char* f64_only() {
+        return "transmission-sweep: float64 plans only (the statistics are defined on the float64 history)";
+    }
+    template <int SRC>
+    static int check(int32_t nsurf, int64_t n_groups, const double* group_params, const SweepSource& s,
+                     const Call& c) {
+        if (n_groups <= 0 || !s.complete(SRC) || !group_params || !c.coatings || !c.workspace || !c.stats_out)
+            return fail(RTPB_E_INVALID, "bad transmission-sweep arguments");
+        if (c.n_coatings != nsurf)
+            return fail(RTPB_E_INVALID, "transmission-sweep: n_coatings (" + std::to_string(c.n_coatings) +
+                                            ") is not the plan's number of surfaces (" + std::to_string(nsurf) + ")");
+        if (nsurf > RTPB_MAX_SURFACES)
+            return fail(RTPB_E_LIMIT, "transmission-sweep: more than RTPB_MAX_SURFACES surfaces");
+        if (n_groups > 65535) return fail(RTPB_E_LIMIT, "transmission-sweep: too many groups or rays per group");
+        // (n_a * n_b: a product past int64 is past the limit too)
+        if (s.n_a > (0x7fffffffll * kBlock) / s.n_b)
+            return fail(RTPB_E_LIMIT, "transmission-sweep: too many groups or rays per group");
+        int rc = trans_check("transmission-sweep", c.coatings, nsurf, c.q_bits, s.n_a * s.n_b);
+        if (rc) return rc;
+        const int64_t tiles = (s.n_a * s.n_b + kBlock - 1) / kBlock;
+        const int64_t blocks = (tiles + kSweepRays - 1) / kSweepRays;
+        if (c.workspace_len / (int64_t(nsurf) * kTransCols) / blocks < n_groups)
+            return fail(RTPB_E_INVALID,
+                        std::string("transmission-sweep: workspace too small: need n_groups * ceil(ceil(") +
+                            rays_of<SRC>() + "/256)/2) * nsurf * 5 doubles");
+        return RTPB_OK;
+    }
+    static size_t head_doubles(int32_t nsurf) {
+        return sizeof(SweepTrans) / sizeof(double) + size_t(nsurf) * kTransCoat;
+    }
+    static void fill(const Call& c, int64_t, int32_t nsurf, char* head, char*) {
+        const SweepTrans h{c.workspace, std::ldexp(1.0, c.q_bits)};
+        std::memcpy(head, &h, sizeof(h));
+        std::memcpy(head + sizeof(h), c.coatings, size_t(nsurf) * kTransCoat * sizeof(double));
+    }
+    static int clear(const Call&, int64_t, hipStream_t) { return RTPB_OK; }
+    static int finish(const Call& c, int64_t n_groups, int64_t tiles, int32_t nsurf, hipStream_t st) {
+        return launch_trans_final(c.workspace, c.stats_out, n_groups, (tiles + kSweepRays - 1) / kSweepRays, nsurf, st);
+    }
+};
+
 // The counter modes have no workspace, no statistics and nothing after the sweep: the kernel adds into the call's
 // outputs, which the call clears first.  Their checks are the plane calls' between the sweep's own.
 struct CounterHost {
@@ -447,7 +499,7 @@ int sweep_impl(const rtpb_plan* plan_c, int32_t device, int64_t n_groups, const 
                             static_cast<unsigned>(pr.singles.size()));
             if (pre_n && f == 0) hipLaunchKernelGGL((sweep_kernel<TS, 16, false, NS, SRC>), grid, dim3(kBlock), 0, st, as);
             else if (pre_n) hipLaunchKernelGGL((sweep_kernel<TS, 17, false, NS, SRC>), grid, dim3(kBlock), 0, st, as);
-            else if constexpr (!kVar)                                                                        // POLY6 media
+            else if constexpr (!kVar && !Mode::kHostMedia)                                                   // POLY6 media
                 hipLaunchKernelGGL((sweep_kernel<TS, 3, false, NS, SRC>), grid, dim3(kBlock), 0, st, as);
         }
     };

@@ -16,6 +16,7 @@
 //   wavefront map   kMapStats = 4     rtpb_wavefront_map_sweep                       rtpb_sweep_wavemap[_beam].hip
 //   final rays      kFinalRays = 8    rtpb_final_rays_variants                       rtpb_sweep_wave_variants[_beam].hip
 //   footprint       kFootStats = 32   rtpb_footprint_sweep                           rtpb_sweep_foot[_beam].hip
+//   transmission    kTransStats = 64  rtpb_transmission_sweep                        rtpb_sweep_trans[_beam].hip
 //
 // What the sweep shares with the plane kernels (the statistics, the counters' contribution rules) is rtpb_stats.h, the
 // host arithmetic of a call (row planning, media table, upload layout) rtpb_sweep_host.h.
@@ -142,6 +143,8 @@ constexpr int kStateRows = 11;                     // bundle state per lane: x y
 //   kBundles    bundle rows allowed (their shared first surface keeps no phase)
 //   kF32        float32 storage allowed
 //   kPlans, kVariants   the systems it has entry points for
+//   kHostMedia  the mode reads the group's indices itself, so only the instantiations with host-evaluated media exist
+//               (FEAT bit 4): its entry points refuse the plans that have none (a POLY6 material)
 //   red_rows(bundle)    rows of the LDS reduction buffer
 //   Head, kPerGroup     the header of the mode's block of the upload (void: none) and the doubles per group behind it
 // and, for the modes without tile partials (kCols = 0) and without history steps, the device hook that the kernel
@@ -152,15 +155,17 @@ constexpr int kStateRows = 11;                     // bundle state per lane: x y
 // code (register allocation and scheduling), and a cleanup leaves the device code as it is (tools/isa_compare.py).
 constexpr int kHistorySteps = 0;
 constexpr int kImageStats = 0, kEnergyStats = 2, kMapStats = 4, kFinalRays = 8, kFootStats = 32;
+constexpr int kTransStats = 64;
 
 template <int NS>
-struct SweepMode;       // (only the eight specialisations below exist)
+struct SweepMode;       // (only the nine specialisations below exist)
 
 struct SweepModeDefaults {      // (what most modes are)
     static constexpr int kCols = 0;
     static constexpr int kSteps = kPosOnly;
     static constexpr int kWpe = RTPB_SWEEP_WPE;
     static constexpr bool kBundles = true, kF32 = true, kPlans = true, kVariants = false;
+    static constexpr bool kHostMedia = false;
     static constexpr int red_rows(bool) { return 1; }
     using Head = void;
     static constexpr int kPerGroup = 0;
@@ -346,6 +351,25 @@ struct SweepMode<kFootStats> : SweepModeHead<SweepFoot> {
     static constexpr bool kBundles = false, kF32 = false;
 };
 
+// Transmission (rtpb_transmission_sweep): the transmission statistics of EVERY surface (rtpb_trans.h, kTransCols
+// columns) -- the footprint mode with another rule per ray and surface.  The rule reads what the history steps hold
+// after a surface anyway: the at-plane with the incoming direction, the ray after the surface with the outgoing one,
+// and the two indices n_cur and n_next (host-evaluated: scalar operands).  One cum per ray of the lane is carried
+// across the surface runs, as n_cur is.  The combination per surface, the waves' rows in LDS (10 KB) and the block
+// epilogue are the footprints', with trans_merge / trans_col.  Its block of the upload: where the block partials go
+// and 2^q_bits, then the surfaces' coatings (kTransCoat doubles each) -- nothing per group.
+struct SweepTrans {
+    double* partials;
+    double scale;
+};
+static_assert(sizeof(SweepTrans) == 2 * sizeof(double), "the coatings follow it");
+template <>
+struct SweepMode<kTransStats> : SweepModeHead<SweepTrans> {
+    static constexpr int kSteps = kHistorySteps;
+    static constexpr int kWpe = RTPB_WAVE_WPE;
+    static constexpr bool kBundles = false, kF32 = false, kHostMedia = true;
+};
+
 #define RTPB_SWEEP_ATTR(NS) __attribute__((amdgpu_waves_per_eu(SweepMode<NS>::kWpe, 8)))
 
 // SRC = kSrcBeam: the generator of a collimated beam; a bundle row's groups share the beam (pt and frame) as the
@@ -361,13 +385,20 @@ __global__ __launch_bounds__(kBlock) RTPB_SWEEP_ATTR(NS) void sweep_kernel(Sweep
     static_assert(!BUNDLE || (Mode::kBundles && (FEAT & 16) != 0),
                   "bundles: a mode that allows them, host-evaluated media");
     static_assert(sizeof(TS) == 8 || Mode::kF32, "the mode's storage is float64");
-    constexpr bool kHistory = Mode::kSteps == kHistorySteps;    // the at-plane kept: the footprints
+    static_assert(!Mode::kHostMedia || (FEAT & 16) != 0, "the mode reads host-evaluated media");
+    // the at-plane kept: the footprints and the transmission
+    constexpr bool kHistory = Mode::kSteps == kHistorySteps;
+    constexpr bool kTrans = NS == kTransStats;
     constexpr int kRedRows = Mode::red_rows(BUNDLE);
     __shared__ double red[kRedRows][kBlock];
     __shared__ double state[BUNDLE ? kStateRows : 1][kBlock];
-    // footprints: per wave, one row per surface (16 KB)
+    // footprints: per wave, one row per surface (16 KB); transmission likewise (10 KB)
     double (*foot_tab)[RTPB_MAX_SURFACES][kFootCols] = nullptr;
-    if constexpr (kHistory) {
+    [[maybe_unused]] double (*trans_tab)[RTPB_MAX_SURFACES][kTransCols] = nullptr;
+    if constexpr (kTrans) {
+        __shared__ double trans_lds[kBlock / 64][RTPB_MAX_SURFACES][kTransCols];
+        trans_tab = trans_lds;
+    } else if constexpr (kHistory) {
         __shared__ double foot_lds[kBlock / 64][RTPB_MAX_SURFACES][kFootCols];
         foot_tab = foot_lds;
     }
@@ -449,6 +480,7 @@ __global__ __launch_bounds__(kBlock) RTPB_SWEEP_ATTR(NS) void sweep_kernel(Sweep
     // branches needs (the ODT path of C5: 12 axial spheres, a lens, a flat = 3 runs).
     double rxy[kSweepRays];
     bool live[kSweepRays];              // history steps: the lane's ray q is one of its group's
+    [[maybe_unused]] double cum[kSweepRays];        // transmission: ray q's product over the surfaces so far
     auto trace_from = [&](int s) {
         while (s < a.nsurf) {
             const int code = code_of(s);
@@ -467,7 +499,7 @@ __global__ __launch_bounds__(kBlock) RTPB_SWEEP_ATTR(NS) void sweep_kernel(Sweep
                     for (int q = 0; q < kSweepRays; ++q) n_next[q] = (BUNDLE || q == 0) ? mat_n(q, s + 1) : n_next[0];
                     auto none = [](const Ray<double>&) {};
                     Ray<double> o[kSweepRays];
-                    [[maybe_unused]] double at[kSweepRays][3];
+                    [[maybe_unused]] double at[kSweepRays][kTrans ? 6 : 3];
 #pragma unroll
                     for (int q = 0; q < kSweepRays; ++q) {
                         const DevSurface<double> sd = (BUNDLE || q == 0) ? surface_for(q, s, base)
@@ -475,6 +507,9 @@ __global__ __launch_bounds__(kBlock) RTPB_SWEEP_ATTR(NS) void sweep_kernel(Sweep
                         if constexpr (kHistory) {
                             auto keep = [&](const Ray<double>& p) {
                                 at[q][0] = p.x; at[q][1] = p.y; at[q][2] = p.z;
+                                if constexpr (kTrans) {
+                                    at[q][3] = p.dx; at[q][4] = p.dy; at[q][5] = p.dz;
+                                }
                             };
                             surface_step<double, K, A, kMode>(sd, r[q], n_cur[q], n_next[q], iwl[q], keep, o[q],
                                                               static_cast<GuardBranch*>(nullptr));
@@ -484,7 +519,26 @@ __global__ __launch_bounds__(kBlock) RTPB_SWEEP_ATTR(NS) void sweep_kernel(Sweep
                                                               kCarry ? &rxy[q] : nullptr);
                         }
                     }
-                    if constexpr (kHistory) {
+                    if constexpr (kTrans) {
+                        // the surface's coating and the call's 2^q_bits: the block's, so scalar loads
+                        const cptr<double> cp = Mode::tail(a) + kTransCoat * s;
+                        const double coat_mode = cp[0], coat_value = cp[1];
+                        const double scale = Mode::head(a)->scale;
+                        TransRay acc = trans_none();
+#pragma unroll
+                        for (int q = 0; q < kSweepRays; ++q) {
+                            double t;
+                            const bool pass = trans_ray(at[q][0], at[q][1], at[q][2], at[q][3], at[q][4], at[q][5],
+                                                        o[q].x, o[q].y, o[q].z, o[q].dx, o[q].dy, o[q].dz, n_cur[q],
+                                                        n_next[q], coat_mode, coat_value, t, cum[q]);
+                            if (live[q] && pass) trans_merge(acc, trans_term(t, cum[q], scale));
+                        }
+                        trans_wave_reduce(acc);
+                        if ((tid & 63) == 0) {
+#pragma unroll
+                            for (int c = 0; c < kTransCols; ++c) trans_tab[tid >> 6][s][c] = acc.v[c];
+                        }
+                    } else if constexpr (kHistory) {
                         // the surface's frame: the block's, so scalar loads
                         const cptr<double> fp = Mode::tail(a) + kFootFrame * s;
                         const double fr[kFootFrame] = {fp[0], fp[1], fp[2], fp[3], fp[4], fp[5], fp[6], fp[7], fp[8]};
@@ -579,8 +633,23 @@ __global__ __launch_bounds__(kBlock) RTPB_SWEEP_ATTR(NS) void sweep_kernel(Sweep
 #pragma unroll
             for (int q = 0; q < kSweepRays; ++q) live[q] = tile[q] * kBlock + tid < a.gsize;
         }
+        if constexpr (kTrans) {
+#pragma unroll
+            for (int q = 0; q < kSweepRays; ++q) cum[q] = 1.0;
+        }
         trace_from(0);
-        if constexpr (kHistory) {
+        if constexpr (kTrans) {
+            // the block's partial: the four waves' rows combined, [group][block][surface][kTransCols]
+            __syncthreads();
+            double* out = Mode::head(a)->partials + (grp[0] * int64_t(gridDim.x) + blockIdx.x) * a.nsurf * kTransCols;
+            for (int k = tid; k < a.nsurf * kTransCols; k += kBlock) {
+                const int s = k / kTransCols, c = k % kTransCols;
+                double v = trans_tab[0][s][c];
+#pragma unroll
+                for (int w = 1; w < kBlock / 64; ++w) v = trans_col(c, v, trans_tab[w][s][c]);
+                out[k] = v;
+            }
+        } else if constexpr (kHistory) {
             // the block's partial: the four waves' rows combined, [group][block][surface][kFootCols]
             __syncthreads();
             double* out = Mode::head(a)->partials + (grp[0] * int64_t(gridDim.x) + blockIdx.x) * a.nsurf * kFootCols;
