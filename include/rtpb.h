@@ -68,8 +68,10 @@ extern "C" {
                                     rtpb_wavefront_map_sweep / rtpb_wavefront_map_sweep_collimated (pupil OPD
                                     maps), then rtpb_transmission_stats / rtpb_transmission_sweep /
                                     rtpb_transmission_sweep_collimated / rtpb_ray_transmission / rtpb_plan_media
-                                    (Fresnel losses per surface and throughput) joined within 10: new symbols
-                                    only, nothing existing changed */
+                                    (Fresnel losses per surface and throughput), then rtpb_polarisation_stats /
+                                    rtpb_polarisation_sweep / rtpb_polarisation_sweep_collimated /
+                                    rtpb_ray_polarisation (two field vectors per ray through every surface) joined
+                                    within 10: new symbols only, nothing existing changed */
 
 /* ---- error codes ---------------------------------------------------------------------------- */
 #define RTPB_OK 0
@@ -761,6 +763,73 @@ int rtpb_transmission_sweep_collimated(const rtpb_plan* plan, int32_t device, in
                                        const double* group_params, const double* group_frames, int64_t n_disps,
                                        int64_t nphis, const double* offsets, const double* phi_cos_sin,
                                        const double* coatings, int32_t n_coatings, int32_t q_bits, double* workspace,
+                                       int64_t workspace_len, double* stats_out, void* stream);
+
+/* POLARISATION statistics: two real field vectors per ray carried through every surface -- what the transmission
+   statistics leave out.  Each ray is launched behind a linear polariser along the unit vector `polariser` with the
+   STATE E1 (the axis projected across the ray, unit length) and E2 = ray x E1, or with NO state (all NaN); |E|^2 is
+   energy.  Defined on the stored history like the transmission statistics, with their A, B, n1, n2 and media; a = A.dxyz
+   and b = B.dxyz are the incoming and outgoing directions.  float64 ONLY.  Every operation one rounded IEEE operation
+   in this order, no FMA, with p.q = (p.x*q.x + p.y*q.y) + p.z*q.z, p x q = (p.y*q.z - p.z*q.y, p.z*q.x - p.x*q.z,
+   p.x*q.y - p.y*q.x) and sqrt correctly rounded:
+       LAUNCH from the ray's first direction a (plane 0), u = polariser:
+         c = a x u, cc = c.c; !(cc >= 2^-40): no state.  Else w = c x a, E1 = w / sqrt(w.w), E2 = a x E1
+       the ray PASSES surface s exactly when the transmission statistics say so; a ray that does not has no state
+       from then on
+       a surface's COATING is two doubles {mode, value}, value in [0, 1]; amplitude = sqrt(value), formed once per call:
+         mode 0, CONSTANT: ts = tp = amplitude.   mode 1, FRESNEL (value ignored): ts = tp = 1 where n1 == n2; else
+           ts = sqrt(1 - rs*rs), tp = sqrt(1 - rp*rp) with the transmission rule's rs and rp (flux-normalised
+           amplitudes: no n*cos factor appears).  Then c = a x b, cc = c.c, d = 1 + a.b; !(d >= 2^-20): no state; else
+           for E = E1 and E = E2:
+             k  = (ts - tp)*((E.c)/cc) where cc >= 2^-900, else 0
+             E' = tp*E + k*c                     f = (E'.b)/d                     E_out = E' - (a + b)*f
+           (the s and p amplitudes about the plane of incidence, then the minimal rotation that takes a to b:
+           E_out.b = 0 by construction)
+         mode 2, MIRROR (value: the reflectance): m = a - b, mm = m.m; !(mm >= 2^-40): no state; else
+             g = (E.m)/mm                        E_out = amplitude*((2*g)*m - E)
+       the ANALYSER after the surface, w = analyser (a unit vector): x = b x w, xx = x.x; p = E_i.x, l_i = (p*p)/xx:
+       the energy of state i behind an analyser CROSSED with w
+       the ray is VALID at s when it passes, all six components of E_out are finite and xx >= 2^-40
+       q(v) = rint((v <= 1 ? v : 1) * 2^q_bits)
+   What it is NOT: the amplitudes are real -- no retardance (total internal reflection, metal mirrors), no thin films,
+   no birefringence; the state of a ray that totally reflects at a refracting surface ends.
+   stats_out (device, n_groups x nsurf x 6 doubles, all integer-valued), per (group, surface):
+       0  the rays that pass      1  the valid rays      2, 3  the sums of q(E1.E1) and q(E2.E2) over the valid rays
+       4, 5  the sums of q(l1) and q(l2) over them
+   q_bits, media, coatings, the limits and the order of the checks are rtpb_transmission_stats's, with mode 2 allowed;
+   polariser and analyser: HOST, three doubles each, finite and not all zero (RTPB_E_INVALID otherwise), taken as
+   given -- the caller normalises them.
+   workspace: device doubles, >= n_groups * ceil(group_size / 256) * nsurf * 6. */
+int rtpb_polarisation_stats(int32_t device, int32_t dtype, const void* history, int64_t group_size, int64_t n_groups,
+                            int32_t nsurf, const double* media, const double* coatings, const double polariser[3],
+                            const double analyser[3], int32_t q_bits, double* workspace, int64_t workspace_len,
+                            double* stats_out, void* stream);
+
+/* Each ray's two final field vectors, for a caller's own sums (a vectorial PSF, say): out (device, 6 doubles per ray of
+   the history: E1.xyz, E2.xyz) holds the state after the last surface, unquantised, NaN for a ray without one.  The
+   arguments and checks of rtpb_polarisation_stats without the analyser, q_bits and the workspace. */
+int rtpb_ray_polarisation(int32_t device, int32_t dtype, const void* history, int64_t group_size, int64_t n_groups,
+                          int32_t nsurf, const double* media, const double* coatings, const double polariser[3],
+                          double* out, void* stream);
+
+/* Fused polarisation sweep: rtpb_transmission_sweep's arguments with the two axes between n_coatings and q_bits.  The
+   surface steps are the footprint sweep's; the state is launched from the generated ray's direction and carried in
+   registers.
+   CONTRACT: stats_out (device, n_groups x nsurf x 6) is bit-identical to rtpb_polarisation_stats of the stored history
+   of the same rays with the media rtpb_plan_media gives for the groups' wavelengths.
+   workspace: device doubles, >= n_groups * ceil(ceil(rays per group / 256) / 2) * nsurf * 6.  float64 plans without
+   POLY6 media only; the group and tile limits and error codes of rtpb_transmission_sweep. */
+int rtpb_polarisation_sweep(const rtpb_plan* plan, int32_t device, int64_t n_groups, const double* group_params,
+                            int64_t n_thetas, int64_t nphis, const double center_ray[3], const double ex[3],
+                            const double ey[3], const double* theta_cos_sin, const double* phi_cos_sin,
+                            const double* coatings, int32_t n_coatings, const double polariser[3],
+                            const double analyser[3], int32_t q_bits, double* workspace, int64_t workspace_len,
+                            double* stats_out, void* stream);
+int rtpb_polarisation_sweep_collimated(const rtpb_plan* plan, int32_t device, int64_t n_groups,
+                                       const double* group_params, const double* group_frames, int64_t n_disps,
+                                       int64_t nphis, const double* offsets, const double* phi_cos_sin,
+                                       const double* coatings, int32_t n_coatings, const double polariser[3],
+                                       const double analyser[3], int32_t q_bits, double* workspace,
                                        int64_t workspace_len, double* stats_out, void* stream);
 
 /* VARIANT sweeps (tolerance runs): rtpb_focus_sweep / rtpb_focus_sweep_collimated over MANY systems in one call.

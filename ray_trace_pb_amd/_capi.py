@@ -168,6 +168,15 @@ SIGNATURES = {
                                                _i64, _P, _P]),
     "rtpb_transmission_sweep_collimated": (ctypes.c_int, [_P, _i32, _i64, _P, _P, _i64, _i64, _P, _P, _P, _i32, _i32,
                                                           _P, _i64, _P, _P]),
+    # (the transmission calls' shape with the polariser and the analyser axes before q_bits; the rays' call has no
+    # analyser)
+    "rtpb_polarisation_stats": (ctypes.c_int, [_i32, _i32, _P, _i64, _i64, _i32, _P, _P, _P, _P, _i32, _P, _i64, _P,
+                                               _P]),
+    "rtpb_ray_polarisation": (ctypes.c_int, [_i32, _i32, _P, _i64, _i64, _i32, _P, _P, _P, _P, _P]),
+    "rtpb_polarisation_sweep": (ctypes.c_int, [_P, _i32, _i64, _P, _i64, _i64, _P, _P, _P, _P, _P, _P, _i32, _P, _P,
+                                               _i32, _P, _i64, _P, _P]),
+    "rtpb_polarisation_sweep_collimated": (ctypes.c_int, [_P, _i32, _i64, _P, _P, _i64, _i64, _P, _P, _P, _i32, _P,
+                                                          _P, _i32, _P, _i64, _P, _P]),
     "rtpb_set_tuning":(ctypes.c_int, [ctypes.c_char_p, _i64]),
     "rtpb_timing_enable": (ctypes.c_int, [_i32]),
     "rtpb_timing_collect": (ctypes.c_int, [ctypes.POINTER(_dbl), ctypes.POINTER(_i64)]),

@@ -24,6 +24,10 @@
 //                          the fused transmission sweep (Fresnel losses per surface and throughput; fans, beams)
 //   rtpb_transmission.hip  the transmission statistics of a stored history, their second pass, each ray's energy
 //                          weight and a plan's indices (rtpb_trans.h: the per-ray rule, plain C++)
+//   rtpb_sweep_pol.hip, rtpb_sweep_pol_beam.hip
+//                          the fused polarisation sweep (two field vectors per ray through every surface; fans, beams)
+//   rtpb_polarisation.hip  the polarisation statistics of a stored history, their second pass and each ray's final
+//                          field vectors (rtpb_pol.h: the per-ray rule, plain C++)
 //   rtpb_surface_ops.hip   propagate_ray2plane and the user-geometry hook kernels
 #pragma once
 
@@ -478,6 +482,16 @@ int launch_trans_final(const double* partials, double* stats, int64_t n_groups, 
                        hipStream_t st);
 int trans_check(const char* call, const double* coatings, int32_t nsurf, int32_t q_bits, int64_t group_size);
 int trans_plan_check(const char* call, const rtpb_plan* plan);
+
+// The same for the polarisation statistics (pol_final_kernel, rtpb_polarisation.hip): partials[n_groups][blocks]
+// [nsurf][6] into stats[n_groups][nsurf][6].  And what the polarisation calls share before the device is touched:
+// every coating finite with mode 0, 1 or 2 and value in [0, 1], both axes finite and not zero (analyser NULL: not
+// checked, rtpb_ray_polarisation has none), 1 <= q_bits <= 40 (RTPB_E_INVALID) and group_size * 2^q_bits <= 2^53
+// (RTPB_E_LIMIT).  `call` names the call.
+int launch_pol_final(const double* partials, double* stats, int64_t n_groups, int64_t blocks, int32_t nsurf,
+                     hipStream_t st);
+int pol_check(const char* call, const double* coatings, int32_t nsurf, const double* polariser, const double* analyser,
+              int32_t q_bits, int64_t group_size);
 
 // What the two image calls share (rtpb_image.hip): the checks of the image arguments -- `call` names the call in the
 // message ("spot-image", "image-sweep"), group_size is the rays per group -- and the zeroing of a call's n_groups

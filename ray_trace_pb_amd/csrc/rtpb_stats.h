@@ -2,14 +2,15 @@
 // rtpb_wavemap.hip) and the fused sweep (rtpb_sweep.hip) share: the statistics sets, the one definition of a ray's
 // contribution to the focus statistics, to the wavefront statistics, to the Huygens PSF, to a spot image and to the
 // energy curves, the footprint statistics' term (rtpb_foot.h, plain C++ so that the host can run it) and its wave and
-// block reductions, the wavefront map's rule (rtpb_wavemap.h, plain C++ likewise) and its wave-level adds,
-// the wave's aggregated image adds, the reduction's argument block and its block-wide tree.  Everything here has
+// block reductions, the transmission and polarisation rules (rtpb_trans.h, rtpb_pol.h) with their wave reductions, the
+// wavefront map's rule (rtpb_wavemap.h, plain C++ likewise) and its wave-level adds, the wave's aggregated image adds, the reduction's argument block and its block-wide tree.  Everything here has
 // internal linkage, as it had inside the one unit: each unit's kernels take its own SpotArgs.
 #pragma once
 
 #include "rtpb_internal.h"
 
 #include "rtpb_foot.h"
+#include "rtpb_pol.h"
 #include "rtpb_trans.h"
 #include "rtpb_wavemap.h"
 
@@ -361,6 +362,29 @@ __device__ __forceinline__ void trans_wave_reduce(rtpb::TransRay& f) {
 #pragma unroll
         for (int c = 0; c < rtpb::kTransCols; ++c) o.v[c] = __shfl_xor(f.v[c], w, 64);
         rtpb::trans_merge(f, o);
+    }
+}
+
+// Polarisation statistics (rtpb_pol.h: pol_surface, pol_term, pol_merge): the same wave reduction, every column a sum
+// of integers that stays exact.
+template <int CTRL>
+__device__ __forceinline__ void pol_dpp_step(rtpb::PolRay& f) {
+    rtpb::PolRay o;
+#pragma unroll
+    for (int c = 0; c < rtpb::kPolCols; ++c) o.v[c] = foot_dpp<CTRL>(f.v[c]);
+    rtpb::pol_merge(f, o);
+}
+__device__ __forceinline__ void pol_wave_reduce(rtpb::PolRay& f) {
+    pol_dpp_step<0xB1>(f);          // quad_perm [1, 0, 3, 2]
+    pol_dpp_step<0x4E>(f);          // quad_perm [2, 3, 0, 1]
+    pol_dpp_step<0x124>(f);         // row_ror 4
+    pol_dpp_step<0x128>(f);         // row_ror 8
+#pragma unroll
+    for (int w = 16; w <= 32; w <<= 1) {
+        rtpb::PolRay o;
+#pragma unroll
+        for (int c = 0; c < rtpb::kPolCols; ++c) o.v[c] = __shfl_xor(f.v[c], w, 64);
+        rtpb::pol_merge(f, o);
     }
 }
 

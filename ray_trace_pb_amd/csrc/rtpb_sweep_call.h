@@ -248,6 +248,69 @@ struct SweepHost<kTransStats> : SweepMode<kTransStats> {
     }
 };
 
+// Polarisation: the transmission mode's call with the two unit axes (host, three doubles each); behind the SweepPol
+// words the coatings ride as {mode, amplitude} (pol_coat_amplitude, once per call).  The workspace holds one partial
+// per block of kSweepRays tiles (n_groups x blocks x nsurf x kPolCols) and stats_out is n_groups x nsurf x kPolCols,
+// combined by launch_pol_final.  The checks of the coatings, the axes and q_bits are rtpb_polarisation_stats's
+// (pol_check).
+template <>
+struct SweepHost<kPolStats> : SweepMode<kPolStats> {
+    struct Call : StatsCall {
+        const double* coatings;
+        int32_t n_coatings;
+        const double* polariser;
+        const double* analyser;
+        int32_t q_bits;
+    };
+    template <int SRC>
+    static const char* f64_only() {
+        return "polarisation-sweep: float64 plans only (the statistics are defined on the float64 history)";
+    }
+    template <int SRC>
+    static int check(int32_t nsurf, int64_t n_groups, const double* group_params, const SweepSource& s,
+                     const Call& c) {
+        if (n_groups <= 0 || !s.complete(SRC) || !group_params || !c.coatings || !c.polariser || !c.analyser ||
+            !c.workspace || !c.stats_out)
+            return fail(RTPB_E_INVALID, "bad polarisation-sweep arguments");
+        if (c.n_coatings != nsurf)
+            return fail(RTPB_E_INVALID, "polarisation-sweep: n_coatings (" + std::to_string(c.n_coatings) +
+                                            ") is not the plan's number of surfaces (" + std::to_string(nsurf) + ")");
+        if (nsurf > RTPB_MAX_SURFACES)
+            return fail(RTPB_E_LIMIT, "polarisation-sweep: more than RTPB_MAX_SURFACES surfaces");
+        if (n_groups > 65535) return fail(RTPB_E_LIMIT, "polarisation-sweep: too many groups or rays per group");
+        // (n_a * n_b: a product past int64 is past the limit too)
+        if (s.n_a > (0x7fffffffll * kBlock) / s.n_b)
+            return fail(RTPB_E_LIMIT, "polarisation-sweep: too many groups or rays per group");
+        int rc = pol_check("polarisation-sweep", c.coatings, nsurf, c.polariser, c.analyser, c.q_bits, s.n_a * s.n_b);
+        if (rc) return rc;
+        const int64_t tiles = (s.n_a * s.n_b + kBlock - 1) / kBlock;
+        const int64_t blocks = (tiles + kSweepRays - 1) / kSweepRays;
+        if (c.workspace_len / (int64_t(nsurf) * kPolCols) / blocks < n_groups)
+            return fail(RTPB_E_INVALID,
+                        std::string("polarisation-sweep: workspace too small: need n_groups * ceil(ceil(") +
+                            rays_of<SRC>() + "/256)/2) * nsurf * 6 doubles");
+        return RTPB_OK;
+    }
+    static size_t head_doubles(int32_t nsurf) {
+        return sizeof(SweepPol) / sizeof(double) + size_t(nsurf) * kTransCoat;
+    }
+    static void fill(const Call& c, int64_t, int32_t nsurf, char* head, char*) {
+        const SweepPol h{c.workspace, std::ldexp(1.0, c.q_bits),
+                         {c.polariser[0], c.polariser[1], c.polariser[2]},
+                         {c.analyser[0], c.analyser[1], c.analyser[2]}};
+        std::memcpy(head, &h, sizeof(h));
+        double* const coat = reinterpret_cast<double*>(head + sizeof(h));
+        for (int32_t k = 0; k < nsurf; ++k) {
+            coat[kTransCoat * k] = c.coatings[kTransCoat * k];
+            coat[kTransCoat * k + 1] = pol_coat_amplitude(c.coatings[kTransCoat * k], c.coatings[kTransCoat * k + 1]);
+        }
+    }
+    static int clear(const Call&, int64_t, hipStream_t) { return RTPB_OK; }
+    static int finish(const Call& c, int64_t n_groups, int64_t tiles, int32_t nsurf, hipStream_t st) {
+        return launch_pol_final(c.workspace, c.stats_out, n_groups, (tiles + kSweepRays - 1) / kSweepRays, nsurf, st);
+    }
+};
+
 // The counter modes have no workspace, no statistics and nothing after the sweep: the kernel adds into the call's
 // outputs, which the call clears first.  Their checks are the plane calls' between the sweep's own.
 struct CounterHost {

@@ -17,6 +17,7 @@
 //   final rays      kFinalRays = 8    rtpb_final_rays_variants                       rtpb_sweep_wave_variants[_beam].hip
 //   footprint       kFootStats = 32   rtpb_footprint_sweep                           rtpb_sweep_foot[_beam].hip
 //   transmission    kTransStats = 64  rtpb_transmission_sweep                        rtpb_sweep_trans[_beam].hip
+//   polarisation    kPolStats = 128   rtpb_polarisation_sweep                        rtpb_sweep_pol[_beam].hip
 //
 // What the sweep shares with the plane kernels (the statistics, the counters' contribution rules) is rtpb_stats.h, the
 // host arithmetic of a call (row planning, media table, upload layout) rtpb_sweep_host.h.
@@ -156,9 +157,10 @@ constexpr int kStateRows = 11;                     // bundle state per lane: x y
 constexpr int kHistorySteps = 0;
 constexpr int kImageStats = 0, kEnergyStats = 2, kMapStats = 4, kFinalRays = 8, kFootStats = 32;
 constexpr int kTransStats = 64;
+constexpr int kPolStats = 128;
 
 template <int NS>
-struct SweepMode;       // (only the nine specialisations below exist)
+struct SweepMode;       // (only the ten specialisations below exist)
 
 struct SweepModeDefaults {      // (what most modes are)
     static constexpr int kCols = 0;
@@ -370,6 +372,30 @@ struct SweepMode<kTransStats> : SweepModeHead<SweepTrans> {
     static constexpr bool kBundles = false, kF32 = false, kHostMedia = true;
 };
 
+// Polarisation (rtpb_polarisation_sweep): the polarisation statistics of EVERY surface (rtpb_pol.h, kPolCols columns)
+// -- the transmission mode with a state of kPolState doubles per ray of the lane in cum's place, launched from the
+// generated ray's direction and carried across the surface runs.  It reads what the transmission rule reads (the
+// at-plane with the incoming direction, the ray after the surface, n_cur and n_next).  The combination per surface, the
+// waves' rows in LDS (12 KB) and the block epilogue are the transmission's, with pol_merge (every column a sum).  Its
+// block of the upload: where the block partials go, 2^q_bits, the polariser and the analyser axes, then the surfaces'
+// coatings as {mode, amplitude} (kTransCoat doubles each) -- nothing per group.  The state is 24 VGPRs a lane on top
+// of the transmission mode's, so the mode has an occupancy class of its own (the registers at each).
+#ifndef RTPB_POL_WPE
+#define RTPB_POL_WPE 3
+#endif
+struct SweepPol {
+    double* partials;
+    double scale;
+    double u[3], w[3];
+};
+static_assert(sizeof(SweepPol) == 8 * sizeof(double), "the coatings follow it");
+template <>
+struct SweepMode<kPolStats> : SweepModeHead<SweepPol> {
+    static constexpr int kSteps = kHistorySteps;
+    static constexpr int kWpe = RTPB_POL_WPE;
+    static constexpr bool kBundles = false, kF32 = false, kHostMedia = true;
+};
+
 #define RTPB_SWEEP_ATTR(NS) __attribute__((amdgpu_waves_per_eu(SweepMode<NS>::kWpe, 8)))
 
 // SRC = kSrcBeam: the generator of a collimated beam; a bundle row's groups share the beam (pt and frame) as the
@@ -386,16 +412,21 @@ __global__ __launch_bounds__(kBlock) RTPB_SWEEP_ATTR(NS) void sweep_kernel(Sweep
                   "bundles: a mode that allows them, host-evaluated media");
     static_assert(sizeof(TS) == 8 || Mode::kF32, "the mode's storage is float64");
     static_assert(!Mode::kHostMedia || (FEAT & 16) != 0, "the mode reads host-evaluated media");
-    // the at-plane kept: the footprints and the transmission
+    // the at-plane kept: the footprints, the transmission and the polarisation
     constexpr bool kHistory = Mode::kSteps == kHistorySteps;
     constexpr bool kTrans = NS == kTransStats;
+    constexpr bool kPol = NS == kPolStats;
     constexpr int kRedRows = Mode::red_rows(BUNDLE);
     __shared__ double red[kRedRows][kBlock];
     __shared__ double state[BUNDLE ? kStateRows : 1][kBlock];
     // footprints: per wave, one row per surface (16 KB); transmission likewise (10 KB)
     double (*foot_tab)[RTPB_MAX_SURFACES][kFootCols] = nullptr;
     [[maybe_unused]] double (*trans_tab)[RTPB_MAX_SURFACES][kTransCols] = nullptr;
-    if constexpr (kTrans) {
+    [[maybe_unused]] double (*pol_tab)[RTPB_MAX_SURFACES][kPolCols] = nullptr;      // polarisation: 12 KB
+    if constexpr (kPol) {
+        __shared__ double pol_lds[kBlock / 64][RTPB_MAX_SURFACES][kPolCols];
+        pol_tab = pol_lds;
+    } else if constexpr (kTrans) {
         __shared__ double trans_lds[kBlock / 64][RTPB_MAX_SURFACES][kTransCols];
         trans_tab = trans_lds;
     } else if constexpr (kHistory) {
@@ -481,6 +512,7 @@ __global__ __launch_bounds__(kBlock) RTPB_SWEEP_ATTR(NS) void sweep_kernel(Sweep
     double rxy[kSweepRays];
     bool live[kSweepRays];              // history steps: the lane's ray q is one of its group's
     [[maybe_unused]] double cum[kSweepRays];        // transmission: ray q's product over the surfaces so far
+    [[maybe_unused]] double pol[kSweepRays][kPolState];     // polarisation: ray q's two field vectors
     auto trace_from = [&](int s) {
         while (s < a.nsurf) {
             const int code = code_of(s);
@@ -499,7 +531,7 @@ __global__ __launch_bounds__(kBlock) RTPB_SWEEP_ATTR(NS) void sweep_kernel(Sweep
                     for (int q = 0; q < kSweepRays; ++q) n_next[q] = (BUNDLE || q == 0) ? mat_n(q, s + 1) : n_next[0];
                     auto none = [](const Ray<double>&) {};
                     Ray<double> o[kSweepRays];
-                    [[maybe_unused]] double at[kSweepRays][kTrans ? 6 : 3];
+                    [[maybe_unused]] double at[kSweepRays][kTrans || kPol ? 6 : 3];
 #pragma unroll
                     for (int q = 0; q < kSweepRays; ++q) {
                         const DevSurface<double> sd = (BUNDLE || q == 0) ? surface_for(q, s, base)
@@ -507,7 +539,7 @@ __global__ __launch_bounds__(kBlock) RTPB_SWEEP_ATTR(NS) void sweep_kernel(Sweep
                         if constexpr (kHistory) {
                             auto keep = [&](const Ray<double>& p) {
                                 at[q][0] = p.x; at[q][1] = p.y; at[q][2] = p.z;
-                                if constexpr (kTrans) {
+                                if constexpr (kTrans || kPol) {
                                     at[q][3] = p.dx; at[q][4] = p.dy; at[q][5] = p.dz;
                                 }
                             };
@@ -519,7 +551,28 @@ __global__ __launch_bounds__(kBlock) RTPB_SWEEP_ATTR(NS) void sweep_kernel(Sweep
                                                               kCarry ? &rxy[q] : nullptr);
                         }
                     }
-                    if constexpr (kTrans) {
+                    if constexpr (kPol) {
+                        // the surface's coating, the analyser and the call's 2^q_bits: the block's, so scalar loads
+                        const cptr<SweepPol> hd = Mode::head(a);
+                        const cptr<double> cp = Mode::tail(a) + kTransCoat * s;
+                        const double coat_mode = cp[0], coat_amp = cp[1];
+                        const double scale = hd->scale;
+                        const double w_an[3] = {hd->w[0], hd->w[1], hd->w[2]};
+                        PolRay acc = pol_none();
+#pragma unroll
+                        for (int q = 0; q < kSweepRays; ++q) {
+                            const bool pass = foot_finite3(at[q][0], at[q][1], at[q][2]) &&
+                                              foot_finite3(o[q].x, o[q].y, o[q].z);
+                            pol_surface(pass, at[q][3], at[q][4], at[q][5], o[q].dx, o[q].dy, o[q].dz, n_cur[q],
+                                        n_next[q], coat_mode, coat_amp, pol[q]);
+                            if (live[q] && pass) pol_merge(acc, pol_term(pol[q], o[q].dx, o[q].dy, o[q].dz, w_an, scale));
+                        }
+                        pol_wave_reduce(acc);
+                        if ((tid & 63) == 0) {
+#pragma unroll
+                            for (int c = 0; c < kPolCols; ++c) pol_tab[tid >> 6][s][c] = acc.v[c];
+                        }
+                    } else if constexpr (kTrans) {
                         // the surface's coating and the call's 2^q_bits: the block's, so scalar loads
                         const cptr<double> cp = Mode::tail(a) + kTransCoat * s;
                         const double coat_mode = cp[0], coat_value = cp[1];
@@ -637,8 +690,26 @@ __global__ __launch_bounds__(kBlock) RTPB_SWEEP_ATTR(NS) void sweep_kernel(Sweep
 #pragma unroll
             for (int q = 0; q < kSweepRays; ++q) cum[q] = 1.0;
         }
+        if constexpr (kPol) {
+            // the launch, from the generated ray's direction and the call's polariser
+            const cptr<SweepPol> hd = Mode::head(a);
+            const double u[3] = {hd->u[0], hd->u[1], hd->u[2]};
+#pragma unroll
+            for (int q = 0; q < kSweepRays; ++q) pol_launch(r[q].dx, r[q].dy, r[q].dz, u, pol[q]);
+        }
         trace_from(0);
-        if constexpr (kTrans) {
+        if constexpr (kPol) {
+            // the block's partial: the four waves' rows combined, [group][block][surface][kPolCols]
+            __syncthreads();
+            double* out = Mode::head(a)->partials + (grp[0] * int64_t(gridDim.x) + blockIdx.x) * a.nsurf * kPolCols;
+            for (int k = tid; k < a.nsurf * kPolCols; k += kBlock) {
+                const int s = k / kPolCols, c = k % kPolCols;
+                double v = pol_tab[0][s][c];
+#pragma unroll
+                for (int w = 1; w < kBlock / 64; ++w) v = v + pol_tab[w][s][c];
+                out[k] = v;
+            }
+        } else if constexpr (kTrans) {
             // the block's partial: the four waves' rows combined, [group][block][surface][kTransCols]
             __syncthreads();
             double* out = Mode::head(a)->partials + (grp[0] * int64_t(gridDim.x) + blockIdx.x) * a.nsurf * kTransCols;
